@@ -7,7 +7,7 @@ of the hot path: Philox normals -> GBM stepping -> the (253 x 10M) fp64 matrix w
 per-path payoff -> wavefront-shuffle reduction -> (N>1: one all-reduce of 3 doubles) -> price.
 Inputs are parameters only, so everything is resident when the timed region starts.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,8 +19,13 @@ Weak scaling: every rank owns `--paths` global path ids [rank*paths, (rank+1)*pa
 stream; no data-path collective except the payoff / moment all-reduces.  The collective is the library's built-in RCCL
 communicator (mcg_comm_init_rank: issued from C on the ctx's stream, nothing on the host waits per date); `--collective
 torch` routes it through torch.distributed instead.  Prints ONE JSON line on rank 0 with the driver's contract fields
-plus "roofline", "cpu_baseline" (N=1 only) and "extra.configs":
-  * N = 1 (default run): C3, C4 and the C5 shard timed once each after the headline loop, the three other pricers of
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall-clock ms of one timed step), the config and the price.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  `--full` adds everything else this script measures, after the timed steps:
+"roofline" (kernel events around the timed launches, the board's write ceiling, the shader clock), "cpu_baseline" (N=1
+only) and "extra.configs":
+  * N = 1: C3, C4 and the C5 shard timed once each after the headline loop, the three other pricers of
     the driver on the C3 matrix and the batched driver rows (SURVEY 8f), the cold first launch of C2;
   * N > 1: BASELINE.json configs[4] (C5: rBergomi American put LSM, 8M paths per GPU -- N = 8 is the 64M-path job)
     timed after the C2 loop without any exchange ("none": every rank prices its own shard, the baseline) and through each
@@ -57,6 +62,33 @@ def bs_call(S0, K, r, sigma, T):
     d2 = d1 - sigma * math.sqrt(T)
     N = lambda x: 0.5 * math.erfc(-x / math.sqrt(2.0))  # noqa: E731
     return S0 * N(d1) - K * math.exp(-r * T) * N(d2)
+
+
+DUMP_COLUMNS = 4096     # path columns of the matrix sample --dump-outputs writes (all n_steps + 1 dates of each)
+DUMP_SAMPLE_SEED = 12345
+
+
+def dump_outputs(out_dir, P, price, se, begin, hw, device) -> None:
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, as float64 .npy files -- the price
+    and its standard error, and a fixed sample of the device path matrix (the full one is 8 * (n_steps + 1) bytes per path):
+    DUMP_COLUMNS columns drawn with a fixed seed, every date of each, step-major [n_steps + 1][columns], plus the global path
+    ids of those columns.  Same arguments, same files: two builds can be compared output for output."""
+    import numpy as np
+    import torch
+
+    from montecarlooptionspricer_amd.engine import _DevView
+    os.makedirs(out_dir, exist_ok=True)
+    rows = P.n_steps + 1
+    k = max(1, min(P.n_paths, DUMP_COLUMNS, (32 << 20) // (8 * rows)))     # the sample stays under 32 MB
+    cols = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(P.n_paths, size=k, replace=False))
+    hw.synchronize()
+    dev = torch.device("cuda", device)
+    mat = torch.as_tensor(_DevView(P.device_ptr, rows * P.ld), device=dev).view(rows, P.ld)
+    sample = mat.index_select(1, torch.as_tensor(cols, device=dev)).cpu().numpy()
+    np.save(os.path.join(out_dir, "price.npy"), np.array([price], dtype=np.float64))
+    np.save(os.path.join(out_dir, "std_err.npy"), np.array([se], dtype=np.float64))
+    np.save(os.path.join(out_dir, "paths_sample.npy"), np.ascontiguousarray(sample, dtype=np.float64))
+    np.save(os.path.join(out_dir, "paths_sample_path_ids.npy"), (cols + begin).astype(np.float64))
 
 
 def cpu_baseline(n_steps: int, budget_s: float = 15.0) -> dict:
@@ -195,8 +227,14 @@ def main() -> None:
     ap.add_argument("--config", default="c2", choices=["c2", "c5"], help="c2: GBM European (headline); c5: rBergomi LSM shard")
     ap.add_argument("--paths", type=int, default=0, help="paths per GPU (default: 10M for c2, 8M for c5)")
     ap.add_argument("--time-steps", type=int, default=252)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3/C4/C5-shard timings after the headline loop")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (kernel events, board write ceiling, shader clock), "
+                         "CPU baselines, the rows of extra.configs and, at N > 1, the C5 rows; a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (price, std_err and a fixed sample of columns "
+                         "of the path matrix, float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="(--full) skip the C3/C4/C5-shard timings after the headline loop")
     ap.add_argument("--collective", default=os.environ.get("MCG_COLLECTIVE", "auto"), choices=["auto", "shm", "ipc", "rccl", "torch"],
                     help="auto: ipc for c5 (the LSM sweeps exchange inside the kernel through a mailbox in peer-mapped device memory; "
                          "falls back to shm = the same mailbox in host memory, then rccl, then torch), rccl for c2")
@@ -218,6 +256,10 @@ def main() -> None:
     ap.add_argument("--c5-child", action="store_true",
                     help="(internal) this process is one rank of the child job that times the C5 rows of an N > 1 run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.rehearsal:
+        ap.error("--dump-outputs needs a real run: a rehearsal computes nothing")
     if args.paths <= 0:
         args.paths = 10_000_000 if args.config == "c2" else 8_000_000
 
@@ -299,11 +341,13 @@ def main() -> None:
         k_main = N.K_GBM
         alg_bytes = 8.0 * (n_steps + 1) * count          # 8*(steps+1) B written per path
 
-        def one_pass():
+        def one_pass(keep=False):
             P = eng.gbm(seed, S0, r, sigma, dt, n_steps, count, path_begin=begin, payoff=(K, True))
             price, se = eng.price_european(P, K, r, T, True)
+            if keep:
+                return price, se, P
             P.free()
-            return price, se
+            return price, se, None
 
         def ramp_launch():
             eng.gbm(seed, S0, r, sigma, dt, n_steps, count, path_begin=begin).free()
@@ -311,11 +355,13 @@ def main() -> None:
         k_main = N.K_RBERGOMI
         alg_bytes = 8.0 * (n_steps + 1) * count
 
-        def one_pass():
+        def one_pass(keep=False):
             P = eng.rbergomi(seed, RB["S0"], RB["r"], RB["xi"], RB["H"], RB["eta"], RB["rho"], dt, n_steps, count, path_begin=begin)
             price, se = eng.price_lsm(P, RB["r"], K, T, dt, False, 2)
+            if keep:
+                return price, se, P
             P.free()
-            return price, se
+            return price, se, None
 
         def ramp_launch():
             eng.rbergomi(seed, RB["S0"], RB["r"], RB["xi"], RB["H"], RB["eta"], RB["rho"], dt, n_steps, count, path_begin=begin).free()
@@ -344,34 +390,40 @@ def main() -> None:
         eng.synchronize()
         hw.synchronize()
 
-    # the very first launch of the measured kernel in this process, on a device that has been idle: reported, not timed
-    eng.timing_enable(True)
+    # the very first launch of the measured kernel in this process, on a device that has been idle: reported (--full), not timed
+    eng.timing_enable(args.full)
     eng.timing_reset()
     ramp_launch()
     eng.synchronize()
-    cold_ms = eng.timing_get(k_main)[0]
+    cold_ms = eng.timing_get(k_main)[0] if args.full else None
     eng.timing_enable(False)
     run_ramp()  # also ahead of the W warm-up steps: every launch of the measured kernel variant runs at the steady clock,
     #             so the rocprofv3 average over all of them agrees with the average over the K timed ones
     for _ in range(args.warmup):
         one_pass()
     fence(ramp=True)
-    # HIP events around the kernels the roofline is computed from only (an event pair costs several microseconds on the
-    # stream; the reductions behind the generator and the transfers are not bracketed inside the timed region)
-    eng.timing_select([k_main] if args.config == "c2" else [k_main, N.K_LSM_SWEEP])
-    eng.timing_enable(True)
-    eng.timing_reset()
+    # --full: HIP events around the kernels the roofline is computed from only (an event pair costs several microseconds on
+    # the stream; the reductions behind the generator and the transfers are not bracketed inside the timed region)
+    if args.full:
+        eng.timing_select([k_main] if args.config == "c2" else [k_main, N.K_LSM_SWEEP])
+        eng.timing_enable(True)
+        eng.timing_reset()
+    keep_last = args.steps - 1 if (args.dump_outputs and rank == 0) else -1   # the matrix of the last step outlives it
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        price, se = one_pass()
+    for i in range(args.steps):
+        price, se, kept = one_pass(keep=i == keep_last)
     fence()
     elapsed = time.perf_counter() - t0
-    eng.timing_select(None)
+    if args.full:
+        eng.timing_select(None)
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept, price, se, begin, hw, device)
+        kept.free()
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev_name)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    mode = c5_rows_mode(args, world) if (dist is not None and args.config == "c2" and not args.no_extra) else "off"
+    mode = c5_rows_mode(args, world) if (args.full and dist is not None and args.config == "c2" and not args.no_extra) else "off"
 
     def c5_rows_after(out):
         """BASELINE.json configs[4] at this N, through every collective in turn (all ranks take part; rank 0 reports) -- AFTER
@@ -403,11 +455,11 @@ def main() -> None:
     k_ms, k_n = eng.timing_get(k_main)
     sweep_ms, sweep_n = eng.timing_get(N.K_LSM_SWEEP)
     solve_ms, solve_n = eng.timing_get(N.K_LSM_SOLVE)
-    # What lets a reader tell a slow board from a regression (boards of one pool differ by ~10 % on this power-limited
+    # --full: what lets a reader tell a slow board from a regression (boards of one pool differ by ~10 % on this power-limited
     # kernel): the shader clock the timed launches ran at, stamped inside the last one by ~60 workgroups, and -- right after
     # the timed region, device still at load -- what THIS board writes with the matrix's store pattern and no arithmetic.
     clock, ceiling = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             eng.timing_enable(False)
             if args.config == "c2":   # one ARMED launch right behind the timed ones (device at load): the timed launches carry no stamps
@@ -424,10 +476,10 @@ def main() -> None:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_paths * args.steps / elapsed / 1e6
         k_avg_ms = k_ms / max(k_n, 1)
-        achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9
+        achieved = alg_bytes / (k_avg_ms * 1e-3) / 1e9 if k_avg_ms > 0 else None   # (no kernel events without --full)
         traffic, traffic_source = None, None
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if args.config == "c2" and os.path.exists(pmc):
+        if args.full and args.config == "c2" and os.path.exists(pmc):
             try:
                 j = json.load(open(pmc))
                 if j.get("paths") == count and j.get("time_steps") == n_steps:
@@ -462,22 +514,24 @@ def main() -> None:
                        "sharding": sharding, "collective": collective,
                        "S0": S0, "K": K, "r": r, "sigma": sigma if args.config == "c2" else None, "seed": seed,
                        "untimed_ramp_launches": RAMP_LAUNCHES},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": kernel_name,
-                         "kernel_avg_ms": k_avg_ms, "launches": int(k_n),
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "board_write_ceiling_GBs": ceiling[0] if ceiling else None,
-                         "board_write_ceiling_ms_per_launch": ceiling[1] if ceiling else None,
-                         "frac_of_board_ceiling": achieved / ceiling[0] if ceiling else None,
-                         "board_write_ceiling_source": "mcg_probe_write_ceiling: 5 launches, right after the timed region, of a kernel that "
-                                                       "stores the same matrix with the generator's store pattern and no arithmetic",
-                         "shader_clock_GHz": clock,
-                         "shader_clock_source": "s_memtime / s_memrealtime stamps of ~40 workgroups of one armed k_gbm_paths launch right behind the timed "
-                                                "ones (mcg_generator_clock_arm / mcg_generator_clock)" if clock else None},
             "parity": parity,
         }
-        if args.config == "c5":
+        if args.full:
+            out["roofline"] = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                "kernel": kernel_name,
+                "kernel_avg_ms": k_avg_ms, "launches": int(k_n),
+                "algorithmic_bytes_per_launch": alg_bytes,
+                "board_write_ceiling_GBs": ceiling[0] if ceiling else None,
+                "board_write_ceiling_ms_per_launch": ceiling[1] if ceiling else None,
+                "frac_of_board_ceiling": achieved / ceiling[0] if ceiling else None,
+                "board_write_ceiling_source": "mcg_probe_write_ceiling: 5 launches, right after the timed region, of a kernel that "
+                                              "stores the same matrix with the generator's store pattern and no arithmetic",
+                "shader_clock_GHz": clock,
+                "shader_clock_source": "s_memtime / s_memrealtime stamps of ~40 workgroups of one armed k_gbm_paths launch right behind the timed "
+                                       "ones (mcg_generator_clock_arm / mcg_generator_clock)" if clock else None}
+        if args.full and args.config == "c5":
             per_pass = max(args.steps, 1)
             one_launch = sweep_n // per_pass <= 2
             design = (16.0 if one_launch else 32.0) * n_steps * count
@@ -505,7 +559,7 @@ def main() -> None:
                         out["roofline"]["lsm"]["traffic_per_launch"] = j5["lsm_per_date_launch"]["hbm_bytes_per_launch"]
                 except Exception:
                     pass
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cb = cpu_baseline(n_steps)
                 ref_price = cb.pop("_ref_price", None)
@@ -515,7 +569,7 @@ def main() -> None:
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "Mpaths/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {e}"}
-        if world == 1 and dist is None and args.config == "c2" and not args.no_extra:
+        if args.full and world == 1 and dist is None and args.config == "c2" and not args.no_extra:
             try:
                 out["parity"]["rough_regime_vs_reference_sample"] = rough_regime_parity(eng)
                 base = None

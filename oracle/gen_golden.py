@@ -5,6 +5,7 @@ TEST INFRASTRUCTURE ONLY.  Run in the dev container (where /root/reference exist
 
     make -C oracle && python oracle/gen_golden.py
     make -C oracle && python oracle/gen_golden.py --eigen     # only where an Eigen3 exists: the LSM / MartingaleOptimization pin
+    make -C oracle && python oracle/gen_golden.py --samples   # tests/golden/reference_samples.npz alone (capture_samples)
 
 The reference has no tests and no golden vectors of its own, so every
 deterministic function on the hot path is pinned by calling the reference's own compiled code on
@@ -55,9 +56,50 @@ def capture_eigen() -> None:
     print("Eigen", ".".join(map(str, ver)), "-> tests/golden/lsm.npz, tests/golden/martingale.npz")
 
 
+# the inputs of tests/test_oracle_golden.py::test_live_reference_random_inputs, drawn in this order from RandomState(5)
+LIVE_CASES = [(33, 0.2, 0.7), (128, 0.45, 2.5), (300, 0.07, 1.1)]
+EST_KEYS = ("xi", "H", "eta", "rho", "S0")
+# tests/test_oracle_models.py: the reference's unseeded class-level sample and its branching upper bounds
+MT_SAMPLE_PATHS, MT_SAMPLE_STEPS = 60_000, 40
+BRANCHING_CALLS = 24
+
+
+def capture_samples() -> None:
+    """--samples: tests/golden/reference_samples.npz, what the tests that compare against the compiled reference read where it
+    is absent (a checkout has no reference tree): the rough-volatility building blocks and the estimators on the random inputs of
+    test_live_reference_random_inputs; the log-returns of one unseeded class-level sample (1001-point synthetic history, 60 000
+    paths x 40 steps) for the two statistics tests; BRANCHING_CALLS upper bounds of BranchingProcesses on the branching fixture."""
+    ref = Reference()
+    out = {}
+    rs = np.random.RandomState(5)
+    for i, (steps, H, eta) in enumerate(LIVE_CASES):
+        lam = ref.lam(steps, H)
+        phi = ref.phi(lam, H)
+        Z = rs.standard_normal(steps) + 1j * rs.standard_normal(steps)
+        X = ref.fractional_gaussian(phi, Z, H, eta)
+        out[f"lam_{i}"], out[f"phi_{i}"], out[f"X_{i}"] = lam, phi, X
+        out[f"fv_{i}"] = ref.forward_variance(X, 0.09, H, eta)
+    h = 80.0 * np.exp(np.cumsum(0.02 * rs.standard_normal(777)))
+    _, p = ref.estimators(h)
+    out["est"] = np.array([p[k] for k in EST_KEYS])
+    hist = synthetic_history(1001, seed=42)
+    a = ref.generate_paths(hist, MT_SAMPLE_STEPS, MT_SAMPLE_PATHS)
+    out["mt_first_col"] = a[:, 0]
+    out["mt_logret"] = np.log(a[:, -1] / a[:, 0])
+    paths = np.load(os.path.join(OUT, "asymptotic.npz"))["paths"]
+    ex = np.load(os.path.join(OUT, "branching.npz"))["ex_all"]
+    out["branching_upper"] = np.array([ref.branching_price(paths, 0.04, 100.0, 40 / 252.0, 1 / 252.0, False, 10, ex)[2]
+                                       for _ in range(BRANCHING_CALLS)])
+    np.savez_compressed(os.path.join(OUT, "reference_samples.npz"), **out)
+    print("tests/golden/reference_samples.npz", os.path.getsize(os.path.join(OUT, "reference_samples.npz")), "bytes")
+
+
 def main() -> None:
     if "--eigen" in sys.argv[1:]:
         capture_eigen()
+        return
+    if "--samples" in sys.argv[1:]:
+        capture_samples()
         return
     os.makedirs(OUT, exist_ok=True)
     ref = Reference()

@@ -24,7 +24,7 @@ def _free_port():
 
 def _run(world, fail="", extra=(), timeout=420, env_extra=None, want_rc=0):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "2", "--warmup", "1",
            "--rehearsal", "--paths", "250000", "--c5-paths", "100001", *extra]
     env = dict(os.environ, MCG_REHEARSAL_FAIL=fail, OMP_NUM_THREADS="1", **(env_extra or {}))
     p = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)

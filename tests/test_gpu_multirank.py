@@ -180,7 +180,7 @@ def test_bench_two_ranks_carries_c2_and_c5_with_the_ranks_seen(tmp_path):
     root = os.path.dirname(HERE)
     c2_paths, c5_paths = 1_000_000, 300_000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--paths", str(c2_paths), "--c5-paths", str(c5_paths)]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -229,7 +229,7 @@ def test_bench_headline_survives_a_failing_c5_child_job():
     line -- the C2 headline -- is still printed, with a row that says what happened."""
     root = os.path.dirname(HERE)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--paths", "500000", "--c5-paths", "100000"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MCG_BENCH_C5_CHILD_FAIL="1")
     p = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
@@ -249,7 +249,7 @@ def test_bench_two_ranks_with_the_c5_rows_inline():
     root = os.path.dirname(HERE)
     c2_paths, c5_paths = 500_000, 200_000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--paths", str(c2_paths), "--c5-paths", str(c5_paths), "--c5-rows", "inline", "--c5-collectives", "none,ipc,rccl"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -277,7 +277,7 @@ def test_bench_four_ranks_take_the_rows_inline_by_themselves():
     root = os.path.dirname(HERE)
     c2_paths, c5_paths = 400_000, 100_000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "4", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--paths", str(c2_paths), "--c5-paths", str(c5_paths), "--c5-collectives", "none,shm"]
     # (four persistent sweeps spinning on ONE card take seconds per pass: one mailbox row is enough here; the peer-memory
     #  mailbox at four ranks is test_two_rank_processes_equal_single_rank[ipc4])

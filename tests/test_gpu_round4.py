@@ -221,7 +221,7 @@ def test_bench_line_attributes_its_own_variance():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
                        cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
@@ -231,6 +231,38 @@ def test_bench_line_attributes_its_own_variance():
     assert abs(r["frac_of_board_ceiling"] - r["achieved"] / r["board_write_ceiling_GBs"]) < 1e-12 and 0.5 < r["frac_of_board_ceiling"] < 1.05
     c = r["shader_clock_GHz"]
     assert c["stamping_workgroups"] >= 32 and 0.8 < c["GHz_min"] <= c["GHz_median"] <= c["GHz_max"] < 2.7
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """A plain bench.py run times the steps and prints the headline only (no roofline, baselines or extra rows); with
+    --dump-outputs it writes the last step's price, std-err and a seeded column sample of its matrix, float64 -- the same
+    numbers the engine gives for the same seed and path range."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n_paths, steps = 300_000, 252
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--paths", str(n_paths),
+                        "--dump-outputs", str(tmp_path)], cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    j = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["dtype"] == "f64" and j["higher_is_better"] is True
+    assert abs(j["value"] - n_paths / (j["ms_per_step"] * 1e-3) / 1e6) <= 1e-9 * j["value"]
+    assert not {"roofline", "cpu_baseline", "extra"} & set(j)
+    got = {n: np.load(tmp_path / f"{n}.npy") for n in ("price", "std_err", "paths_sample", "paths_sample_path_ids")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    cols = got["paths_sample_path_ids"].astype(np.int64)
+    assert got["paths_sample"].shape == (steps + 1, 4096) and len(np.unique(cols)) == 4096 and cols.max() < n_paths
+    e = mc.PathEngine(0)
+    P = e.gbm(SEED, 100.0, 0.04, 0.2, DT, steps, n_paths, payoff=(100.0, True))
+    price, se = e.price_european(P, 100.0, 0.04, steps * DT, True)
+    want = P.to_host_step_major()[:, cols]
+    P.free()
+    e.close()
+    assert got["price"][0] == j["parity"]["price"] and abs(price - got["price"][0]) <= 1e-12 * price
+    assert abs(se - got["std_err"][0]) <= 1e-9 * se
+    assert np.array_equal(got["paths_sample"], want)
 
 
 # ------------------------------------------------------------------------------------------------

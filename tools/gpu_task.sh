@@ -21,14 +21,14 @@ task=${1:?task}; T=${2:-r5}; shift; shift || true
 O=gpurun_out
 mkdir -p $O
 guard() { rc=$?; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "step killed at its limit (rc=$rc): stopping"; exit $rc; fi; return $rc; }
-C2="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
+C2="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
 case $task in
 suite)
   timeout -k 10 1000 python -m pytest tests -m gpu -q --durations=8 > $O/${T}_pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -14 $O/${T}_pytest.log; exit $rc ;;
 tests)
   timeout -k 10 900 python -m pytest tests -m gpu -q -x -k "$1" > $O/${T}_pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -14 $O/${T}_pytest.log; exit $rc ;;
 bench)
-  timeout -k 10 900 python3 bench.py "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err; rc=$?; echo "bench rc=$rc"; tail -3 $O/${T}_bench.err; head -c 1500 $O/${T}_bench.json; exit $rc ;;
+  timeout -k 10 900 python3 bench.py --full "$@" > $O/${T}_bench.json 2> $O/${T}_bench.err; rc=$?; echo "bench rc=$rc"; tail -3 $O/${T}_bench.err; head -c 1500 $O/${T}_bench.json; exit $rc ;;
 limiter)
   timeout -k 10 1100 python3 tools/pmc_passes.py --tag ${T}_c2lim --kernels "k_gbm_paths<true,k_probe_write" \
     --group "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
@@ -56,13 +56,13 @@ rblimiter) # round 6: the same attribution for the rBergomi generator (C5 shard'
     --group "SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 GRBM_GUI_ACTIVE" \
     -- python3 tools/bench_configs.py --configs c5,c4 --reps 4 2>&1 | tee $O/${T}_rblim.log; guard ;;
 stats)
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_stats -- python3 bench.py "$@" > $O/${T}_stats.log 2>&1; rc=$?; echo "stats rc=$rc"; tail -2 $O/${T}_stats.log; exit $rc ;;
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_stats -- python3 bench.py --full "$@" > $O/${T}_stats.log 2>&1; rc=$?; echo "stats rc=$rc"; tail -2 $O/${T}_stats.log; exit $rc ;;
 ab)
   timeout -k 10 900 tools/ab_libs.sh ${3:-c2} ${4:-4} $1 $2 2>&1 | tee $O/${T}_ab.log; guard ;;
 two-rank)
   for mode in inline child off; do
     timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
-      bench.py --gpus 2 --steps 3 --warmup 1 --backend gloo --paths 2000000 --c5-paths 1000000 --c5-rows $mode "$@" \
+      bench.py --full --gpus 2 --steps 3 --warmup 1 --backend gloo --paths 2000000 --c5-paths 1000000 --c5-rows $mode "$@" \
       > $O/${T}_two_rank_$mode.json 2> $O/${T}_two_rank_$mode.err; rc=$?; echo "two-rank $mode rc=$rc"; guard || exit $rc
     head -c 600 $O/${T}_two_rank_$mode.json; echo
   done ;;

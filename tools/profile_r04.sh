@@ -8,11 +8,11 @@ export TMPDIR=/tmp
 ROOT=$(pwd)
 O=$ROOT/gpurun_out
 mkdir -p $O
-BENCH="python3 bench.py --steps 10 --warmup 3"                                   # the driver's default line: C2 + C3/C4/C5 + the 8(f) rows
-C2="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
-C5="python3 bench.py --config c5 --steps 5 --warmup 2 --no-cpu-baseline"         # one-launch sweep, no collective
-C5D="python3 bench.py --config c5 --steps 5 --warmup 2 --no-cpu-baseline --collective rccl"   # (MCG_FORCE_DIST=1) per-date route
-C5I="python3 bench.py --config c5 --steps 5 --warmup 2 --no-cpu-baseline --collective ipc"    # (MCG_FORCE_DIST=1) peer-memory mailbox
+BENCH="python3 bench.py --full --steps 10 --warmup 3"                                   # the driver's default line: C2 + C3/C4/C5 + the 8(f) rows
+C2="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
+C5="python3 bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu-baseline"         # one-launch sweep, no collective
+C5D="python3 bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu-baseline --collective rccl"   # (MCG_FORCE_DIST=1) per-date route
+C5I="python3 bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu-baseline --collective ipc"    # (MCG_FORCE_DIST=1) peer-memory mailbox
 st() { rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1; }
 pm() { d=$1; shift; c=$1; shift; rocprofv3 --pmc $c --output-format csv -d $O/$d -- "$@" > $O/$d.log 2>&1; }
 VA="SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE"

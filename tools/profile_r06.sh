@@ -8,9 +8,9 @@ export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
 part=${1:-all}
-BENCH="python3 bench.py --steps 10 --warmup 3"
-C2="python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
-C5="python3 bench.py --config c5 --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="python3 bench.py --full --steps 10 --warmup 3"
+C2="python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extra"
+C5="python3 bench.py --full --config c5 --steps 5 --warmup 2 --no-cpu-baseline"
 st() { timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$1 -- $2 > $O/$1.log 2>&1; rc=$?; [ $rc -eq 124 ] || [ $rc -eq 137 ] && { echo "$1 killed at its limit"; exit $rc; }; return $rc; }
 pm() { d=$1; shift; c=$1; shift; timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $O/$d -- "$@" > $O/$d.log 2>&1; rc=$?; [ $rc -eq 124 ] || [ $rc -eq 137 ] && { echo "$d killed at its limit"; exit $rc; }; return $rc; }
 VA="SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE"

@@ -160,6 +160,48 @@ int mcg_price_european(mcg_ctx* ctx, const mcg_paths* paths, double K, double r,
 int mcg_price_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, double maturity,
                   double dt, int is_call, int poly_order, double* mean, double* std_err);
 
+/* ---- Greeks ----------------------------------------------------------------------------- */
+/* Price sensitivities with Monte Carlo standard errors.  Every field an entry point does not fill is NaN, and so is its
+ * std error.  dual_delta = dP/dK.  Repeated calls on the same matrix are bit-identical (fixed-order reductions).
+ * Neither call changes mcg_lsm_one_launch_enabled or anything mcg_price_* reads.
+ * Errors: a ctx with a collective (mcg_set_allreduce, RCCL, shm) -> MCG_ERR_INVALID (sharded Greeks are not supported
+ * yet); an empty matrix -> MCG_ERR_EMPTY_PATHS.
+ * Out of scope: sharded Greeks; Greeks through the one-launch LSM sweeps or the batch rows; LSM gamma, vega and rho;
+ * rBergomi vega (in xi or eta); Greeks of MartingaleOptimization, BranchingProcesses and AsymptoticAnalysis; anything in
+ * the drop-in classes. */
+typedef struct mcg_greeks {
+    double price, delta, gamma, vega, rho, dual_delta;                    /* dual_delta = dP/dK */
+    double price_se, delta_se, gamma_se, vega_se, rho_se, dual_delta_se;  /* MC std errors      */
+} mcg_greeks;
+
+/* European Greeks from row 0 (S0) and row n_steps (S_T) only, in one pass.  f' = 1{S_T > K} (call), -1{S_T < K} (put),
+ * D = e^{-rT}, W_T = (ln(S_T/S0) - (r - sigma^2/2) T) / sigma.
+ *   price      D mean(payoff)                                  always (== mcg_price_european up to summation order)
+ *   dual_delta -D mean(f')                                     always
+ *   delta      D mean(f' S_T / S0)                             when row 0 is one positive constant
+ *   rho        -T price + D mean(f' T S_T)                     when the matrix came from mcg_paths_gbm* / mcg_paths_rbergomi*
+ *                                                              (S_T proportional to e^{rT}); NaN for mcg_paths_from_host
+ *   vega       D mean(f' S_T (W_T - sigma T))                  when sigma > 0: the caller asserts GBM with that sigma,
+ *   gamma      D K / (S0^2 sigma T) mean(1{S_T > K} W_T)       generated over horizon T at rate r (gamma: mixed pathwise /
+ *                                                              likelihood ratio, the same estimator for puts by parity)
+ * sigma <= 0 (e.g. rBergomi paths): gamma and vega are NaN. */
+int mcg_greeks_european(mcg_ctx* ctx, const mcg_paths* paths, double K, double r, double T, int is_call, double sigma,
+                        mcg_greeks* out);
+
+/* LSM (mcg_price_lsm's estimator) with its K-tangent carried through the sweep on the per-date route (one launch per
+ * exercise date whatever the path count; exercise decisions held fixed):
+ *   price      the LSM price (equal to mcg_price_lsm up to the summation order of the regression moments)
+ *   dual_delta mean(dV_0/dK)                                   always
+ *   delta      (price - K dual_delta) / S0                     when row 0 is one positive constant (the estimator is
+ *                                                              homogeneous of degree 1 in (S0, K): both generators scale
+ *                                                              with S0 and the regression is in S/K - 1)
+ * Std errors from the per-path V_0, dV_0 and (V_0 - K dV_0) / S0.  gamma, vega and rho are NaN: for fixed decisions the
+ * estimator is piecewise linear in K (a pathwise gamma is zero almost everywhere), and rho / vega need terms of the
+ * regression matrix's derivative that are not moments of the sweep -- out of scope.  poly_order in [0, 8] (else
+ * MCG_ERR_INVALID). */
+int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, double maturity, double dt, int is_call,
+                   int poly_order, mcg_greeks* out);
+
 /* Whether this ctx currently uses the one-launch LSM sweep (one launch per price up to 8.37M paths per GPU, order <= 4):
  * it is switched off for the next eight LSM prices when the in-kernel hand-shake between workgroups times out
  * (another process holding part of the GPU); mcg_price_lsm answers those -- and the call that timed out -- from the

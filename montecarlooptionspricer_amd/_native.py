@@ -34,6 +34,15 @@ class Stats(C.Structure):
         "coalesced_prefetch_hits")]
 
 
+class Greeks(C.Structure):
+    """mcg_greeks (include/mcgpu.h): price sensitivities and their Monte Carlo std errors; NaN where not computed."""
+    FIELDS = ("price", "delta", "gamma", "vega", "rho", "dual_delta")
+    _fields_ = [(k, C.c_double) for k in FIELDS] + [(k + "_se", C.c_double) for k in FIELDS]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class McgError(RuntimeError):
     """A non-zero status from libmcgpu (message = mcg_last_error()) or a missing library."""
 
@@ -128,6 +137,8 @@ def load_library():
     L.mcg_price_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp]
     L.mcg_price_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp]
     L.mcg_lsm_one_launch_enabled.argtypes = [vp, C.POINTER(C.c_int)]
+    L.mcg_greeks_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.POINTER(Greeks)]
+    L.mcg_greeks_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Greeks)]
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_compat_asymptotic_price.argtypes = [dp, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_price_martingale.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_int, dp, dp, dp]

@@ -91,7 +91,9 @@ struct WaveSums {
     }
 };
 
-template <int NV>
+// TAG: a separate instance for the same NV (the LSM K-tangent sweep's 35 moments are also k_lsm_date<12>'s: sharing one
+// instance changed the register assignment of the latter, and the price-only kernels are kept instruction for instruction).
+template <int NV, int TAG = 0>
 __device__ __forceinline__ WaveSums<NV> wave_sums_folded(const double (&v)[NV]) {
     typedef unsigned v2u __attribute__((ext_vector_type(2)));
     constexpr int N2 = WaveSums<NV>::N2, N4 = WaveSums<NV>::N4;
@@ -142,8 +144,8 @@ __device__ __forceinline__ void wave_sum_all(double (&v)[NV]) {
 }
 
 // Sum NV values per thread over a block of NW waves.  Result valid in thread 0.
-// Deterministic: fixed butterfly inside the wave, fixed wave order across waves.
-template <int NV, int NW>
+// Deterministic: fixed butterfly inside the wave, fixed wave order across waves.  TAG: see wave_sums_folded.
+template <int NV, int NW, int TAG = 0>
 __device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* NV*NW doubles */) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if constexpr (NV < 2) {
@@ -151,7 +153,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* NV*NW 
         if (lane == 0) lds[wave * NV] = v[0];
     } else {
         // folded (wave_sums_folded): value i's total sits in the 16 lanes from WaveSums::home_lane(i) on; that lane stores it
-        const WaveSums<NV> r = wave_sums_folded<NV>(v);
+        const WaveSums<NV> r = wave_sums_folded<NV, TAG>(v);
         if ((lane & 15) == 0) {
             const int row = lane >> 4;                       // row {0,1,2,3} holds value 4k + {0,2,1,3}
             const int sub = ((row & 1) << 1) | (row >> 1);

@@ -116,7 +116,8 @@ constexpr int LSM_DATE_GROUP = LSM_DATE_GROUP_N;
 constexpr int LSM_DATE_MAX_GROUPS = 2048 / LSM_DATE_GROUP;  // tickets: [0 .. MAX_GROUPS) the groups', [MAX_GROUPS] the top one
 static_assert((LSM_DATE_MAX_GROUPS + 1 + 1) / 2 <= SCALARS_DOUBLES - SC_LSM_TICKET, "the tickets fit the ctx's scalar workspace");
 
-template <int NM>
+// TAN: the K-tangent sweep's own instance, down to the block reduction (devmath.hpp: TAG).
+template <int NM, bool TAN = false>
 __device__ __forceinline__ bool lsm_date_tail(const LsmDateArgs& a, bool have, double (&m)[NM], double* red, unsigned* sm_last, int date) {
     const unsigned G = gridDim.x, n_groups = (G + LSM_DATE_GROUP - 1) / LSM_DATE_GROUP;
     const unsigned grp = blockIdx.x / LSM_DATE_GROUP, first = grp * LSM_DATE_GROUP;
@@ -124,7 +125,7 @@ __device__ __forceinline__ bool lsm_date_tail(const LsmDateArgs& a, bool have, d
     double* gsum = a.partials + (int64_t)NM * G;  // [NM][n_groups]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     static_assert(LSM_DATE_GROUP <= 64, "one member per lane");
-    if (have) block_sum<NM, 4>(m, red);
+    if (have) block_sum<NM, 4, TAN>(m, red);
     if (threadIdx.x == 0) {
         const bool hooked = a.hook_mode != 0 && date == a.hook_date && (int)blockIdx.x == a.hook_wg;
         auto send = [&]() {
@@ -200,13 +201,24 @@ __device__ __forceinline__ void lsm_date_advance(const LsmDateArgs& a, int next_
 #endif
 constexpr int LSM_DATE_DEPTH = LSM_DATE_DEPTH_N;
 
-template <int NB>
-__global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
-    constexpr int NM = 3 * NB - 1;
+// TAN (mcg_greeks_lsm): the K-tangent dV of V rides along (LsmDateTanArgs::dV, loaded and stored in the same ring slots
+// as V): with the exercise decisions held fixed, the fitted continuation is the projection of b = disc V onto a span that
+// does not involve K, so its tangent is the projection of disc dV onto the same span -- p+1 more cross sums per date
+// (NM = 4p+3) and a second right-hand side of the same solve.  Update rules mirror update() line for line.  The TAN = false
+// instances are the price-only kernels, instruction for instruction (everything TAN adds is under `if constexpr`).
+struct LsmDateTanArgs : LsmDateArgs {
+    double* dV;   // dV/dK per path, laid out like V
+};
+
+template <int NB, bool TAN = false>
+__global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN, LsmDateTanArgs, LsmDateArgs>::type a) {
+    constexpr int NM = (TAN ? 4 : 3) * NB - 1;
     constexpr int D = LSM_DATE_DEPTH;
+    static_assert(!TAN || NM <= 48, "the tangent's moments fit sm_mom and the ctx's message slot");
     __shared__ double red[NM * 4];
     __shared__ double sm_mom[48];
     __shared__ double sm_coef[LSM_COEF_STRIDE];
+    __shared__ double sm_dcoef[TAN ? LSM_COEF_STRIDE : 1];
     __shared__ double sm_ws[lsm_ws_doubles(NB)];
     __shared__ unsigned sm_last;
     const int j = (int)a.state[LSM_ST_J];
@@ -219,6 +231,8 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
     const double2* S_j = reinterpret_cast<const double2*>(a.data + (int64_t)j * a.ld);
     const double2* S_mom = reinterpret_cast<const double2*>(a.data + (int64_t)(have ? j - 1 : j) * a.ld);
     double2* V2 = reinterpret_cast<double2*>(a.V);
+    double2* dV2 = nullptr;
+    if constexpr (TAN) dV2 = reinterpret_cast<double2*>(a.dV);
     const int64_t n_units = (a.n + 1) / 2;
     const int64_t chunk = (int64_t)gridDim.x * 256;
     const int64_t n_chunks = (n_units + chunk - 1) / chunk;
@@ -226,12 +240,13 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
     const int64_t lane_unit = (int64_t)blockIdx.x * 256 + threadIdx.x;
     auto unit_of = [&](int64_t k) { return k < n_chunks ? (rev ? n_chunks - 1 - k : k) * chunk + lane_unit : n_units; };
     int64_t u[D];
-    double2 s[D], v[D], sm[D];
+    double2 s[D], v[D], sm[D], dv[D];
     auto fetch = [&](int d, int64_t k, bool with_mom) {
         u[d] = unit_of(k);
         s[d] = make_double2(0.0, 0.0);
         v[d] = make_double2(0.0, 0.0);
         sm[d] = make_double2(0.0, 0.0);
+        if constexpr (TAN) dv[d] = make_double2(0.0, 0.0);
         if (u[d] < n_units) {
             typedef double v2d __attribute__((ext_vector_type(2)));
             const v2d t = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(S_j + u[d]));  // row j is not needed again (-1.3 %)
@@ -239,11 +254,13 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
             if (need_v) v[d] = V2[u[d]];  // (V and row j-1 come back at the next launch: ordinary loads and stores, the
             //                               memory-side cache keeps part of them; nontemporal there costs 2 %)
             if (with_mom) sm[d] = S_mom[u[d]];
+            if constexpr (TAN)
+                if (need_v) dv[d] = dV2[u[d]];
         }
     };
 #pragma unroll
     for (int d = 0; d < D; ++d) fetch(d, d, have);  // (row j-1 is not needed by a refinement launch: wasted loads on those rare ones)
-    double c[NB];
+    double c[NB], dc[NB];
     double n_itm = 0.0, center = 0.0;
     double m[NM];
 #pragma unroll
@@ -253,7 +270,11 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
 #pragma unroll
             for (int t = 0; t < NM; ++t) sm_mom[t] = a.msg[t];
             if (phase == LSM_PH_REFINED) {
-                lsm_solve_centered(sm_mom, NB, a.state[LSM_ST_MU], a.K, sm_coef, sm_ws);
+                if constexpr (TAN) lsm_solve_centered_tan(sm_mom, NB, a.state[LSM_ST_MU], a.K, sm_coef, sm_dcoef, sm_ws);
+                else lsm_solve_centered(sm_mom, NB, a.state[LSM_ST_MU], a.K, sm_coef, sm_ws);
+            } else if constexpr (TAN) {
+                static_assert(!TAN || NB <= 9, "the tangent sweep serves orders <= 8");
+                lsm_solve_nb<NB, true>(sm_mom, 1.0, a.K, sm_coef, sm_dcoef);
             } else if constexpr (NB <= 9) {
                 lsm_solve_nb<NB>(sm_mom, 1.0, a.K, sm_coef);
             } else {
@@ -275,18 +296,28 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
                     if (u[d] < n_units) {
-                        lsm_accumulate_centered<NB>(m, payoff_of(call, s[d].x, a.K) > 1e-14, s[d].x, v[d].x, a.invK, mu, a.disc);
-                        lsm_accumulate_centered<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > 1e-14, s[d].y, v[d].y,
-                                                    a.invK, mu, a.disc);
+                        if constexpr (TAN) {
+                            lsm_accumulate_centered<NB>(m, payoff_of(call, s[d].x, a.K) > 1e-14, s[d].x, v[d].x, a.invK, mu, a.disc,
+                                                        dv[d].x);
+                            lsm_accumulate_centered<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > 1e-14, s[d].y,
+                                                        v[d].y, a.invK, mu, a.disc, dv[d].y);
+                        } else {
+                            lsm_accumulate_centered<NB>(m, payoff_of(call, s[d].x, a.K) > 1e-14, s[d].x, v[d].x, a.invK, mu, a.disc);
+                            lsm_accumulate_centered<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > 1e-14, s[d].y,
+                                                        v[d].y, a.invK, mu, a.disc);
+                        }
                     }
                     fetch(d, k0 + d + D, false);
                 }
             }
-            if (lsm_date_tail<NM>(a, true, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j, LSM_PH_REFINED, mu);
+            if (lsm_date_tail<NM, TAN>(a, true, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j, LSM_PH_REFINED, mu);
             return;
         }
 #pragma unroll
         for (int q = 0; q < NB; ++q) c[q] = sm_coef[q];
+        if constexpr (TAN)
+#pragma unroll
+            for (int q = 0; q < NB; ++q) dc[q] = sm_dcoef[q];
         n_itm = sm_coef[LSM_C_COUNT];
         center = sm_coef[LSM_C_CENTER];
     }
@@ -298,6 +329,19 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
             return fmax(pay, lsm_continuation<NB>(c, center, fma(s_now, a.invK, -1.0)));
         if (pay < 1e-14) return v_old * a.disc;                         // :89-94
         return 0.0;  // payoff == 1e-14 exactly falls through both branches (:55 vs :91)
+    };
+    // (TAN) dV/dK along update(): the payoff's slope where the payoff wins fmax, the tangent fit where the fit wins
+    const double sgn = call ? -1.0 : 1.0;  // d payoff / dK in the money
+    auto tangent = [&](double s_now, double dv_old) {
+        if (phase == LSM_PH_INIT) return payoff_of(call, s_now, a.K) > 0.0 ? sgn : 0.0;
+        if (!reg) return dv_old * a.disc;
+        const double pay = payoff_of(call, s_now, a.K);
+        if (pay > 1e-14 && n_itm > 0.0) {
+            const double x = fma(s_now, a.invK, -1.0);
+            return lsm_continuation<NB>(c, center, x) > pay ? lsm_continuation<NB>(dc, center, x) : sgn;
+        }
+        if (pay < 1e-14) return dv_old * a.disc;
+        return 0.0;
     };
     auto accumulate = [&](bool live, double s_prev, double v_new) {  // regression inputs of date j-1
         if (live && payoff_of(call, s_prev, a.K) > 1e-14) {
@@ -312,6 +356,20 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
             }
         }
     };
+    auto accumulate_tan = [&](bool live, double s_prev, double v_new, double dv_new) {  // (TAN) ... and the tangent's cross sums
+        if (live && payoff_of(call, s_prev, a.K) > 1e-14) {
+            const double x = fma(s_prev, a.invK, -1.0);
+            const double y = v_new * a.disc, dy = dv_new * a.disc;
+            double pw = 1.0;
+#pragma unroll
+            for (int q = 0; q < 2 * NB - 1; ++q) {
+                m[q] += pw;
+                if (q < NB) m[2 * NB - 1 + q] = fma(pw, y, m[2 * NB - 1 + q]);
+                if (q < NB) m[3 * NB - 1 + q] = fma(pw, dy, m[3 * NB - 1 + q]);
+                pw *= x;
+            }
+        }
+    };
     for (int64_t k0 = 0; k0 < n_chunks; k0 += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
@@ -320,7 +378,14 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
                 // stored into V's slack, never counted)
                 const double2 vn = make_double2(update(s[d].x, v[d].x), update(s[d].y, v[d].y));
                 V2[u[d]] = vn;
-                if (have) {
+                if constexpr (TAN) {
+                    const double2 dvn = make_double2(tangent(s[d].x, dv[d].x), tangent(s[d].y, dv[d].y));
+                    dV2[u[d]] = dvn;
+                    if (have) {
+                        accumulate_tan(true, sm[d].x, vn.x, dvn.x);
+                        accumulate_tan(2 * u[d] + 1 < a.n, sm[d].y, vn.y, dvn.y);
+                    }
+                } else if (have) {
                     accumulate(true, sm[d].x, vn.x);
                     accumulate(2 * u[d] + 1 < a.n, sm[d].y, vn.y);
                 }
@@ -328,7 +393,7 @@ __global__ __launch_bounds__(256) void k_lsm_date(LsmDateArgs a) {
             fetch(d, k0 + d + D, have);
         }
     }
-    if (lsm_date_tail<NM>(a, have, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j - 1, LSM_PH_REGULAR, 0.0);
+    if (lsm_date_tail<NM, TAN>(a, have, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j - 1, LSM_PH_REGULAR, 0.0);
 }
 
 // What the solve needs to know about MartingaleOptimization's refit (its samples are not a row of the matrix, its driver
@@ -1428,8 +1493,10 @@ int lsm_reduce_allreduce_solve(mcg_ctx* ctx, int grid, int nm, int nb, double mi
     return MCG_OK;
 }
 
-// k_lsm_date<nb> for nb = 1 .. LSM_MAX_NB (poly_order 0 .. 15)
+// k_lsm_date<nb> for nb = 1 .. LSM_MAX_NB (poly_order 0 .. 15); the K-tangent instances for nb = 1 .. LSM_TAN_MAX_NB
 typedef void (*LsmDateKernel)(LsmDateArgs);
+typedef void (*LsmDateTanKernel)(LsmDateTanArgs);
+constexpr int LSM_TAN_MAX_NB = 9;  // poly_order <= 8: the 4p+3 moments fit the message slot and sm_mom
 static LsmDateKernel date_kernel(int nb) {
     static const LsmDateKernel k[LSM_MAX_NB] = {k_lsm_date<1>,  k_lsm_date<2>,  k_lsm_date<3>,  k_lsm_date<4>,
                                                 k_lsm_date<5>,  k_lsm_date<6>,  k_lsm_date<7>,  k_lsm_date<8>,
@@ -1437,13 +1504,20 @@ static LsmDateKernel date_kernel(int nb) {
                                                 k_lsm_date<13>, k_lsm_date<14>, k_lsm_date<15>, k_lsm_date<16>};
     return k[nb - 1];
 }
+static LsmDateTanKernel date_kernel_tan(int nb) {
+    static const LsmDateTanKernel k[LSM_TAN_MAX_NB] = {k_lsm_date<1, true>, k_lsm_date<2, true>, k_lsm_date<3, true>,
+                                                       k_lsm_date<4, true>, k_lsm_date<5, true>, k_lsm_date<6, true>,
+                                                       k_lsm_date<7, true>, k_lsm_date<8, true>, k_lsm_date<9, true>};
+    return k[nb - 1];
+}
 
 // Workgroups of k_lsm_date<nb> a CU holds at once: the per-date route launches exactly one resident wave of them.
-static int date_kernel_occupancy(int nb) {
-    static std::atomic<int> cache[LSM_MAX_NB + 1];
-    int occ = cache[nb].load(std::memory_order_relaxed);
+static int date_kernel_occupancy(int nb, bool tan = false) {
+    static std::atomic<int> cache[2][LSM_MAX_NB + 1];
+    int occ = cache[tan][nb].load(std::memory_order_relaxed);
     if (occ > 0) return occ;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)date_kernel(nb), 256, 0) != hipSuccess || occ < 1) {
+    const void* fn = tan ? (const void*)date_kernel_tan(nb) : (const void*)date_kernel(nb);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, 0) != hipSuccess || occ < 1) {
         (void)hipGetLastError();
         occ = 1;
     }
@@ -1451,23 +1525,36 @@ static int date_kernel_occupancy(int nb) {
     // tickets to the tail (C5 shard, span per pass: 10.86 ms at four, 10.69 at three and at two)
     const int want = std::max(1, study_switch("MCG_LSM_DATE_WGS_PER_CU", 3));
     occ = std::min(occ, want);
-    cache[nb].store(occ, std::memory_order_relaxed);
+    cache[tan][nb].store(occ, std::memory_order_relaxed);
     return occ;
 }
 
-static void launch_date(mcg_ctx* ctx, int nb, int grid, const LsmDateArgs& a) {
-    hipLaunchKernelGGL(date_kernel(nb), dim3(grid), dim3(256), 0, ctx->stream, a);
+static void launch_date(mcg_ctx* ctx, int nb, int grid, const LsmDateArgs& a, double* dV) {
+    if (dV) {
+        LsmDateTanArgs t;
+        static_cast<LsmDateArgs&>(t) = a;
+        t.dV = dV;
+        hipLaunchKernelGGL(date_kernel_tan(nb), dim3(grid), dim3(256), 0, ctx->stream, t);
+    } else {
+        hipLaunchKernelGGL(date_kernel(nb), dim3(grid), dim3(256), 0, ctx->stream, a);
+    }
 }
+
+// Grid of the per-date route: 512 paths per workgroup and trip, at most one resident wave, at most the tickets' groups.
+static int date_grid(mcg_ctx* ctx, int64_t N, int nb, bool tan) {
+    int grid = (int)std::min<int64_t>((N + 511) / 512, (int64_t)ctx->n_cus * date_kernel_occupancy(nb, tan));
+    grid = std::min(grid, LSM_DATE_GROUP * LSM_DATE_MAX_GROUPS);
+    return grid < 1 ? 1 : grid;
+}
+
+static int run_lsm_dates(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int nb,
+                         int grid, double* dV);
 
 int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
             int poly_order, double* mean, double* std_err) {
     const int nb = poly_order + 1;
-    const int nm = 3 * nb - 1;
     const int64_t N = P->n_paths;
-    const int M = P->n_steps + 1;
-    int grid = (int)std::min<int64_t>((N + 511) / 512, (int64_t)ctx->n_cus * date_kernel_occupancy(nb));  // 512 paths per workgroup and trip
-    grid = std::min(grid, LSM_DATE_GROUP * LSM_DATE_MAX_GROUPS);
-    if (grid < 1) grid = 1;
+    const int grid = date_grid(ctx, N, nb, false);
 
     if (N >= 1 && N <= 1024 && !ctx->allreduce && nb <= 9) {  // one launch for the whole sweep
         const double disc_s = std::exp(-r * dt);
@@ -1513,7 +1600,36 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
             return MCG_OK;
         }
     }
-    rc = ensure_cap(ctx, &ctx->lsm_v, &ctx->lsm_v_cap, (size_t)std::max<int64_t>(N, 1) + 1);  // (a whole two-path unit at the end)
+    rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, grid, nullptr);
+    if (rc) return rc;
+
+    {
+        TimedLaunch t(ctx, MCG_K_LSM_SWEEP);
+        hipLaunchKernelGGL(k_lsm_final, dim3(grid), dim3(256), 0, ctx->stream, ctx->lsm_v, N, ctx->partials);
+    }
+    MCG_HIP(hipGetLastError());
+    double s[3];
+    rc = finish_sums(ctx, grid, N, s);
+    if (rc) return rc;
+    const double n = s[2];
+    if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
+    const double m = s[0] / n;  // :97-101
+    *mean = m;
+    if (std_err) {
+        const double var = n > 1.0 ? std::max(0.0, (s[1] - n * m * m) / (n - 1.0)) : 0.0;
+        *std_err = std::sqrt(var / n);
+    }
+    return MCG_OK;
+}
+
+// The per-date sweep: every date's launch (and, sharded, its collective) up to date 0, leaving V_0 in ctx->lsm_v.
+// dV != nullptr: the K-tangent sweep (k_lsm_date<nb, true>), leaving dV_0/dK in dV (N + 1 doubles, 16-byte aligned).
+static int run_lsm_dates(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int nb,
+                         int grid, double* dV) {
+    const int nm = (dV ? 4 : 3) * nb - 1;
+    const int64_t N = P->n_paths;
+    const int M = P->n_steps + 1;
+    int rc = ensure_cap(ctx, &ctx->lsm_v, &ctx->lsm_v_cap, (size_t)std::max<int64_t>(N, 1) + 1);  // (a whole two-path unit at the end)
     if (rc) return rc;
     rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, ((size_t)grid + LSM_DATE_MAX_GROUPS) * (size_t)std::max(nm, 2));  // (k_lsm_final: 2 per workgroup)
     if (rc) return rc;
@@ -1574,7 +1690,7 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
                         return fail(MCG_ERR_COMM, "all-reduce of regression moments failed");
                 }
                 first = false;
-                launch_date(ctx, nb, grid, a);
+                launch_date(ctx, nb, grid, a, dV);
             }
         }
         g_stats.lsm_per_date_launches.fetch_add(batch, std::memory_order_relaxed);
@@ -1609,24 +1725,21 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
                                   ? std::min<int64_t>(left, second_launches * left / dates_done) : 0;
         batch = dates_left + extra;
     }
-
-    {
-        TimedLaunch t(ctx, MCG_K_LSM_SWEEP);
-        hipLaunchKernelGGL(k_lsm_final, dim3(grid), dim3(256), 0, ctx->stream, ctx->lsm_v, N, ctx->partials);
-    }
-    MCG_HIP(hipGetLastError());
-    double s[3];
-    rc = finish_sums(ctx, grid, N, s);
-    if (rc) return rc;
-    const double n = s[2];
-    if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
-    const double m = s[0] / n;  // :97-101
-    *mean = m;
-    if (std_err) {
-        const double var = n > 1.0 ? std::max(0.0, (s[1] - n * m * m) / (n - 1.0)) : 0.0;
-        *std_err = std::sqrt(var / n);
-    }
     return MCG_OK;
+}
+
+// mcg_greeks_lsm: the K-tangent sweep on the per-date route whatever the path count (single GPU), then one reduction of
+// V_0, dV_0 and the delta terms (kernels_greeks.hip).
+int run_lsm_greeks(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int poly_order,
+                   mcg_greeks* out) {
+    const int nb = poly_order + 1;
+    if (nb < 1 || nb > LSM_TAN_MAX_NB) return fail(MCG_ERR_INVALID, "poly_order must be in [0,8] for Greeks (got %d)", poly_order);
+    const int64_t N = P->n_paths;
+    int rc = ensure_cap(ctx, &ctx->lsm_dv, &ctx->lsm_dv_cap, (size_t)std::max<int64_t>(N, 1) + 1);  // padded like V
+    if (rc) return rc;
+    rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, date_grid(ctx, N, nb, true), ctx->lsm_dv);
+    if (rc) return rc;
+    return greeks_lsm_final(ctx, P, K, ctx->lsm_v, ctx->lsm_dv, out);
 }
 
 }  // namespace mcg

@@ -52,13 +52,20 @@ __device__ __forceinline__ double lsm_rsqrt(double x) {
     return fma(y * e, fma(e, 0.375, 0.5), y);
 }
 
-template <int NB>
-__device__ __forceinline__ void lsm_solve_nb(const double* moments, double min_count, double K, double* coef) {
+// TAN: the K-tangent of the sweep (mcg_greeks_lsm) -- moments[3p+2 .. 4p+3) are a second set of cross sums; dcoef[0..NB)
+// receives their solution with the SAME factorisation.  Which path is taken (fast, refine) reads the power sums only, so
+// both right-hand sides always get the same treatment.
+template <int NB, bool TAN = false>
+__device__ __forceinline__ void lsm_solve_nb(const double* moments, double min_count, double K, double* coef,
+                                             double* dcoef = nullptr) {
     constexpr int nb = NB;
     double G[NB][NB], Q[NB][NB], rhs[NB], d[NB], sol[NB], inv_piv[NB];
+    double rhs2[NB], sol2[NB];
     const double count = moments[0];
     coef[LSM_C_COUNT] = count;
     for (int a = 0; a < LSM_MAX_NB; ++a) coef[a] = 0.0;
+    if constexpr (TAN)
+        for (int a = 0; a < LSM_MAX_NB; ++a) dcoef[a] = 0.0;
     coef[LSM_C_CENTER] = 0.0;
     coef[LSM_C_REFINE] = 0.0;
     coef[LSM_C_HINT] = 0.0;
@@ -71,6 +78,7 @@ __device__ __forceinline__ void lsm_solve_nb(const double* moments, double min_c
 #pragma unroll
     for (int a = 0; a < nb; ++a) {
         rhs[a] = moments[2 * nb - 1 + a] * d[a];
+        if constexpr (TAN) rhs2[a] = moments[3 * nb - 1 + a] * d[a];
 #pragma unroll
         for (int b = 0; b < nb; ++b) G[a][b] = moments[a + b] * d[a] * d[b];
     }
@@ -135,6 +143,26 @@ __device__ __forceinline__ void lsm_solve_nb(const double* moments, double min_c
         }
 #pragma unroll
         for (int a = 0; a < nb; ++a) coef[a] = sol[a] * d[a];
+        if constexpr (TAN) {
+#pragma unroll
+            for (int i = 0; i < nb; ++i) {
+                double v = rhs2[i];
+#pragma unroll
+                for (int k = 0; k < i; ++k) v -= Q[i][k] * sol2[k];
+                sol2[i] = v;
+            }
+#pragma unroll
+            for (int i = 0; i < nb; ++i) sol2[i] *= inv_piv[i];
+#pragma unroll
+            for (int i = nb - 1; i >= 0; --i) {
+                double v = sol2[i];
+#pragma unroll
+                for (int k = i + 1; k < nb; ++k) v -= Q[k][i] * sol2[k];
+                sol2[i] = v;
+            }
+#pragma unroll
+            for (int a = 0; a < nb; ++a) dcoef[a] = sol2[a] * d[a];
+        }
         return;
     }
     // ---- no LDL^T factorisation (fewer distinct in-the-money prices than basis functions): the coefficients stay 0 and
@@ -307,19 +335,33 @@ __device__ __noinline__ void lsm_solve_centered(const double* mc, int nb, double
     }
 }
 
+// The centred re-fit of the K-tangent sweep (mcg_greeks_lsm): mc[3p+2 .. 4p+3) are the tangent's cross sums.  The
+// eigen- and singular-vector work and Eigen's rank rule read the power sums only, so the tangent coefficients are the same
+// projector applied to the tangent's right-hand side: the solve above once more with those cross sums in place (mc is
+// overwritten).  A rare path (date 0 and near-degenerate dates): two calls keep the one shared solve as it is.
+__device__ inline void lsm_solve_centered_tan(double* mc, int nb, double mu, double K, double* coef, double* dcoef, double* ws) {
+    lsm_solve_centered(mc, nb, mu, K, coef, ws);
+    for (int a = 0; a < nb; ++a) mc[2 * nb - 1 + a] = mc[3 * nb - 1 + a];
+    lsm_solve_centered(mc, nb, mu, K, dcoef, ws);
+}
+
 // Regression inputs about a centre (the refinement pass): the same sums as every kernel's first pass with
-// y = (S/K - 1) - mu in place of x.
-template <int NB>
-__device__ __forceinline__ void lsm_accumulate_centered(double (&m)[3 * NB - 1], bool itm, double s, double v, double invK, double mu,
-                                                        double disc) {
+// y = (S/K - 1) - mu in place of x.  NM = 4 NB - 1 (the K-tangent sweep): also the cross sums of the tangent dv.
+template <int NB, int NM>
+__device__ __forceinline__ void lsm_accumulate_centered(double (&m)[NM], bool itm, double s, double v, double invK, double mu,
+                                                        double disc, double dv = 0.0) {
+    static_assert(NM == 3 * NB - 1 || NM == 4 * NB - 1, "power sums + one or two sets of cross sums");
     if (itm) {
         const double yv = fma(s, invK, -1.0) - mu;
         const double b = v * disc;
+        const double db = dv * disc;
         double pw = 1.0;
 #pragma unroll
         for (int t = 0; t < 2 * NB - 1; ++t) {
             m[t] += pw;
             if (t < NB) m[2 * NB - 1 + t] = fma(pw, b, m[2 * NB - 1 + t]);
+            if constexpr (NM == 4 * NB - 1)
+                if (t < NB) m[3 * NB - 1 + t] = fma(pw, db, m[3 * NB - 1 + t]);
             pw *= yv;
         }
     }

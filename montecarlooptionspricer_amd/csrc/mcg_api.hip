@@ -302,6 +302,7 @@ int mcg_finalize(mcg_ctx* ctx) {
     if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
     if (ctx->weights) (void)hipFree(ctx->weights);
     if (ctx->lsm_v) (void)hipFree(ctx->lsm_v);
+    if (ctx->lsm_dv) (void)hipFree(ctx->lsm_dv);
     if (ctx->log_tab) (void)hipFree(ctx->log_tab);
     if (ctx->batch_fork) (void)hipEventDestroy(ctx->batch_fork);
     if (ctx->batch_join) (void)hipEventDestroy(ctx->batch_join);
@@ -360,6 +361,7 @@ static int gen_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigm
             return rc;
         }
     }
+    P->generated = true;
     *out = P;
     return MCG_OK;
 }
@@ -394,6 +396,7 @@ static int gen_rb(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, d
             return rc;
         }
     }
+    P->generated = true;
     *out = P;
     return MCG_OK;
 }
@@ -551,6 +554,34 @@ int mcg_price_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
     if (P->n_paths < 1 && !ctx->allreduce) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
     MCG_HIP(hipSetDevice(ctx->device));
     return run_lsm(ctx, P, r, K, maturity, dt, is_call, poly_order, mean, std_err);
+}
+
+// ---- Greeks ----------------------------------------------------------------------------------
+static int greeks_args(mcg_ctx* ctx, const mcg_paths* P, mcg_greeks* out) {
+    if (!ctx || !P || !out) return fail(MCG_ERR_INVALID, "ctx/paths/out is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    if (ctx->allreduce || ctx->rccl_comm || ctx->shm)
+        return fail(MCG_ERR_INVALID, "sharded Greeks are not supported yet: this ctx holds a collective");
+    return MCG_OK;
+}
+
+int mcg_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,
+                        mcg_greeks* out) {
+    int rc = greeks_args(ctx, P, out);
+    if (rc) return rc;
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_greeks_european(ctx, P, K, r, T, is_call, sigma, out);
+}
+
+int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
+                   int poly_order, mcg_greeks* out) {
+    int rc = greeks_args(ctx, P, out);
+    if (rc) return rc;
+    if (poly_order < 0 || poly_order > 8) return fail(MCG_ERR_INVALID, "poly_order must be in [0,8] for Greeks (got %d)", poly_order);
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_lsm_greeks(ctx, P, r, K, maturity, dt, is_call, poly_order, out);
 }
 
 int mcg_lsm_one_launch_enabled(mcg_ctx* ctx, int* enabled) {

@@ -99,6 +99,8 @@ struct mcg_ctx {
     size_t weights_cap = 0;
     double* lsm_v = nullptr;     // LSM value vector
     size_t lsm_v_cap = 0;
+    double* lsm_dv = nullptr;    // its K-tangent (mcg_greeks_lsm)
+    size_t lsm_dv_cap = 0;
     unsigned long long* clk_stamps = nullptr;  // [GBM_CLK_SLOTS][2] {shader cycles, 100 MHz ticks} of the last GBM launch's stamping workgroups
     int clk_slots_used = 0;
     bool clk_armed = false;                    // mcg_generator_clock_arm: only armed launches stamp (and pay the memset ahead of them)
@@ -128,6 +130,8 @@ struct mcg_paths {
     int n_steps = 0;
     int64_t ld = 0;
     uint64_t path_begin = 0;
+    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
+    bool generated = false;
     // fused terminal-payoff sums left by *_payoff generators
     bool has_sums = false;
     double sums_K = 0.0;
@@ -141,6 +145,7 @@ constexpr int GBM_CLK_SLOTS = 64;     // stamping workgroups of a GBM generator 
 constexpr int SCALARS_DOUBLES = 256;
 // layout of ctx->scalars (doubles)
 constexpr int SC_SUMS = 0;     // [0..3)  sum, sumsq, n
+constexpr int SC_GREEKS = 4;   // [4..18) Greeks sums: {sum, sum^2} of up to six estimators, then min and max of row 0
 constexpr int SC_COEF = 40;    // [40..60) the LSM coefficient block of the current date (lsm_device.hpp: LSM_C_*)
 constexpr int SC_FINAL = 64;   // [64..67) LSM final sums
 constexpr int SC_BARRIER = 72; // [72] 32-bit timeout flag of k_lsm_coop's hand-shake
@@ -193,6 +198,12 @@ int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);
 int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
             int poly_order, double* mean, double* std_err);
+// Greeks (kernels_greeks.hip; the LSM tangent sweep in kernels_lsm.hip)
+int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,
+                        mcg_greeks* out);
+int run_lsm_greeks(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
+                   int poly_order, mcg_greeks* out);
+int greeks_lsm_final(mcg_ctx* ctx, const mcg_paths* P, double K, const double* V, const double* dV, mcg_greeks* out);
 
 // MartingaleOptimization's refit (its driver re-accumulates on request): mo_mode 1 = first pass, leave the refinement
 // request in the coefficient block; 2 = the moments are about mo_mu, solve them with lsm_solve_centered.

@@ -242,6 +242,26 @@ class PathEngine:
                                     C.byref(m), C.byref(se)))
         return m.value, se.value
 
+    def greeks_european(self, paths: PathMatrix, K: float, r: float, T: float, is_call: bool,
+                        sigma: Optional[float] = None) -> dict:
+        """European price, delta, gamma, vega, rho, dual delta and their std errors (mcg_greeks_european); NaN where a
+        Greek is not defined for these inputs.  sigma: the GBM volatility the paths were generated with (gamma, vega)."""
+        paths._alive()
+        g = N.Greeks()
+        check(self._L.mcg_greeks_european(self._ctx, paths._h, K, r, T, int(bool(is_call)),
+                                          float(sigma) if sigma is not None else 0.0, C.byref(g)))
+        return g.as_dict()
+
+    def greeks_lsm(self, paths: PathMatrix, r: float, K: float, maturity: float, dt: float, is_call: bool,
+                   poly_order: int) -> dict:
+        """LSM price, dual delta (K-tangent through the sweep) and delta by homogeneity, with std errors
+        (mcg_greeks_lsm); gamma, vega and rho are NaN."""
+        paths._alive()
+        g = N.Greeks()
+        check(self._L.mcg_greeks_lsm(self._ctx, paths._h, r, K, maturity, dt, int(bool(is_call)), int(poly_order),
+                                     C.byref(g)))
+        return g.as_dict()
+
     def lsm_one_launch_enabled(self) -> bool:
         """False once the one-launch LSM sweep's hand-shake has timed out on this ctx (mcg_lsm_one_launch_enabled)."""
         v = C.c_int()

@@ -8,7 +8,7 @@ import pytest
 
 import montecarlooptionspricer_amd as mc
 from oracle.binding import Oracle
-from test_greeks_reference import lsm_greeks_numpy
+from test_greeks_reference import lsm_greeks_numpy, lsm_tangent_numpy, mean_se
 
 pytestmark = pytest.mark.gpu
 
@@ -36,16 +36,24 @@ def row(P, j):
     return t.cpu().numpy().copy()
 
 
-def euro_numpy(s0, st, K, r, T, is_call, sigma):
+def euro_paths(s0, st, K, r, T, is_call, sigma):
+    """Per-path discounted estimators of mcg_greeks_european (its header's formulas), one array per Greek."""
     D = math.exp(-r * T)
     pay = np.maximum(0.0, st - K) if is_call else np.maximum(0.0, K - st)
     fp = (st > K).astype(float) if is_call else -(st < K).astype(float)
-    g = {"price": D * pay.mean(), "dual_delta": -D * fp.mean(), "delta": D * (fp * st / s0).mean(),
-         "rho": D * (T * (fp * st - pay)).mean()}
+    x = {"price": D * pay, "dual_delta": -D * fp, "delta": D * (fp * st / s0), "rho": D * (T * (fp * st - pay))}
     if sigma:
         w = (np.log(st / s0) - (r - 0.5 * sigma * sigma) * T) / sigma
-        g["vega"] = D * (fp * st * (w - sigma * T)).mean()
-        g["gamma"] = D * (np.where(st > K, w * K / (sigma * T), 0.0) / (s0 * s0)).mean()
+        x["vega"] = D * (fp * st * (w - sigma * T))
+        x["gamma"] = D * (np.where(st > K, w * K / (sigma * T), 0.0) / (s0 * s0))
+    return x
+
+
+def euro_numpy(s0, st, K, r, T, is_call, sigma):
+    """Means and std errors (ddof 1, over sqrt n; 0 for one path) of euro_paths: {Greek: mean, Greek_se: se}."""
+    g = {}
+    for k, x in euro_paths(s0, st, K, r, T, is_call, sigma).items():
+        g[k], g[k + "_se"] = mean_se(x)
     return g
 
 
@@ -190,3 +198,301 @@ def test_refusals_and_no_side_effects(eng):
                 call()
         Q.free()
     P.free()
+
+
+# ---- every order, every strike band, the std errors, edge shapes, host matrices, generators ---------------------------
+# Tolerances (GPU vs the float64 numpy reference of the same estimator, relative): 1e-8 at orders <= 3, where the fast
+# LDL^T solve decides every date with a path spread; 2e-6 at orders >= 4, where every date with a path in the money is
+# re-fitted through lsm_solve_centered(_tan), which follows the reference's rank rule on raw monomials (the price's band in
+# test_gpu_parity's test_lsm_high_orders_follow_the_reference_rank_rule).  The std errors sit in the band of their means.
+LSM_R, LSM_DT, LSM_STEPS = 0.04, 0.02, 29
+
+
+def lsm_tol(poly):
+    return 1e-8 if poly <= 3 else 2e-6
+
+
+def bs_all(S, K, r, sigma, T, is_call):
+    """Black-Scholes price and the five Greeks mcg_greeks_european estimates (dual_delta = dP/dK)."""
+    from math import erf, exp, sqrt
+    Nc = lambda x: 0.5 * (1 + erf(x / sqrt(2)))  # noqa: E731
+    g, gamma, vega = bs(S, K, r, sigma, T, is_call)
+    d1 = (math.log(S / K) + (r + 0.5 * sigma * sigma) * T) / (sigma * sqrt(T))
+    d2 = d1 - sigma * sqrt(T)
+    D = exp(-r * T)
+    if is_call:
+        g.update(price=S * Nc(d1) - K * D * Nc(d2), dual_delta=-D * Nc(d2))
+    else:
+        g.update(price=K * D * Nc(-d2) - S * Nc(-d1), dual_delta=D * Nc(-d2))
+    g.update(gamma=gamma, vega=vega)
+    return g
+
+
+def close(a, b, tol):
+    """|a - b| <= tol |b|, and exactly equal when b is 0 (a zero reference leaves no room)."""
+    return a == b if b == 0.0 else abs(a - b) <= tol * abs(b)
+
+
+def gen(eng, model, seed, n, steps=LSM_STEPS, S0=100.0, dt=LSM_DT, path_begin=0, payoff=None):
+    if model == "gbm":
+        return eng.gbm(seed, S0, LSM_R, 0.2, dt, steps, n, path_begin=path_begin, payoff=payoff)
+    return eng.rbergomi(seed, S0, LSM_R, RB["xi"], RB["H"], RB["eta"], RB["rho"], dt, steps, n, path_begin=path_begin,
+                        payoff=payoff)
+
+
+def greeks_lsm_counted(eng, P, K, mat, dt, is_call, poly):
+    """greeks_lsm and the number of re-fit launches (lsm_solve_centered_tan) the sweep took."""
+    mc.stats(reset=True)
+    g = eng.greeks_lsm(P, LSM_R, K, mat, dt, is_call, poly)
+    return g, mc.stats()["lsm_per_date_refits"]
+
+
+def check_lsm(g, ref, poly, with_se=True):
+    """GPU Greeks vs lsm_greeks_numpy: price, dual_delta, delta and (with_se) their std errors, NaN where the reference
+    has NaN.  Prints the observed relative errors."""
+    tol = lsm_tol(poly)
+    errs = {}
+    for k in ("price", "dual_delta", "delta"):
+        for f in (k, k + "_se") if with_se else (k,):
+            if math.isnan(ref[f]):
+                assert math.isnan(g[f]), (f, g[f])
+                continue
+            errs[f] = abs(g[f] - ref[f]) / abs(ref[f]) if ref[f] else abs(g[f])
+            assert close(g[f], ref[f], tol), (f, g[f], ref[f], tol)
+    print(f"lsm-err poly={poly} " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
+    for k in ("gamma", "vega", "rho"):
+        assert math.isnan(g[k]) and math.isnan(g[k + "_se"])
+
+
+@pytest.mark.parametrize("model", ["gbm", "rbergomi"])
+@pytest.mark.parametrize("is_call", [False, True])
+@pytest.mark.parametrize("poly", list(range(9)))
+def test_lsm_every_tangent_kernel_against_numpy(eng, orc, model, is_call, poly):
+    """k_lsm_date<NB, true> for NB = 1 .. 9 at 20 000 x 30, K = S0.  At orders >= 4 the reference's rank rule sends every
+    date with a path in the money through the centred re-fit: the counter proves lsm_solve_centered_tan ran."""
+    P = gen(eng, model, 20251031 + poly, 20_000)
+    g, refits = greeks_lsm_counted(eng, P, 100.0, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)
+    if poly >= 4:
+        assert refits > 0
+    price, price_se = eng.price_lsm(P, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)
+    host = P.to_host_step_major()
+    P.free()
+    assert rel(g["price"], price) <= lsm_tol(poly) and rel(g["price_se"], price_se) <= 1e-9, (g, price, price_se)
+    assert rel(g["price"], orc.lsm_price(host, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)) <= lsm_tol(poly)
+    check_lsm(g, lsm_greeks_numpy(host, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly), poly)
+
+
+@pytest.mark.parametrize("poly", [0, 5])
+def test_lsm_tangent_many_workgroups(eng, orc, poly):
+    """200 001 paths: many per-date workgroups (512 paths each per trip), several greeks blocks, an odd path count."""
+    n = 200_001
+    P = gen(eng, "gbm", 99, n)
+    g, refits = greeks_lsm_counted(eng, P, 100.0, LSM_STEPS * LSM_DT, LSM_DT, False, poly)
+    assert (refits > 0) == (poly >= 4)
+    assert bits(eng.greeks_lsm(P, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, False, poly)) == bits(g)
+    host = P.to_host_step_major()
+    P.free()
+    assert rel(g["price"], orc.lsm_price(host, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, False, poly)) <= lsm_tol(poly)
+    check_lsm(g, lsm_greeks_numpy(host, LSM_R, 100.0, LSM_STEPS * LSM_DT, LSM_DT, False, poly), poly)
+
+
+LSM_STRIKES = [(False, 80.0), (False, 110.0), (False, 130.0), (True, 70.0), (True, 90.0), (True, 120.0)]
+
+
+@pytest.mark.parametrize("model", ["gbm", "rbergomi"])
+@pytest.mark.parametrize("is_call,K", LSM_STRIKES)
+@pytest.mark.parametrize("poly", [2, 5])
+def test_lsm_strikes(eng, orc, model, is_call, K, poly):
+    """Off-money strikes.  Put 110 / 130 and call 90 / 70 put date 0 in the money: every path regresses on the one price
+    S0 there, a rank-1 sample that always takes the centred re-fit (also at order 2); V_0 is then one number and the
+    price's std error is rounding only."""
+    P = gen(eng, model, 4242, 20_000)
+    g, refits = greeks_lsm_counted(eng, P, K, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)
+    host = P.to_host_step_major()
+    P.free()
+    assert rel(g["price"], orc.lsm_price(host, LSM_R, K, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)) <= lsm_tol(poly)
+    V, dV = lsm_tangent_numpy(host, LSM_R, K, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)
+    ref = lsm_greeks_numpy(host, LSM_R, K, LSM_STEPS * LSM_DT, LSM_DT, is_call, poly)
+    date0_itm = (K > 100.0) != is_call
+    if date0_itm:
+        assert refits >= 1
+        assert np.ptp(V) == 0.0 and np.ptp(dV) == 0.0
+        # one-pass variance of n equal numbers: (sum2 - n m^2) / (n - 1) is rounding, ~1e-13 m^2 at most
+        assert g["price_se"] <= 1e-6 * g["price"] and g["dual_delta_se"] <= 1e-6 * abs(g["dual_delta"]), g
+    check_lsm(g, ref, poly, with_se=not date0_itm)
+
+
+def check_euro(g, ref, mean_tol=1e-12, se_tol=1e-10):
+    """GPU European Greeks vs euro_numpy on the same rows: means at mean_tol, std errors at se_tol (relative; exact when the
+    reference is 0); every field euro_numpy leaves out must be NaN."""
+    for k in FIELDS:
+        if k not in ref:
+            assert math.isnan(g[k]) and math.isnan(g[k + "_se"]), k
+            continue
+        assert close(g[k], ref[k], mean_tol), (k, g[k], ref[k])
+        assert close(g[k + "_se"], ref[k + "_se"], se_tol), (k + "_se", g[k + "_se"], ref[k + "_se"])
+
+
+@pytest.mark.parametrize("is_call", [True, False])
+@pytest.mark.parametrize("K", [60.0, 100.0, 140.0])
+def test_european_strikes_and_std_errors(eng, K, is_call):
+    """Deep in, at and deep out of the money: numpy at 1e-12 (means) and 1e-10 (std errors: a swapped or misindexed
+    partial sum is off by far more), Black-Scholes within 4 se for every Greek."""
+    r, sigma, T, steps, n = 0.04, 0.2, 1.0, 64, 1_000_000
+    P = eng.gbm(7, 100.0, r, sigma, T / steps, steps, n)
+    g = eng.greeks_european(P, K, r, T, is_call, sigma=sigma)
+    check_euro(g, euro_numpy(row(P, 0), row(P, steps), K, r, T, is_call, sigma))
+    P.free()
+    for k, v in bs_all(100.0, K, r, sigma, T, is_call).items():
+        assert abs(g[k] - v) <= 4 * g[k + "_se"], (k, g[k], v, g[k + "_se"])
+
+
+def test_european_constant_estimators(eng):
+    """K far below every S_T: a call's f' is 1 on every path, so the dual delta is the constant -D and its std error is 0
+    exactly (sums of +-1 are exact); a put's price, dual delta, delta, rho and vega are all 0 with se 0 (its gamma is not:
+    the estimator is the call's, by parity)."""
+    r, sigma, T = 0.04, 0.2, 1.0
+    P = eng.gbm(8, 100.0, r, sigma, T / 16, 16, 100_000)
+    st = row(P, 16)
+    K = 0.5 * float(st.min())
+    g = eng.greeks_european(P, K, r, T, True, sigma=sigma)
+    assert g["dual_delta"] == pytest.approx(-math.exp(-r * T), rel=1e-15, abs=0) and g["dual_delta_se"] == 0.0
+    assert g["price_se"] > 0 and g["delta_se"] > 0
+    g = eng.greeks_european(P, K, r, T, False, sigma=sigma)
+    for k in ("price", "dual_delta", "delta", "rho", "vega"):
+        assert g[k] == 0.0 and g[k + "_se"] == 0.0, (k, g[k], g[k + "_se"])
+    P.free()
+
+
+@pytest.mark.parametrize("n", [1, 3, 257, 20_001])
+@pytest.mark.parametrize("is_call", [False, True])
+def test_path_counts(eng, orc, n, is_call):
+    """Odd counts take the padding guards (a put counts a padding slot as in the money if the guard is lost); one path
+    has every std error 0; 3 paths at order 5 are rank-deficient on every date; one greeks block at n <= 256."""
+    K, mat = (110.0 if is_call else 90.0), LSM_STEPS * LSM_DT
+    P = gen(eng, "gbm", 31 + n, n)
+    host = P.to_host_step_major()
+    ge = eng.greeks_european(P, K, LSM_R, mat, is_call, sigma=0.2)
+    check_euro(ge, euro_numpy(host[0], host[-1], K, LSM_R, mat, is_call, 0.2))
+    for poly in (2, 5):
+        g = eng.greeks_lsm(P, LSM_R, K, mat, LSM_DT, is_call, poly)
+        assert close(g["price"], orc.lsm_price(host, LSM_R, K, mat, LSM_DT, is_call, poly), lsm_tol(poly))
+        check_lsm(g, lsm_greeks_numpy(host, LSM_R, K, mat, LSM_DT, is_call, poly), poly)
+        if n == 1:
+            assert g["price_se"] == g["dual_delta_se"] == g["delta_se"] == 0.0
+    if n == 1:
+        assert all(ge[k + "_se"] == 0.0 for k in FIELDS)
+    P.free()
+
+
+@pytest.mark.parametrize("is_call,K", [(False, 110.0), (True, 90.0), (False, 100.0)])
+def test_one_step(eng, orc, is_call, K):
+    """n_steps = 1: the European rows 0 and 1; LSM's only regression is date 0 (in the money for put 110 / call 90)."""
+    P = gen(eng, "gbm", 17, 5000, steps=1, dt=0.25)
+    host = P.to_host_step_major()
+    check_euro(eng.greeks_european(P, K, LSM_R, 0.25, is_call, sigma=0.2),
+               euro_numpy(host[0], host[1], K, LSM_R, 0.25, is_call, 0.2))
+    for poly in (0, 3, 6):
+        g = eng.greeks_lsm(P, LSM_R, K, 0.25, 0.25, is_call, poly)
+        assert close(g["price"], orc.lsm_price(host, LSM_R, K, 0.25, 0.25, is_call, poly), lsm_tol(poly))
+        check_lsm(g, lsm_greeks_numpy(host, LSM_R, K, 0.25, 0.25, is_call, poly), poly, with_se=K == 100.0)
+    P.free()
+
+
+@pytest.mark.parametrize("model", ["gbm", "rbergomi"])
+@pytest.mark.parametrize("poly", [2, 5])
+def test_lsm_maturity_before_horizon(eng, orc, model, poly):
+    """maturity < (M-1) dt: dates past maturity only discount V and dV (tangent()'s !reg branch)."""
+    P = gen(eng, model, 61, 20_000)
+    g = eng.greeks_lsm(P, LSM_R, 100.0, 0.37, LSM_DT, False, poly)
+    host = P.to_host_step_major()
+    P.free()
+    assert close(g["price"], orc.lsm_price(host, LSM_R, 100.0, 0.37, LSM_DT, False, poly), lsm_tol(poly))
+    check_lsm(g, lsm_greeks_numpy(host, LSM_R, 100.0, 0.37, LSM_DT, False, poly), poly)
+
+
+def test_host_matrices_and_ties(eng):
+    """from_host: no rho; delta only with a constant row 0.  Ties S == K exactly: f' = 0 for call and put (European), the
+    payoff-0 branch on exercise dates (LSM).  An all out-of-the-money matrix: price, dual delta and se exactly 0."""
+    K, r, dt, steps, n = 100.0, 0.04, 0.05, 10, 4000
+    rs = np.random.RandomState(5)
+    pm = K * np.exp(np.cumsum(0.04 * rs.standard_normal((n, steps + 1)), axis=1))
+    pm[:, 0] = K
+    pm[::7, -1] = K        # ties at maturity
+    pm[1::5, 3:8] = K      # ties on exercise dates
+    H = eng.from_host(pm)
+    sm = pm.T
+    for is_call in (True, False):
+        g = eng.greeks_european(H, K, r, steps * dt, is_call, sigma=0.2)
+        ref = euro_numpy(sm[0], sm[-1], K, r, steps * dt, is_call, 0.2)
+        ref.pop("rho"), ref.pop("rho_se")
+        check_euro(g, ref)
+        for poly in (1, 4):
+            g = eng.greeks_lsm(H, r, K, steps * dt, dt, is_call, poly)
+            assert not math.isnan(g["delta"])
+            check_lsm(g, lsm_greeks_numpy(sm, r, K, steps * dt, dt, is_call, poly), poly)
+    H.free()
+    # row 0 varying: delta NaN, the rest still numpy's
+    pm[:, 0] = K + rs.rand(n)
+    H = eng.from_host(pm)
+    for poly in (1, 4):
+        g = eng.greeks_lsm(H, r, K, steps * dt, dt, False, poly)
+        ref = lsm_greeks_numpy(pm.T, r, K, steps * dt, dt, False, poly)
+        assert math.isnan(ref["delta"]) and math.isnan(g["delta"]) and math.isnan(g["delta_se"])
+        check_lsm(g, ref, poly)
+    H.free()
+    # all out of the money (puts, every S > K): zeros, not NaN
+    H = eng.from_host(150.0 + rs.rand(501, steps + 1))
+    ge = eng.greeks_european(H, K, r, steps * dt, False)
+    gl = eng.greeks_lsm(H, r, K, steps * dt, dt, False, 3)
+    for g in (ge, gl):
+        for k in ("price", "dual_delta"):
+            assert g[k] == 0.0 and g[k + "_se"] == 0.0, (k, g)
+    H.free()
+
+
+@pytest.mark.parametrize("model", ["gbm", "rbergomi"])
+def test_fused_payoff_generators_and_path_begin(eng, model):
+    """Matrices from the fused-payoff generators give bit-identical Greeks to the plain ones (same seed); matrices that
+    start at path_begin != 0 are still generated (rho reported) and match numpy on their own rows."""
+    K, T, steps = 100.0, 0.5, 25
+    P = gen(eng, model, 123, 10_000, steps=steps, dt=T / steps)
+    for is_call in (False, True):
+        F = gen(eng, model, 123, 10_000, steps=steps, dt=T / steps, payoff=(K, is_call))
+        assert bits(eng.greeks_european(F, K, LSM_R, T, is_call)) == bits(eng.greeks_european(P, K, LSM_R, T, is_call))
+        for poly in (2, 5):
+            assert bits(eng.greeks_lsm(F, LSM_R, K, T, T / steps, is_call, poly)) == \
+                bits(eng.greeks_lsm(P, LSM_R, K, T, T / steps, is_call, poly))
+        F.free()
+    P.free()
+    Q = gen(eng, model, 123, 4_000, steps=steps, dt=T / steps, path_begin=1000)
+    host = Q.to_host_step_major()
+    g = eng.greeks_european(Q, K, LSM_R, T, False)
+    check_euro(g, euro_numpy(host[0], host[-1], K, LSM_R, T, False, None))
+    assert not math.isnan(g["rho"])
+    check_lsm(eng.greeks_lsm(Q, LSM_R, K, T, T / steps, False, 2), lsm_greeks_numpy(host, LSM_R, K, T, T / steps, False, 2), 2)
+    Q.free()
+
+
+@pytest.mark.parametrize("model", ["gbm", "rbergomi"])
+@pytest.mark.parametrize("poly", [0, 5, 8])
+@pytest.mark.parametrize("is_call,K", [(True, 105.0), (False, 95.0)])
+def test_lsm_delta_by_homogeneity_at_truncating_orders(eng, model, poly, is_call, K):
+    """Delta = (price - K dual_delta) / S0 against a central difference in S0 through the generators, at orders where the
+    fit follows the rank rule on raw monomials (not scale-free term by term).  Relative step by the gap rule (fd_step):
+    half the smallest |S_ij - K| / S_ij, so no path changes an in-the-money set within +-h.  Observed <= 4e-8 relative at
+    every order (the fixed seeds make it deterministic); 1e-6 leaves 25x room."""
+    r, dt, steps, n, S0 = LSM_R, LSM_DT, LSM_STEPS, 20_000, 100.0
+    P = gen(eng, model, 77, n)
+    g = eng.greeks_lsm(P, r, K, steps * dt, dt, is_call, poly)
+    host = P.to_host_step_major()
+    P.free()
+    h = 0.5 * float(np.min(np.abs(host[1:] - K) / host[1:]))
+    prices = []
+    for s0 in (S0 * (1 + h), S0 * (1 - h)):
+        Q = gen(eng, model, 77, n, S0=s0)
+        prices.append(eng.price_lsm(Q, r, K, steps * dt, dt, is_call, poly)[0])
+        Q.free()
+    fd = (prices[0] - prices[1]) / (2 * h * S0)
+    print(f"homogeneity {model} poly={poly} K={K} h={h:.1e} delta={g['delta']:.8f} fd={fd:.8f} rel={rel(g['delta'], fd):.1e}")
+    assert rel(g["delta"], fd) <= 1e-6, (g["delta"], fd, h)

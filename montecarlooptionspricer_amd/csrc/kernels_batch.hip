@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void k_batch_martingale(BatchArgs a) {
         for (int q = 0; q < NM; ++q) mc[q] = 0.0;
         if (live) {
 #pragma unroll
-            for (int s = 0; s < 2; ++s) lsm_accumulate_centered<NB>(mc, true, xs[s], ys[s], invK, mu, 1.0);
+            for (int s = 0; s < 2; ++s) lsm_accumulate_moments<NB>(mc, true, xs[s], ys[s], invK, mu, 1.0);
         }
         block_sum<NM, 4>(mc, red);
         if (threadIdx.x == 0) {

@@ -145,10 +145,9 @@ static int greeks_reduce(mcg_ctx* ctx, int n_blocks, int ne, double* host) {
 
 // mean and standard error of an estimator from its sum and sum of squares over n paths, times `scale`
 static void mean_se(double sum, double sum2, double n, double scale, double* mean, double* se) {
-    const double m = sum / n;
-    const double var = n > 1.0 ? std::max(0.0, (sum2 - n * m * m) / (n - 1.0)) : 0.0;
-    *mean = scale * m;
-    *se = std::fabs(scale) * std::sqrt(var / n);
+    sums_to_mean_stderr(sum, sum2, n, mean, se);
+    *mean = scale * *mean;
+    *se = std::fabs(scale) * *se;
 }
 
 static void greeks_all_nan(mcg_greeks* out) {

@@ -204,7 +204,7 @@ constexpr int LSM_DATE_DEPTH = LSM_DATE_DEPTH_N;
 // TAN (mcg_greeks_lsm): the K-tangent dV of V rides along (LsmDateTanArgs::dV, loaded and stored in the same ring slots
 // as V): with the exercise decisions held fixed, the fitted continuation is the projection of b = disc V onto a span that
 // does not involve K, so its tangent is the projection of disc dV onto the same span -- p+1 more cross sums per date
-// (NM = 4p+3) and a second right-hand side of the same solve.  Update rules mirror update() line for line.  The TAN = false
+// (NM = 4p+3) and a second right-hand side of the same solve.  The TAN = false
 // instances are the price-only kernels, instruction for instruction (everything TAN adds is under `if constexpr`).
 struct LsmDateTanArgs : LsmDateArgs {
     double* dV;   // dV/dK per path, laid out like V
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
         s[d] = make_double2(0.0, 0.0);
         v[d] = make_double2(0.0, 0.0);
         sm[d] = make_double2(0.0, 0.0);
-        if constexpr (TAN) dv[d] = make_double2(0.0, 0.0);
+        dv[d] = make_double2(0.0, 0.0);  // (unused without TAN)
         if (u[d] < n_units) {
             typedef double v2d __attribute__((ext_vector_type(2)));
             const v2d t = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(S_j + u[d]));  // row j is not needed again (-1.3 %)
@@ -296,16 +296,10 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
                     if (u[d] < n_units) {
-                        if constexpr (TAN) {
-                            lsm_accumulate_centered<NB>(m, payoff_of(call, s[d].x, a.K) > 1e-14, s[d].x, v[d].x, a.invK, mu, a.disc,
-                                                        dv[d].x);
-                            lsm_accumulate_centered<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > 1e-14, s[d].y,
-                                                        v[d].y, a.invK, mu, a.disc, dv[d].y);
-                        } else {
-                            lsm_accumulate_centered<NB>(m, payoff_of(call, s[d].x, a.K) > 1e-14, s[d].x, v[d].x, a.invK, mu, a.disc);
-                            lsm_accumulate_centered<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > 1e-14, s[d].y,
-                                                        v[d].y, a.invK, mu, a.disc);
-                        }
+                        lsm_accumulate_moments<NB>(m, payoff_of(call, s[d].x, a.K) > LSM_ITM_EPS, s[d].x, v[d].x, a.invK, mu,
+                                                   a.disc, dv[d].x);
+                        lsm_accumulate_moments<NB>(m, 2 * u[d] + 1 < a.n && payoff_of(call, s[d].y, a.K) > LSM_ITM_EPS, s[d].y,
+                                                   v[d].y, a.invK, mu, a.disc, dv[d].y);
                     }
                     fetch(d, k0 + d + D, false);
                 }
@@ -325,50 +319,28 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
         if (phase == LSM_PH_INIT) return payoff_of(call, s_now, a.K);  // LSMPricer.cpp:37-40
         if (!reg) return v_old * a.disc;                                // :43-49
         const double pay = payoff_of(call, s_now, a.K);
-        if (pay > 1e-14 && n_itm > 0.0)                                 // :78-86
+        if (pay > LSM_ITM_EPS && n_itm > 0.0)                           // :78-86
             return fmax(pay, lsm_continuation<NB>(c, center, fma(s_now, a.invK, -1.0)));
-        if (pay < 1e-14) return v_old * a.disc;                         // :89-94
-        return 0.0;  // payoff == 1e-14 exactly falls through both branches (:55 vs :91)
+        if (pay < LSM_ITM_EPS) return v_old * a.disc;                   // :89-94
+        return 0.0;  // payoff == LSM_ITM_EPS exactly falls through both branches (:55 vs :91)
     };
-    // (TAN) dV/dK along update(): the payoff's slope where the payoff wins fmax, the tangent fit where the fit wins
+    // (TAN) dV/dK along update(), branch for branch: the payoff's slope where the payoff wins fmax, the tangent fit where
+    // the fit wins
     const double sgn = call ? -1.0 : 1.0;  // d payoff / dK in the money
     auto tangent = [&](double s_now, double dv_old) {
         if (phase == LSM_PH_INIT) return payoff_of(call, s_now, a.K) > 0.0 ? sgn : 0.0;
         if (!reg) return dv_old * a.disc;
         const double pay = payoff_of(call, s_now, a.K);
-        if (pay > 1e-14 && n_itm > 0.0) {
+        if (pay > LSM_ITM_EPS && n_itm > 0.0) {
             const double x = fma(s_now, a.invK, -1.0);
             return lsm_continuation<NB>(c, center, x) > pay ? lsm_continuation<NB>(dc, center, x) : sgn;
         }
-        if (pay < 1e-14) return dv_old * a.disc;
+        if (pay < LSM_ITM_EPS) return dv_old * a.disc;
         return 0.0;
     };
-    auto accumulate = [&](bool live, double s_prev, double v_new) {  // regression inputs of date j-1
-        if (live && payoff_of(call, s_prev, a.K) > 1e-14) {
-            const double x = fma(s_prev, a.invK, -1.0);
-            const double y = v_new * a.disc;
-            double pw = 1.0;
-#pragma unroll
-            for (int q = 0; q < 2 * NB - 1; ++q) {
-                m[q] += pw;
-                if (q < NB) m[2 * NB - 1 + q] = fma(pw, y, m[2 * NB - 1 + q]);
-                pw *= x;
-            }
-        }
-    };
-    auto accumulate_tan = [&](bool live, double s_prev, double v_new, double dv_new) {  // (TAN) ... and the tangent's cross sums
-        if (live && payoff_of(call, s_prev, a.K) > 1e-14) {
-            const double x = fma(s_prev, a.invK, -1.0);
-            const double y = v_new * a.disc, dy = dv_new * a.disc;
-            double pw = 1.0;
-#pragma unroll
-            for (int q = 0; q < 2 * NB - 1; ++q) {
-                m[q] += pw;
-                if (q < NB) m[2 * NB - 1 + q] = fma(pw, y, m[2 * NB - 1 + q]);
-                if (q < NB) m[3 * NB - 1 + q] = fma(pw, dy, m[3 * NB - 1 + q]);
-                pw *= x;
-            }
-        }
+    auto accumulate = [&](bool live, double s_prev, double v_new, double dv_new) {  // regression inputs of date j-1
+        lsm_accumulate_moments<NB>(m, live && payoff_of(call, s_prev, a.K) > LSM_ITM_EPS, s_prev, v_new, a.invK, 0.0, a.disc,
+                                   dv_new);
     };
     for (int64_t k0 = 0; k0 < n_chunks; k0 += D) {
 #pragma unroll
@@ -378,16 +350,14 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
                 // stored into V's slack, never counted)
                 const double2 vn = make_double2(update(s[d].x, v[d].x), update(s[d].y, v[d].y));
                 V2[u[d]] = vn;
+                double2 dvn = make_double2(0.0, 0.0);
                 if constexpr (TAN) {
-                    const double2 dvn = make_double2(tangent(s[d].x, dv[d].x), tangent(s[d].y, dv[d].y));
+                    dvn = make_double2(tangent(s[d].x, dv[d].x), tangent(s[d].y, dv[d].y));
                     dV2[u[d]] = dvn;
-                    if (have) {
-                        accumulate_tan(true, sm[d].x, vn.x, dvn.x);
-                        accumulate_tan(2 * u[d] + 1 < a.n, sm[d].y, vn.y, dvn.y);
-                    }
-                } else if (have) {
-                    accumulate(true, sm[d].x, vn.x);
-                    accumulate(2 * u[d] + 1 < a.n, sm[d].y, vn.y);
+                }
+                if (have) {
+                    accumulate(true, sm[d].x, vn.x, dvn.x);
+                    accumulate(2 * u[d] + 1 < a.n, sm[d].y, vn.y, dvn.y);
                 }
             }
             fetch(d, k0 + d + D, have);
@@ -456,10 +426,8 @@ __global__ __launch_bounds__(256) void k_lsm_reduce_solve(const double* partials
 }
 
 template <int NB, int PPT>
-__global__ __launch_bounds__(256) void k_lsm_small(const double* data, int64_t ld, int n, int n_cols, double r_unused,
-                                                   double K, double maturity, double dt, double disc, int is_call,
-                                                   double* out3) {
-    (void)r_unused;
+__global__ __launch_bounds__(256) void k_lsm_small(const double* data, int64_t ld, int n, int n_cols, double K, double maturity,
+                                                   double dt, double disc, int is_call, double* out3) {
     lsm_small_body<NB, PPT>(data, ld, n, n_cols, K, maturity, dt, disc, is_call, out3);
 }
 
@@ -485,7 +453,7 @@ static void launch_small_nb(mcg_ctx* ctx, const mcg_paths* P, double K, double m
                            P->n_steps + 1, K, maturity, dt, disc, is_call, out3);
     else
         hipLaunchKernelGGL((k_lsm_small<NB, 4>), dim3(1), dim3(256), 0, ctx->stream, P->data, P->ld, (int)P->n_paths,
-                           P->n_steps + 1, 0.0, K, maturity, dt, disc, is_call, out3);
+                           P->n_steps + 1, K, maturity, dt, disc, is_call, out3);
 }
 
 // sum V, sum V^2 -> partials[grid][2]
@@ -789,7 +757,7 @@ __device__ __forceinline__ double lsm_pay(const LsmPay& p, double s) { return fm
 template <int NB>
 __device__ __forceinline__ void lsm_accumulate(double (&m)[3 * NB - 1], const LsmPay& p, double s, double v, double invK,
                                                double disc) {
-    const double w = lsm_pay(p, s) > 1e-14 ? 1.0 : 0.0;  // regression inputs, LSMPricer.cpp:51-74
+    const double w = lsm_pay(p, s) > LSM_ITM_EPS ? 1.0 : 0.0;  // regression inputs, LSMPricer.cpp:51-74
     const double x = fma(s, invK, -1.0);
     const double y = v * disc;
     double pw = w;
@@ -821,11 +789,11 @@ __device__ __forceinline__ double lsm_update(const LsmPay& p, double s, double v
                                              double invK, double disc) {  // LSMPricer.cpp:78-94
     const double pay = lsm_pay(p, s);
     const double cont = lsm_continuation<NB>(c, center, fma(s, invK, -1.0));
-    // payoff == 1e-14 exactly falls through both of the reference's branches (:55 vs :91) and keeps 0
+    // payoff == LSM_ITM_EPS exactly falls through both of the reference's branches (:55 vs :91) and keeps 0
     // The two selects are written as v_cndmask on a ballot mask: from `c ? a : b` hipcc builds a divergent branch
     // around the polynomial here, i.e. four extra basic blocks and two exec-mask round trips per path.
-    const double v = lsm_select(__builtin_amdgcn_ballot_w64(pay < 1e-14), v_old, 0.0) * disc;
-    return lsm_select(__builtin_amdgcn_ballot_w64(pay > 1e-14) & any_itm, fmax(pay, cont), v);
+    const double v = lsm_select(__builtin_amdgcn_ballot_w64(pay < LSM_ITM_EPS), v_old, 0.0) * disc;
+    return lsm_select(__builtin_amdgcn_ballot_w64(pay > LSM_ITM_EPS) & any_itm, fmax(pay, cont), v);
 }
 
 // Second launch bound = workgroups per CU the register budget must allow.
@@ -893,16 +861,7 @@ __global__ __launch_bounds__(256, (PPT >= 8 ? 2 : 3)) void k_lsm_coop(LsmCoopArg
         for (int t = 0; t < NP; ++t) mp[t] = 0.0;
 #pragma unroll
         for (int q = 0; q < PPT; ++q) {
-            const double s = row[q];
-            if (q < n_live && payoff_of(call, s, a.K) > 1e-14) {
-                const double x = fma(s, a.invK, -1.0);
-                double pw = 1.0;
-#pragma unroll
-                for (int t = 0; t < NP; ++t) {
-                    mp[t] += pw;
-                    pw *= x;
-                }
-            }
+            if (q < n_live && payoff_of(call, row[q], a.K) > LSM_ITM_EPS) lsm_power_sums<NB>(mp, fma(row[q], a.invK, -1.0));
         }
     };
     bool early = false;
@@ -913,17 +872,8 @@ __global__ __launch_bounds__(256, (PPT >= 8 ? 2 : 3)) void k_lsm_coop(LsmCoopArg
         for (int t = 0; t < NB; ++t) mc[t] = 0.0;
 #pragma unroll
         for (int q = 0; q < PPT; ++q) {
-            const double s = s_j[q];
-            if (q < n_live && payoff_of(call, s, a.K) > 1e-14) {
-                const double x = fma(s, a.invK, -1.0);
-                const double y = V[q] * a.disc;
-                double pw = 1.0;
-#pragma unroll
-                for (int t = 0; t < NB; ++t) {
-                    mc[t] = fma(pw, y, mc[t]);
-                    pw *= x;
-                }
-            }
+            if (q < n_live && payoff_of(call, s_j[q], a.K) > LSM_ITM_EPS)
+                lsm_cross_sums<NB>(mc, fma(s_j[q], a.invK, -1.0), V[q] * a.disc);
         }
         LSM_TRACE(round, 1);  // moments accumulated
         if (!early) {  // (uniform) first regression date, or no prefetch: the power sums go out with the cross sums
@@ -966,7 +916,8 @@ __global__ __launch_bounds__(256, (PPT >= 8 ? 2 : 3)) void k_lsm_coop(LsmCoopArg
             for (int q = 0; q < NM; ++q) m[q] = 0.0;
 #pragma unroll
             for (int q = 0; q < PPT; ++q)
-                lsm_accumulate_centered<NB>(m, q < n_live && payoff_of(call, s_j[q], a.K) > 1e-14, s_j[q], V[q], a.invK, mu, a.disc);
+                lsm_accumulate_moments<NB>(m, q < n_live && payoff_of(call, s_j[q], a.K) > LSM_ITM_EPS, s_j[q], V[q], a.invK, mu,
+                                           a.disc);
             lsm_exchange<NB>(a, m, LSM_AREA_REFINE, gave_up, red, sm_mom, sm_coef, true, mu, sm_ws, round++, []() {});
         }
         double c[NB];
@@ -979,9 +930,9 @@ __global__ __launch_bounds__(256, (PPT >= 8 ? 2 : 3)) void k_lsm_coop(LsmCoopArg
             const double pay = payoff_of(call, s, a.K);
             const double vn = V[q] * a.disc;
             double v;
-            if (pay > 1e-14 && n_itm > 0.0) {
+            if (pay > LSM_ITM_EPS && n_itm > 0.0) {
                 v = fmax(pay, lsm_continuation<NB>(c, center, fma(s, a.invK, -1.0)));
-            } else if (pay < 1e-14) {
+            } else if (pay < LSM_ITM_EPS) {
                 v = vn;
             } else {
                 v = 0.0;
@@ -1191,8 +1142,8 @@ __global__ __launch_bounds__(256, 2) void k_lsm_big(LsmCoopArgs a) {
 #pragma unroll
             for (int u = 0; u < NU; ++u) {
                 const double2 sv = sanitize(*reinterpret_cast<const double2*>(unit_ptr(row_j, u)), u);
-                lsm_accumulate_centered<NB>(m, lsm_pay(pf, sv.x) > 1e-14, sv.x, V[2 * u], a.invK, mu, a.disc);
-                lsm_accumulate_centered<NB>(m, lsm_pay(pf, sv.y) > 1e-14, sv.y, V[2 * u + 1], a.invK, mu, a.disc);
+                lsm_accumulate_moments<NB>(m, lsm_pay(pf, sv.x) > LSM_ITM_EPS, sv.x, V[2 * u], a.invK, mu, a.disc);
+                lsm_accumulate_moments<NB>(m, lsm_pay(pf, sv.y) > LSM_ITM_EPS, sv.y, V[2 * u + 1], a.invK, mu, a.disc);
                 if ((u % 4) == 3) asm volatile("" ::: "memory");
             }
             lsm_publish_partials<NB>(a, m, G, wg, LSM_AREA_REFINE, red);
@@ -1556,6 +1507,9 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
     const int64_t N = P->n_paths;
     const int grid = date_grid(ctx, N, nb, false);
 
+    int rc;
+    bool done = false;
+    double s3[3];
     if (N >= 1 && N <= 1024 && !ctx->allreduce && nb <= 9) {  // one launch for the whole sweep
         const double disc_s = std::exp(-r * dt);
         double* d3 = ctx->scalars + SC_SUMS;
@@ -1576,29 +1530,15 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
         MCG_HIP(hipGetLastError());
         MCG_HIP(hipMemcpyAsync(ctx->h_scalars + SC_SUMS, d3, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         MCG_HIP(hipStreamSynchronize(ctx->stream));
-        const double n = ctx->h_scalars[SC_SUMS + 2], m = ctx->h_scalars[SC_SUMS] / n;
-        *mean = m;
-        if (std_err) {
-            const double var = n > 1.0 ? std::max(0.0, (ctx->h_scalars[SC_SUMS + 1] - n * m * m) / (n - 1.0)) : 0.0;
-            *std_err = std::sqrt(var / n);
-        }
-        return MCG_OK;
-    }
-    int rc;
-    if ((N > 1024 && !ctx->allreduce) || shm_mailbox_device(ctx)) {  // (with the node mailbox every rank asks: they agree inside)
-        bool done = false;
-        double s3[3];
+        for (int q = 0; q < 3; ++q) s3[q] = ctx->h_scalars[SC_SUMS + q];
+        done = true;
+    } else if ((N > 1024 && !ctx->allreduce) || shm_mailbox_device(ctx)) {  // (with the node mailbox every rank asks: they agree inside)
         rc = run_lsm_coop(ctx, P, r, K, maturity, dt, is_call, nb, s3, &done);
         if (rc) return rc;
-        if (done) {
-            const double n = s3[2], m = s3[0] / n;
-            *mean = m;
-            if (std_err) {
-                const double var = n > 1.0 ? std::max(0.0, (s3[1] - n * m * m) / (n - 1.0)) : 0.0;
-                *std_err = std::sqrt(var / n);
-            }
-            return MCG_OK;
-        }
+    }
+    if (done) {  // the small-path and the one-launch sweeps end here
+        sums_to_mean_stderr(s3[0], s3[1], s3[2], mean, std_err);
+        return MCG_OK;
     }
     rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, grid, nullptr);
     if (rc) return rc;
@@ -1613,12 +1553,7 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
     if (rc) return rc;
     const double n = s[2];
     if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
-    const double m = s[0] / n;  // :97-101
-    *mean = m;
-    if (std_err) {
-        const double var = n > 1.0 ? std::max(0.0, (s[1] - n * m * m) / (n - 1.0)) : 0.0;
-        *std_err = std::sqrt(var / n);
-    }
+    sums_to_mean_stderr(s[0], s[1], n, mean, std_err);  // :97-101
     return MCG_OK;
 }
 

@@ -15,6 +15,10 @@ constexpr int LSM_C_HINT = 19;     //    lsm_solve_centered; the coefficients al
 constexpr int LSM_COEF_DOUBLES = 20;
 constexpr int LSM_COEF_STRIDE = 24;  // doubles between two coefficient blocks in memory / size of one in LDS
 
+// A path is in the money at a date -- enters its regression, may be exercised -- when its payoff exceeds this
+// (LSMPricer.cpp:55, :78, :91).
+constexpr double LSM_ITM_EPS = 1e-14;
+
 // LDS workspace of lsm_solve_centered for basis size nb (doubles)
 __host__ __device__ constexpr int lsm_ws_doubles(int nb) { return 7 * nb * nb + 8 * nb; }
 
@@ -345,26 +349,36 @@ __device__ inline void lsm_solve_centered_tan(double* mc, int nb, double mu, dou
     lsm_solve_centered(mc, nb, mu, K, dcoef, ws);
 }
 
-// Regression inputs about a centre (the refinement pass): the same sums as every kernel's first pass with
-// y = (S/K - 1) - mu in place of x.  NM = 4 NB - 1 (the K-tangent sweep): also the cross sums of the tangent dv.
-template <int NB, int NM>
-__device__ __forceinline__ void lsm_accumulate_centered(double (&m)[NM], bool itm, double s, double v, double invK, double mu,
-                                                        double disc, double dv = 0.0) {
-    static_assert(NM == 3 * NB - 1 || NM == 4 * NB - 1, "power sums + one or two sets of cross sums");
-    if (itm) {
-        const double yv = fma(s, invK, -1.0) - mu;
-        const double b = v * disc;
-        const double db = dv * disc;
-        double pw = 1.0;
+// Regression inputs of one in-the-money path (LSMPricer.cpp:51-74): with x = S/K - 1 - mu and y = disc V, the power
+// sums m[t] += x^t (t < 2 NB - 1) and the cross sums m[2 NB - 1 + t] += x^t y (t < NB).  mu is the literal 0.0 on a
+// date's first pass and the regressor's mean on its refinement pass.  NM = 4 NB - 1 (the K-tangent sweep): also the
+// cross sums of the tangent, m[3 NB - 1 + t] += x^t disc dV.  The two halves exist on their own because k_lsm_coop
+// sends a date's power sums, which do not depend on V, a round ahead of its cross sums.
+// m: NP power sums, then NC sets of NB cross sums (with y, with dy)
+template <int NB, int NP, int NC, class M>
+__device__ __forceinline__ void lsm_sums(M& m, double x, double y = 0.0, double dy = 0.0) {
+    double pw = 1.0;
 #pragma unroll
-        for (int t = 0; t < 2 * NB - 1; ++t) {
-            m[t] += pw;
-            if (t < NB) m[2 * NB - 1 + t] = fma(pw, b, m[2 * NB - 1 + t]);
-            if constexpr (NM == 4 * NB - 1)
-                if (t < NB) m[3 * NB - 1 + t] = fma(pw, db, m[3 * NB - 1 + t]);
-            pw *= yv;
-        }
+    for (int t = 0; t < (NP > 0 ? NP : NB); ++t) {
+        if (t < NP) m[t] += pw;
+        if (NC >= 1 && t < NB) m[NP + t] = fma(pw, y, m[NP + t]);
+        if (NC >= 2 && t < NB) m[NP + NB + t] = fma(pw, dy, m[NP + NB + t]);
+        pw *= x;
     }
+}
+template <int NB>
+__device__ __forceinline__ void lsm_power_sums(double (&mp)[2 * NB - 1], double x) {
+    lsm_sums<NB, 2 * NB - 1, 0>(mp, x);
+}
+template <int NB>
+__device__ __forceinline__ void lsm_cross_sums(double (&mc)[NB], double x, double y) {
+    lsm_sums<NB, 0, 1>(mc, x, y);
+}
+template <int NB, int NM>
+__device__ __forceinline__ void lsm_accumulate_moments(double (&m)[NM], bool itm, double s, double v, double invK, double mu,
+                                                       double disc, double dv = 0.0) {
+    static_assert(NM == 3 * NB - 1 || NM == 4 * NB - 1, "power sums + one or two sets of cross sums");
+    if (itm) lsm_sums<NB, 2 * NB - 1, NM == 4 * NB - 1 ? 2 : 1>(m, fma(s, invK, -1.0) - mu, v * disc, dv * disc);
 }
 
 // Continuation value from a coefficient block: Horner in y = x - centre (centre = 0 exactly unless refined).
@@ -430,7 +444,7 @@ __device__ __forceinline__ void lsm_small_body(const double* data, int64_t ld, i
             const int p = threadIdx.x + 256 * q;
             s_j[q] = p < n ? row[p] : 0.0;
             pay_j[q] = payoff_of(call, s_j[q], K);
-            if (p < n && pay_j[q] > 1e-14) {
+            if (p < n && pay_j[q] > LSM_ITM_EPS) {
                 const double x = fma(s_j[q], invK, -1.0);
                 const double y = V[q] * disc;
                 double pw = 1.0;
@@ -455,7 +469,8 @@ __device__ __forceinline__ void lsm_small_body(const double* data, int64_t ld, i
             for (int q = 0; q < NM; ++q) m[q] = 0.0;
 #pragma unroll
             for (int q = 0; q < PPT; ++q)
-                lsm_accumulate_centered<NB>(m, threadIdx.x + 256 * q < n && pay_j[q] > 1e-14, s_j[q], V[q], invK, mu, disc);
+                lsm_accumulate_moments<NB>(m, threadIdx.x + 256 * q < n && pay_j[q] > LSM_ITM_EPS, s_j[q], V[q], invK, mu,
+                                           disc);
             block_sum<NM, 4>(m, red);
             if (threadIdx.x == 0) {
 #pragma unroll
@@ -472,9 +487,9 @@ __device__ __forceinline__ void lsm_small_body(const double* data, int64_t ld, i
         for (int q = 0; q < PPT; ++q) {
             const double vn = V[q] * disc;
             double v;
-            if (pay_j[q] > 1e-14 && n_itm > 0.0) {
+            if (pay_j[q] > LSM_ITM_EPS && n_itm > 0.0) {
                 v = fmax(pay_j[q], lsm_continuation<NB>(c, center, fma(s_j[q], invK, -1.0)));
-            } else if (pay_j[q] < 1e-14) {
+            } else if (pay_j[q] < LSM_ITM_EPS) {
                 v = vn;
             } else {
                 v = 0.0;
@@ -550,7 +565,7 @@ __device__ __forceinline__ void lsm_wave_body(const double* data, int64_t ld, in
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int p = lane + 64 * q;
-            if (p < n && payoff_of(call, s_j[q], K) > 1e-14) {
+            if (p < n && payoff_of(call, s_j[q], K) > LSM_ITM_EPS) {
                 const double x = fma(s_j[q], invK, -1.0);
                 const double y = V[q] * disc;
                 double pw = 1.0;
@@ -572,8 +587,8 @@ __device__ __forceinline__ void lsm_wave_body(const double* data, int64_t ld, in
             for (int t = 0; t < NM; ++t) mc[t] = 0.0;
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                lsm_accumulate_centered<NB>(mc, lane + 64 * q < n && payoff_of(call, s_j[q], K) > 1e-14, s_j[q], V[q], invK, mu,
-                                            disc);
+                lsm_accumulate_moments<NB>(mc, lane + 64 * q < n && payoff_of(call, s_j[q], K) > LSM_ITM_EPS, s_j[q], V[q],
+                                           invK, mu, disc);
             wave_sum_all<NM>(mc);
             double* ws_coef = ws + lsm_ws_doubles(NB);
             if (lane == 0) lsm_solve_centered(mc, NB, mu, K, ws_coef, ws);
@@ -592,9 +607,9 @@ __device__ __forceinline__ void lsm_wave_body(const double* data, int64_t ld, in
             const double pay = payoff_of(call, s_j[q], K);
             const double vn = V[q] * disc;
             double v;
-            if (pay > 1e-14 && n_itm > 0.0) {
+            if (pay > LSM_ITM_EPS && n_itm > 0.0) {
                 v = fmax(pay, lsm_continuation<NB>(c, center, fma(s_j[q], invK, -1.0)));
-            } else if (pay < 1e-14) {
+            } else if (pay < LSM_ITM_EPS) {
                 v = vn;
             } else {
                 v = 0.0;

@@ -539,10 +539,9 @@ int mcg_price_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, dou
     const double n = s[2];
     if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
     const double disc = std::exp(-r * T);
-    const double m = s[0] / n;
-    const double var = n > 1.0 ? std::max(0.0, (s[1] - n * m * m) / (n - 1.0)) : 0.0;
-    *mean = disc * m;
-    if (std_err) *std_err = disc * std::sqrt(var / n);
+    sums_to_mean_stderr(s[0], s[1], n, mean, std_err);
+    *mean = disc * *mean;
+    if (std_err) *std_err = disc * *std_err;
     return MCG_OK;
 }
 

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -196,6 +198,15 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);
+// {sum, sum of squares, n} of an estimator -> its mean and (std_err may be null) standard error
+inline void sums_to_mean_stderr(double sum, double sum2, double n, double* mean, double* std_err) {
+    const double m = sum / n;
+    *mean = m;
+    if (std_err) {
+        const double var = n > 1.0 ? std::max(0.0, (sum2 - n * m * m) / (n - 1.0)) : 0.0;
+        *std_err = std::sqrt(var / n);
+    }
+}
 int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
             int poly_order, double* mean, double* std_err);
 // Greeks (kernels_greeks.hip; the LSM tangent sweep in kernels_lsm.hip)

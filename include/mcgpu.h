@@ -54,7 +54,8 @@ enum mcg_kernel {
     MCG_K_MARTINGALE = 7, /* MartingaleOptimization primal/offset/dual scans */
     MCG_K_BRANCHING = 8,  /* BranchingProcesses suffix-max + bounds kernels   */
     MCG_K_BATCH = 9,      /* the six kernels of mcg_batch_price_rows (one span) */
-    MCG_K_COUNT = 10
+    MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics */
+    MCG_K_COUNT = 11
 };
 
 const char* mcg_last_error(void);
@@ -201,6 +202,45 @@ int mcg_greeks_european(mcg_ctx* ctx, const mcg_paths* paths, double K, double r
  * MCG_ERR_INVALID). */
 int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, double maturity, double dt, int is_call,
                    int poly_order, mcg_greeks* out);
+
+/* ---- path-dependent European payoffs: Asian, lookback, barrier -------------------------------- */
+/* One pass over the matrix reduces every path to five statistics over the monitoring dates, rows first_row .. n_steps
+ * inclusive (0 <= first_row <= n_steps; first_row = 1 leaves S0 out):
+ *   S_T = row n_steps,  A = arithmetic mean,  G = exp(mean of ln S),  m = min,  M = max.
+ * A book of contracts is then priced on those statistics.  Undiscounted payoff per path (X is A or G):
+ *   Asian, fixed strike       call max(X - K, 0)           put max(K - X, 0)
+ *   Asian, floating strike    call max(S_T - X, 0)         put max(X - S_T, 0)          (K ignored)
+ *   lookback, fixed strike    call max(M - K, 0)           put max(K - m, 0)
+ *   lookback, floating strike call S_T - m                 put M - S_T                  (K ignored)
+ *   barrier                   an up barrier is hit when M >= barrier, a down barrier when m <= barrier (discrete
+ *                             monitoring on the dates above, plain comparisons of the stored doubles); an "out" contract
+ *                             pays the vanilla payoff of S_T (max(S_T - K, 0) / max(K - S_T, 0)) when the barrier is
+ *                             not hit, else `rebate`; an "in" contract pays it when the barrier is hit, else `rebate`.
+ *                             The rebate is paid at T.
+ * price[c] = e^{-rT} mean(payoff of contract c), std_err[c] its Monte Carlo standard error.
+ * Rules: 1 <= n_contracts <= 1024; kind in range; K, barrier and rebate finite where the kind reads them (K: fixed
+ * strikes and barriers; barrier, rebate: barriers); the paths belong to the ctx -- anything else is MCG_ERR_INVALID with a
+ * message.  An empty matrix on a ctx without a collective is MCG_ERR_EMPTY_PATHS.  Repeated calls are bit-identical
+ * (fixed-order reductions, no floating-point atomics), and a contract's result does not depend on what else is in the
+ * book or where in the book it stands.  Matrices holding non-finite values are outside the contract.
+ * Collectives: on a ctx with a collective (mcg_set_allreduce, RCCL, shm) the 2 n_contracts + 1 sums are all-reduced in one
+ * call (the node-local shm collective carries 62 doubles a call: there in pieces of 62) and every rank returns the GLOBAL
+ * prices, like mcg_price_european; `sums` lets a caller combine shards by hand.
+ * Out of scope: Greeks of these payoffs; early exercise; fusing the statistics into the generators; the batched driver
+ * rows; the drop-in classes; continuity corrections for discretely monitored barriers. */
+enum mcg_exotic_kind {
+    MCG_X_ASIAN_ARITH_FIXED = 0, MCG_X_ASIAN_ARITH_FLOAT = 1,
+    MCG_X_ASIAN_GEO_FIXED   = 2, MCG_X_ASIAN_GEO_FLOAT   = 3,
+    MCG_X_LOOKBACK_FIXED    = 4, MCG_X_LOOKBACK_FLOAT    = 5,
+    MCG_X_BARRIER_UP_OUT = 6, MCG_X_BARRIER_UP_IN = 7, MCG_X_BARRIER_DOWN_OUT = 8, MCG_X_BARRIER_DOWN_IN = 9
+};
+typedef struct mcg_exotic { int kind; int is_call; double K, barrier, rebate; } mcg_exotic;
+
+/* per-path statistics over the monitoring rows first_row .. n_steps: out5[q*n_paths + p], q = 0 S_T, 1 A, 2 G, 3 min, 4 max */
+int mcg_path_stats(mcg_ctx* ctx, const mcg_paths* paths, int first_row, double* host_out5);
+int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double T, int first_row,
+                      const mcg_exotic* book, int n_contracts,
+                      double* price, double* std_err /* may be NULL */, double* sums /* may be NULL: {sum, sum^2} per contract, then n */);
 
 /* Whether this ctx currently uses the one-launch LSM sweep (one launch per price up to 8.37M paths per GPU, order <= 4):
  * it is switched off for the next eight LSM prices when the in-kernel hand-shake between workgroups times out

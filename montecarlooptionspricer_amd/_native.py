@@ -9,9 +9,19 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("MCG_LIB") or os.path.join(_HERE, "lib", "libmcgpu.so")  # MCG_LIB: A/B experiments with another build
 
 MCG_OK = 0
-K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH = range(10)
+K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC = range(11)
 KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_SWEEP: "lsm_sweep",
-                K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows"}
+                K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
+                K_EXOTIC: "exotic"}
+
+# enum mcg_exotic_kind (include/mcgpu.h)
+(X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXED, X_ASIAN_GEO_FLOAT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT,
+ X_BARRIER_UP_OUT, X_BARRIER_UP_IN, X_BARRIER_DOWN_OUT, X_BARRIER_DOWN_IN) = range(10)
+EXOTIC_KINDS = {"asian_arith_fixed": X_ASIAN_ARITH_FIXED, "asian_arith_float": X_ASIAN_ARITH_FLOAT,
+                "asian_geo_fixed": X_ASIAN_GEO_FIXED, "asian_geo_float": X_ASIAN_GEO_FLOAT,
+                "lookback_fixed": X_LOOKBACK_FIXED, "lookback_float": X_LOOKBACK_FLOAT,
+                "barrier_up_out": X_BARRIER_UP_OUT, "barrier_up_in": X_BARRIER_UP_IN,
+                "barrier_down_out": X_BARRIER_DOWN_OUT, "barrier_down_in": X_BARRIER_DOWN_IN}
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
@@ -41,6 +51,11 @@ class Greeks(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Exotic(C.Structure):
+    """mcg_exotic (include/mcgpu.h): one path-dependent European contract."""
+    _fields_ = [("kind", C.c_int), ("is_call", C.c_int), ("K", C.c_double), ("barrier", C.c_double), ("rebate", C.c_double)]
 
 
 class McgError(RuntimeError):
@@ -139,6 +154,8 @@ def load_library():
     L.mcg_lsm_one_launch_enabled.argtypes = [vp, C.POINTER(C.c_int)]
     L.mcg_greeks_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.POINTER(Greeks)]
     L.mcg_greeks_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Greeks)]
+    newer("mcg_path_stats", [vp, vp, C.c_int, dp])
+    newer("mcg_price_exotics", [vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_compat_asymptotic_price.argtypes = [dp, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_price_martingale.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_int, dp, dp, dp]

@@ -107,6 +107,7 @@ uint64_t process_token() {  // one random word per process, never written anywhe
     return t;
 }
 constexpr int SHM_FLAG_SLOT = 63;            // entry of a rank's host slot row that carries shm_sum_flag's integer
+static_assert(SHM_ALLREDUCE_MAX < SHM_FLAG_SLOT, "an all-reduce payload must leave the flag slot alone");
 
 size_t mailbox_bytes() { return (size_t)SHM_MAX_ROUNDS * SHM_MAX_RANKS * SHM_ROW_DOUBLES * sizeof(double); }
 size_t shm_bytes() { return sizeof(ShmHeader) + mailbox_bytes(); }

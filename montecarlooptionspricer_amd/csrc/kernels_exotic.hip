@@ -1,0 +1,313 @@
+// Path-dependent European payoffs (mcg_path_stats, mcg_price_exotics): ONE pass over the monitored rows of the step-major
+// matrix reduces every path to {S_T, arithmetic mean, geometric mean, min, max} (k_path_stats: a pure HBM-read stream of
+// 8 B per path and date, 40 B per path written); a book of contracts is then evaluated on those statistics
+// (k_exotic_book: per-block {sum, sum^2} of every contract's payoff through block_sum, k_exotic_reduce: fixed order).
+// No float atomics: repeated calls are bit-identical, and a contract's sums do not depend on the rest of the book.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "devmath.hpp"
+#include "mcg_internal.hpp"
+
+namespace mcg {
+
+typedef double xs_d2 __attribute__((ext_vector_type(2)));
+
+constexpr int XS_ROWS = 8;   // rows per unrolled group: 8 x 16 B in flight per lane, 32 KiB per workgroup
+constexpr int XS_Q = 5;      // statistics per path: 0 S_T, 1 A, 2 G, 3 min, 4 max
+constexpr int XB_CH = 8;     // contracts one workgroup of k_exotic_book keeps in registers
+constexpr int XB_NF = 2 * XB_CH;
+
+template <int W>
+__device__ __forceinline__ void xs_load(const double* p, double (&x)[W]) {
+    if constexpr (W == 2) {
+        const xs_d2 v = __builtin_nontemporal_load(reinterpret_cast<const xs_d2*>(p));
+        x[0] = v.x;
+        x[1] = v.y;
+    } else {
+        x[0] = __builtin_nontemporal_load(p);
+    }
+}
+
+// x = m 2^k with m in [1, 2), for a positive normal x: returns m and adds k to e (three integer instructions, no log).
+__device__ __forceinline__ double xs_split(double x, int& e) {
+    const int hi = __double2hiint(x);
+    e += ((hi >> 20) & 0x7ff) - 1023;
+    return __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(x));
+}
+
+// Statistics of W adjacent paths over n_rows rows from col on.  The rows of a group of XS_ROWS are loaded first and then
+// combined pairwise (sum, min, max, product of mantissas), so a group costs one dependent step per accumulator.
+// Geometric mean: prod (renormalised to [1, 2) after every group) and the exponent sum carry ln of the product exactly up
+// to the roundings of the n_rows multiplications; ONE log per path at the end.  A path that holds a value below the
+// smallest normal double (zero, subnormal, negative) is rescanned with a log per element: exp(mean(log S)) as written.
+template <bool GEO, int W>
+__device__ __forceinline__ void path_stats_scan(const double* col, int64_t ld, int n_rows, int64_t n_paths, int64_t p0, double* out5) {
+    double sum[W], mn[W], mx[W], last[W], prod[W];
+    long long es[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        sum[w] = 0.0;
+        mn[w] = std::numeric_limits<double>::infinity();
+        mx[w] = -std::numeric_limits<double>::infinity();
+        last[w] = 0.0;
+        prod[w] = 1.0;
+        es[w] = 0;
+    }
+    int j = 0;
+    for (; j + XS_ROWS <= n_rows; j += XS_ROWS) {
+        double x[XS_ROWS][W];
+#pragma unroll
+        for (int k = 0; k < XS_ROWS; ++k) xs_load<W>(col + (int64_t)(j + k) * ld, x[k]);
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            double s[XS_ROWS], lo[XS_ROWS], hi[XS_ROWS], m[XS_ROWS];
+            int e = 0;
+#pragma unroll
+            for (int k = 0; k < XS_ROWS; ++k) {
+                s[k] = lo[k] = hi[k] = x[k][w];
+                if constexpr (GEO) m[k] = xs_split(x[k][w], e);
+            }
+#pragma unroll
+            for (int h = XS_ROWS / 2; h >= 1; h >>= 1) {
+#pragma unroll
+                for (int k = 0; k < h; ++k) {
+                    s[k] += s[k + h];
+                    lo[k] = fmin(lo[k], lo[k + h]);
+                    hi[k] = fmax(hi[k], hi[k + h]);
+                    if constexpr (GEO) m[k] *= m[k + h];
+                }
+            }
+            sum[w] += s[0];
+            mn[w] = fmin(mn[w], lo[0]);
+            mx[w] = fmax(mx[w], hi[0]);
+            last[w] = x[XS_ROWS - 1][w];
+            if constexpr (GEO) {
+                prod[w] = xs_split(prod[w] * m[0], e);  // < 2 * 2^8 before, [1, 2) after
+                es[w] += e;
+            }
+        }
+    }
+    for (; j < n_rows; ++j) {  // at most XS_ROWS - 1 rows: prod stays below 2^8
+        double x[W];
+        xs_load<W>(col + (int64_t)j * ld, x);
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            sum[w] += x[w];
+            mn[w] = fmin(mn[w], x[w]);
+            mx[w] = fmax(mx[w], x[w]);
+            last[w] = x[w];
+            if constexpr (GEO) {
+                int e = 0;
+                prod[w] *= xs_split(x[w], e);
+                es[w] += e;
+            }
+        }
+    }
+    const double nd = (double)n_rows;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const int64_t p = p0 + w;
+        out5[0 * n_paths + p] = last[w];
+        out5[1 * n_paths + p] = sum[w] / nd;
+        out5[3 * n_paths + p] = mn[w];
+        out5[4 * n_paths + p] = mx[w];
+        if constexpr (GEO) {
+            double ls = (double)es[w] * 0.6931471805599453094 + log(prod[w]);
+            if (!(mn[w] >= std::numeric_limits<double>::min())) {
+                ls = 0.0;
+                for (int k = 0; k < n_rows; ++k) ls += log(col[(int64_t)k * ld + w]);
+            }
+            out5[2 * n_paths + p] = exp(ls / nd);
+        }
+    }
+}
+
+// One lane per W adjacent paths.  W = 2 needs 16-byte aligned rows (even ld, aligned base: what paths_new makes); the last
+// path of an odd count is scanned alone by its lane.
+template <bool GEO, int W>
+__global__ __launch_bounds__(256) void k_path_stats(const double* data, int64_t ld, int64_t n_paths, int first_row, int n_rows,
+                                                    double* out5) {
+    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;
+    if (p0 >= n_paths) return;
+    const double* col = data + (int64_t)first_row * ld + p0;
+    if (W == 2 && p0 + 1 == n_paths) path_stats_scan<GEO, 1>(col, ld, n_rows, n_paths, p0, out5);
+    else path_stats_scan<GEO, W>(col, ld, n_rows, n_paths, p0, out5);
+}
+
+// The undiscounted payoffs of include/mcgpu.h, on one path's statistics.  Strike and barrier tests are plain comparisons
+// of the stored doubles.
+__device__ __forceinline__ double exotic_payoff(const mcg_exotic& c, double st, double A, double G, double mn, double mx) {
+    const bool call = c.is_call != 0;
+    switch (c.kind) {
+        case MCG_X_ASIAN_ARITH_FIXED: return payoff_of(call, A, c.K);
+        case MCG_X_ASIAN_ARITH_FLOAT: return payoff_of(call, st, A);
+        case MCG_X_ASIAN_GEO_FIXED: return payoff_of(call, G, c.K);
+        case MCG_X_ASIAN_GEO_FLOAT: return payoff_of(call, st, G);
+        case MCG_X_LOOKBACK_FIXED: return call ? fmax(0.0, mx - c.K) : fmax(0.0, c.K - mn);
+        case MCG_X_LOOKBACK_FLOAT: return call ? st - mn : mx - st;
+        default: {
+            const bool up = c.kind == MCG_X_BARRIER_UP_OUT || c.kind == MCG_X_BARRIER_UP_IN;
+            const bool in = c.kind == MCG_X_BARRIER_UP_IN || c.kind == MCG_X_BARRIER_DOWN_IN;
+            const bool hit = up ? mx >= c.barrier : mn <= c.barrier;
+            return hit == in ? payoff_of(call, st, c.K) : c.rebate;
+        }
+    }
+}
+
+// blockIdx.y: a chunk of XB_CH contracts; blockIdx.x strides over the paths (a grid that depends on the path count only:
+// a contract's partial sums are the same whatever else the book holds and wherever it stands).
+// partials[(chunk * gridDim.x + blockIdx.x) * XB_NF + {q: sum, XB_CH + q: sum of squares}]
+__global__ __launch_bounds__(256) void k_exotic_book(const double* stats, int64_t n, int geo, const mcg_exotic* book, int n_contracts,
+                                                     double* partials) {
+    __shared__ double red[XB_NF * 4];
+    const int c0 = blockIdx.y * XB_CH;
+    const int live = min(XB_CH, n_contracts - c0);
+    double e[XB_NF];
+#pragma unroll
+    for (int q = 0; q < XB_NF; ++q) e[q] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double st = stats[i], A = stats[n + i], G = geo ? stats[2 * n + i] : 0.0, mn = stats[3 * n + i], mx = stats[4 * n + i];
+#pragma unroll
+        for (int q = 0; q < XB_CH; ++q) {
+            if (q < live) {
+                const double x = exotic_payoff(book[c0 + q], st, A, G, mn, mx);
+                e[q] += x;
+                e[XB_CH + q] = fma(x, x, e[XB_CH + q]);
+            }
+        }
+    }
+    block_sum<XB_NF, 4>(e, red);
+    if (threadIdx.x == 0) {
+        double* out = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * XB_NF;
+#pragma unroll
+        for (int q = 0; q < XB_NF; ++q) out[q] = e[q];
+    }
+}
+
+// One workgroup per chunk, like k_greeks_reduce: wave w takes the fields w, w + 4, ...; lane l the blocks l, l + 64, ...,
+// then the butterfly.  sums = {sum, sum^2} per contract, then the local path count.
+__global__ __launch_bounds__(256) void k_exotic_reduce(const double* partials, int n_blocks, int n_contracts, double n_local, double* sums) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* src = partials + (int64_t)blockIdx.x * n_blocks * XB_NF;
+    for (int q = wave; q < XB_NF; q += 4) {
+        double s = 0.0;
+        for (int b = lane; b < n_blocks; b += 64) s += src[(int64_t)b * XB_NF + q];
+        s = wave_sum(s);
+        const int c = blockIdx.x * XB_CH + q % XB_CH;
+        if (lane == 0 && c < n_contracts) sums[2 * c + q / XB_CH] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * n_contracts] = n_local;
+}
+
+static int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats) {
+    const int n_rows = P->n_steps - first_row + 1;
+    const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0;
+    const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
+    const int64_t n_blocks = (lanes + 255) / 256;
+    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
+    const dim3 grid((unsigned)n_blocks), block(256);
+    {
+        TimedLaunch t(ctx, MCG_K_EXOTIC);
+#define MCG_XS_LAUNCH(GEO, W) \
+    hipLaunchKernelGGL((k_path_stats<GEO, W>), grid, block, 0, ctx->stream, P->data, P->ld, P->n_paths, first_row, n_rows, d_stats)
+        if (geo && wide) MCG_XS_LAUNCH(true, 2);
+        else if (geo) MCG_XS_LAUNCH(true, 1);
+        else if (wide) MCG_XS_LAUNCH(false, 2);
+        else MCG_XS_LAUNCH(false, 1);
+#undef MCG_XS_LAUNCH
+    }
+    MCG_HIP(hipGetLastError());
+    return MCG_OK;
+}
+
+int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5) {
+    const size_t bytes = (size_t)XS_Q * P->n_paths * sizeof(double);
+    void* ws = nullptr;
+    int rc = pool_alloc(ctx, bytes, &ws);
+    if (rc) return rc;
+    rc = launch_path_stats(ctx, P, first_row, true, (double*)ws);
+    if (rc == MCG_OK) {
+        hipError_t e = hipMemcpyAsync(host_out5, ws, bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) rc = fail(MCG_ERR_HIP, "download of the path statistics failed: %s", hipGetErrorString(e));
+    }
+    pool_release(ctx, ws, bytes);
+    return rc;
+}
+
+// The all-reduce of a payload that may exceed what the node-local collective carries in one call.
+static int allreduce_sums(mcg_ctx* ctx, double* d, int count) {
+    const int piece = ctx->shm ? SHM_ALLREDUCE_MAX : count;
+    for (int at = 0; at < count; at += piece)
+        if (ctx->allreduce(ctx->allreduce_user, d + at, std::min(piece, count - at), (void*)ctx->stream) != 0)
+            return fail(MCG_ERR_COMM, "all-reduce of the exotic payoff sums failed");
+    return MCG_OK;
+}
+
+// Workspace (one pool buffer): [5 n statistics][n_chunks * n_blocks * XB_NF partials][2 n_contracts + 1 sums].
+static int exotic_sums(mcg_ctx* ctx, const mcg_paths* P, int first_row, const mcg_exotic* book, int nc, std::vector<double>& h) {
+    const int64_t n = P->n_paths;
+    const int n_sums = 2 * nc + 1, n_chunks = (nc + XB_CH - 1) / XB_CH;
+    const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+    const size_t n_part = (size_t)n_chunks * n_blocks * XB_NF;
+    const size_t bytes = ((size_t)XS_Q * n + n_part + n_sums) * sizeof(double);
+    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)nc * sizeof(mcg_exotic) / sizeof(double));
+    if (rc) return rc;
+    void* ws = nullptr;
+    rc = pool_alloc(ctx, bytes, &ws);
+    if (rc) return rc;
+    double *d_stats = (double*)ws, *d_part = d_stats + XS_Q * n, *d_sums = d_part + n_part;
+    const mcg_exotic* d_book = reinterpret_cast<const mcg_exotic*>(ctx->weights);
+    auto body = [&]() -> int {
+        if (n > 0) {
+            bool geo = false;
+            for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
+            MCG_HIP(hipMemcpyAsync(ctx->weights, book, (size_t)nc * sizeof(mcg_exotic), hipMemcpyHostToDevice, ctx->stream));
+            const int r2 = launch_path_stats(ctx, P, first_row, geo, d_stats);
+            if (r2) return r2;
+            {
+                TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
+                hipLaunchKernelGGL(k_exotic_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, geo ? 1 : 0, d_book, nc, d_part);
+                hipLaunchKernelGGL(k_exotic_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
+            }
+            MCG_HIP(hipGetLastError());
+        } else {
+            MCG_HIP(hipMemsetAsync(d_sums, 0, n_sums * sizeof(double), ctx->stream));  // an empty shard still takes part in the collective
+        }
+        if (ctx->allreduce) {
+            const int r2 = allreduce_sums(ctx, d_sums, n_sums);
+            if (r2) return r2;
+        }
+        h.resize(n_sums);
+        MCG_HIP(hipMemcpyAsync(h.data(), d_sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        MCG_HIP(hipStreamSynchronize(ctx->stream));
+        return MCG_OK;
+    };
+    rc = body();
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still use the workspace when it goes back to the pool
+    pool_release(ctx, ws, bytes);
+    return rc;
+}
+
+int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int nc, double* price,
+                double* std_err, double* sums) {
+    std::vector<double> h;
+    const int rc = exotic_sums(ctx, P, first_row, book, nc, h);
+    if (rc) return rc;
+    const double n = h[2 * nc];
+    if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    const double disc = std::exp(-r * T);
+    for (int c = 0; c < nc; ++c) {
+        double se;
+        sums_to_mean_stderr(h[2 * c], h[2 * c + 1], n, &price[c], &se);
+        price[c] = disc * price[c];
+        if (std_err) std_err[c] = disc * se;
+    }
+    if (sums) std::copy(h.begin(), h.end(), sums);
+    return MCG_OK;
+}
+
+}  // namespace mcg

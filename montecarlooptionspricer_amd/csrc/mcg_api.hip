@@ -583,6 +583,45 @@ int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
     return run_lsm_greeks(ctx, P, r, K, maturity, dt, is_call, poly_order, out);
 }
 
+// ---- path-dependent European payoffs ---------------------------------------------------------
+static int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row) {
+    if (!ctx || !P) return fail(MCG_ERR_INVALID, "ctx/paths is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    if (first_row < 0 || first_row > P->n_steps)
+        return fail(MCG_ERR_INVALID, "first_row must be in [0, n_steps = %d] (got %d)", P->n_steps, first_row);
+    return MCG_OK;
+}
+
+int mcg_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (!host_out5) return fail(MCG_ERR_INVALID, "host_out5 is NULL");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to take statistics of");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_path_stats(ctx, P, first_row, host_out5);
+}
+
+int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
+                      double* price, double* std_err, double* sums) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (!book || !price) return fail(MCG_ERR_INVALID, "book/price is NULL");
+    if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
+    for (int c = 0; c < n_contracts; ++c) {
+        const mcg_exotic& x = book[c];
+        if (x.kind < MCG_X_ASIAN_ARITH_FIXED || x.kind > MCG_X_BARRIER_DOWN_IN)
+            return fail(MCG_ERR_INVALID, "contract %d: kind must be in [0, 9] (got %d)", c, x.kind);
+        const bool barrier = x.kind >= MCG_X_BARRIER_UP_OUT;
+        const bool strike = barrier || x.kind == MCG_X_ASIAN_ARITH_FIXED || x.kind == MCG_X_ASIAN_GEO_FIXED || x.kind == MCG_X_LOOKBACK_FIXED;
+        if (strike && !std::isfinite(x.K)) return fail(MCG_ERR_INVALID, "contract %d: K must be finite", c);
+        if (barrier && !std::isfinite(x.barrier)) return fail(MCG_ERR_INVALID, "contract %d: barrier must be finite", c);
+        if (barrier && !std::isfinite(x.rebate)) return fail(MCG_ERR_INVALID, "contract %d: rebate must be finite", c);
+    }
+    if (P->n_paths < 1 && !ctx->allreduce) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_exotics(ctx, P, r, T, first_row, book, n_contracts, price, std_err, sums);
+}
+
 int mcg_lsm_one_launch_enabled(mcg_ctx* ctx, int* enabled) {
     if (!ctx || !enabled) return fail(MCG_ERR_INVALID, "ctx/enabled is NULL");
     *enabled = ctx->coop_launch ? 1 : 0;

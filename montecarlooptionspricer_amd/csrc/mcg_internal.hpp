@@ -66,6 +66,7 @@ struct ShmComm;  // comm_shm.cpp: node-local collective over POSIX shared memory
 constexpr int SHM_MAX_RANKS = 16;     // processes (GPUs) sharing one segment
 constexpr int SHM_MAX_ROUNDS = 4096;  // exchange rounds of one LSM sweep the device mailbox holds (2 per exercise date at most)
 constexpr int SHM_ROW_DOUBLES = 16;   // one rank's row of a round: up to 14 moments (orders <= 4)
+constexpr int SHM_ALLREDUCE_MAX = 62; // doubles one host all-reduce of the segment carries (a rank's slot row holds 64)
 
 }  // namespace mcg
 
@@ -215,6 +216,10 @@ int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, do
 int run_lsm_greeks(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
                    int poly_order, mcg_greeks* out);
 int greeks_lsm_final(mcg_ctx* ctx, const mcg_paths* P, double K, const double* V, const double* dV, mcg_greeks* out);
+// path-dependent European payoffs (kernels_exotic.hip)
+int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5);
+int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
+                double* price, double* std_err, double* sums);
 
 // MartingaleOptimization's refit (its driver re-accumulates on request): mo_mode 1 = first pass, leave the refinement
 // request in the coefficient block; 2 = the moments are about mo_mu, solve them with lsm_solve_centered.

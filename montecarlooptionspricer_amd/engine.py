@@ -262,6 +262,27 @@ class PathEngine:
                                      C.byref(g)))
         return g.as_dict()
 
+    def path_stats(self, paths: PathMatrix, first_row: int = 1) -> np.ndarray:
+        """Per-path statistics over the monitoring rows first_row .. n_steps (mcg_path_stats): [5][n_paths] =
+        S_T, arithmetic mean, geometric mean, min, max."""
+        paths._alive()
+        out = np.empty((5, paths.n_paths), dtype=np.float64)
+        check(self._L.mcg_path_stats(self._ctx, paths._h, int(first_row), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def price_exotics(self, paths: PathMatrix, r: float, T: float, book, first_row: int = 1, return_sums: bool = False):
+        """Asian, lookback and barrier contracts from one pass over the matrix (mcg_price_exotics).  book: a sequence of
+        exotic(...) tuples (kind, is_call, K, barrier, rebate) or dicts with those keys; returns (price[n], std_err[n]),
+        plus sums[2 n + 1] = {sum, sum^2} per contract then the path count when return_sums."""
+        paths._alive()
+        arr = make_book(book)
+        n = len(arr)
+        dp = C.POINTER(C.c_double)
+        price, se, sums = np.empty(n), np.empty(n), np.empty(2 * n + 1)
+        check(self._L.mcg_price_exotics(self._ctx, paths._h, r, T, int(first_row), arr, n, price.ctypes.data_as(dp),
+                                        se.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
+        return (price, se, sums) if return_sums else (price, se)
+
     def lsm_one_launch_enabled(self) -> bool:
         """False once the one-launch LSM sweep's hand-shake has timed out on this ctx (mcg_lsm_one_launch_enabled)."""
         v = C.c_int()
@@ -394,6 +415,26 @@ def make_rows(rows):
         r = arr[i]
         for k in names:
             setattr(r, k, d[k])
+    return arr
+
+
+def exotic(kind, is_call: bool, K: float = 0.0, barrier: float = 0.0, rebate: float = 0.0) -> tuple:
+    """One contract of a price_exotics book: (kind, is_call, K, barrier, rebate).  kind: one of _native.X_* or its name
+    ("asian_arith_fixed", "lookback_float", "barrier_up_out", ...: _native.EXOTIC_KINDS)."""
+    k = N.EXOTIC_KINDS.get(kind.lower()) if isinstance(kind, str) else (int(kind) if int(kind) in N.EXOTIC_KINDS.values() else None)
+    if k is None:
+        raise McgError(f"unknown exotic kind {kind!r}: one of {sorted(N.EXOTIC_KINDS)} or 0..9", 1)
+    return (k, bool(is_call), float(K), float(barrier), float(rebate))
+
+
+def make_book(book):
+    """ctypes array of mcg_exotic from a sequence of exotic(...) tuples or dicts with the mcg_exotic fields (fields a
+    dict leaves out are 0).  Kinds and counts are checked by the library."""
+    names = [k for k, _ in N.Exotic._fields_]
+    arr = (N.Exotic * len(book))()
+    for i, c in enumerate(book):
+        vals = [c.get(k, 0) for k in names] if isinstance(c, dict) else c
+        arr[i] = N.Exotic(int(vals[0]), int(bool(vals[1])), float(vals[2]), float(vals[3]), float(vals[4]))
     return arr
 
 

@@ -55,7 +55,8 @@ enum mcg_kernel {
     MCG_K_BRANCHING = 8,  /* BranchingProcesses suffix-max + bounds kernels   */
     MCG_K_BATCH = 9,      /* the six kernels of mcg_batch_price_rows (one span) */
     MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics */
-    MCG_K_COUNT = 11
+    MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
+    MCG_K_COUNT = 12
 };
 
 const char* mcg_last_error(void);
@@ -138,6 +139,31 @@ int mcg_paths_rbergomi_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
                               double eta, double rho, double dt, int n_steps, uint64_t path_begin,
                               int64_t n_paths, double K, int is_call, mcg_paths** out);
 
+/* Heston stochastic volatility, full-truncation log-Euler.  For step n = 0 .. n_steps-1, with S_0 = S0 and v_0 = v0:
+ *   z1 = draw n of (path, price driver),  z2 = draw n of (path, volatility driver)
+ *        (Philox streams 0 and 1 of `seed`: block n >> 2, element n & 3 -- the RNG contract of DESIGN.md)
+ *   vp = max(v_n, 0);  s = sqrt(vp * dt)
+ *   S_{n+1} = S_n * exp((r - vp/2) dt + s (rho z2 + sqrt(1 - rho^2) z1))
+ *   v_{n+1} = v_n + kappa (theta - vp) dt + sigma_v s z2
+ * Row n of *out is S_n.  var_out may be NULL; otherwise *var_out receives a second matrix of the same shape whose row n is
+ * v_n, untruncated (negative where the scheme overshoots; the caller frees both).  A path depends only on (seed, global
+ * path id): paths [path_begin, path_begin + n_paths) of any split reproduce the one-call matrix bit for bit, and repeated
+ * calls are bit-identical.  path_begin may be odd.
+ * The price matrix is marked as generated, like GBM's (S_T proportional to e^{rT}): mcg_greeks_european with sigma <= 0
+ * returns price, delta, rho and dual delta on it, gamma and vega NaN.  The variance matrix is a plain matrix.
+ * The _payoff form also leaves {sum payoff, sum payoff^2, n} for mcg_price_european, as mcg_paths_gbm_payoff does (all-reduced
+ * on a ctx with a collective).
+ * MCG_ERR_INVALID with a message: a NULL ctx or out; a non-finite S0, r, v0, kappa, theta, sigma_v, rho, dt (or K);
+ * S0 <= 0; dt <= 0; v0, kappa, theta or sigma_v < 0; |rho| > 1; n_steps < 1; n_paths < 0.
+ * Out of scope: Andersen's QE and exact schemes; sensitivities to v0, kappa, theta and sigma_v; Heston in the batch rows,
+ * the coalescing layer and the drop-in classes. */
+int mcg_paths_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                     double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                     mcg_paths** out, mcg_paths** var_out);
+int mcg_paths_heston_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                            double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                            double K, int is_call, mcg_paths** out, mcg_paths** var_out);
+
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,
                         mcg_paths** out);
@@ -180,7 +206,7 @@ typedef struct mcg_greeks {
  *   price      D mean(payoff)                                  always (== mcg_price_european up to summation order)
  *   dual_delta -D mean(f')                                     always
  *   delta      D mean(f' S_T / S0)                             when row 0 is one positive constant
- *   rho        -T price + D mean(f' T S_T)                     when the matrix came from mcg_paths_gbm* / mcg_paths_rbergomi*
+ *   rho        -T price + D mean(f' T S_T)                     when the matrix came from a generator (mcg_paths_gbm* / _rbergomi* / _heston*)
  *                                                              (S_T proportional to e^{rT}); NaN for mcg_paths_from_host
  *   vega       D mean(f' S_T (W_T - sigma T))                  when sigma > 0: the caller asserts GBM with that sigma,
  *   gamma      D K / (S0^2 sigma T) mean(1{S_T > K} W_T)       generated over horizon T at rate r (gamma: mixed pathwise /

@@ -9,10 +9,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("MCG_LIB") or os.path.join(_HERE, "lib", "libmcgpu.so")  # MCG_LIB: A/B experiments with another build
 
 MCG_OK = 0
-K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC = range(11)
+K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC, K_HESTON = range(12)
 KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_SWEEP: "lsm_sweep",
                 K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
-                K_EXOTIC: "exotic"}
+                K_EXOTIC: "exotic", K_HESTON: "heston"}
 
 # enum mcg_exotic_kind (include/mcgpu.h)
 (X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXED, X_ASIAN_GEO_FLOAT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT,
@@ -144,6 +144,9 @@ def load_library():
                                                                           C.POINTER(vp)]
     L.mcg_paths_rbergomi_payoff.argtypes = [vp, C.c_uint64] + [C.c_double] * 7 + [C.c_int, C.c_uint64, C.c_int64,
                                                                                  C.c_double, C.c_int, C.POINTER(vp)]
+    L.mcg_paths_heston.argtypes = [vp, C.c_uint64] + [C.c_double] * 8 + [C.c_int, C.c_uint64, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
+    L.mcg_paths_heston_payoff.argtypes = [vp, C.c_uint64] + [C.c_double] * 8 + [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_int,
+                                          C.POINTER(vp), C.POINTER(vp)]
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

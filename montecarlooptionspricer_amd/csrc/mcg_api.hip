@@ -412,6 +412,61 @@ int mcg_paths_rbergomi_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
     return gen_rb(ctx, seed, S0, r, xi, H, eta, rho, dt, n_steps, path_begin, n_paths, true, K, is_call, out);
 }
 
+static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
+                      double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call,
+                      mcg_paths** out, mcg_paths** var_out) {
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    const double args[] = {S0, r, v0, kappa, theta, sigma_v, rho, dt};
+    const char* names[] = {"S0", "r", "v0", "kappa", "theta", "sigma_v", "rho", "dt"};
+    for (int i = 0; i < 8; ++i)
+        if (!std::isfinite(args[i])) return fail(MCG_ERR_INVALID, "Heston: %s must be finite", names[i]);
+    if (payoff && !std::isfinite(K)) return fail(MCG_ERR_INVALID, "Heston: K must be finite");
+    int rc = check_gen_args(ctx, S0, dt, n_steps, n_paths, out);
+    if (rc) return rc;
+    if (!(S0 > 0.0)) return fail(MCG_ERR_INVALID, "Heston: S0 must be > 0");
+    if (!(v0 >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: v0 must be >= 0");
+    if (!(kappa >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: kappa must be >= 0");
+    if (!(theta >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: theta must be >= 0");
+    if (!(sigma_v >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: sigma_v must be >= 0");
+    if (!(std::fabs(rho) <= 1.0)) return fail(MCG_ERR_INVALID, "Heston: |rho| must be <= 1");
+    mcg_paths *P = nullptr, *V = nullptr;
+    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
+    if (rc) return rc;
+    if (var_out) {
+        rc = paths_new(ctx, n_paths, n_steps, path_begin, &V);
+        if (rc) {
+            mcg_paths_free(P);
+            return rc;
+        }
+    }
+    if (n_paths > 0) {
+        rc = launch_heston(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
+        if (rc) {
+            mcg_paths_free(P);
+            if (V) mcg_paths_free(V);
+            return rc;
+        }
+    }
+    P->generated = true;
+    *out = P;
+    if (var_out) *var_out = V;
+    return MCG_OK;
+}
+
+int mcg_paths_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                     double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                     mcg_paths** out, mcg_paths** var_out) {
+    return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out,
+                      var_out);
+}
+
+int mcg_paths_heston_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                            double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                            double K, int is_call, mcg_paths** out, mcg_paths** var_out) {
+    return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, true, K, is_call,
+                      out, var_out);
+}
+
 // ---- host <-> device ---------------------------------------------------------------------------
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols, mcg_paths** out) {
     if (!ctx || !out) return fail(MCG_ERR_INVALID, "ctx/out is NULL");

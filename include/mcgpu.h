@@ -155,14 +155,52 @@ int mcg_paths_rbergomi_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
  * on a ctx with a collective).
  * MCG_ERR_INVALID with a message: a NULL ctx or out; a non-finite S0, r, v0, kappa, theta, sigma_v, rho, dt (or K);
  * S0 <= 0; dt <= 0; v0, kappa, theta or sigma_v < 0; |rho| > 1; n_steps < 1; n_paths < 0.
- * Out of scope: Andersen's QE and exact schemes; sensitivities to v0, kappa, theta and sigma_v; Heston in the batch rows,
- * the coalescing layer and the drop-in classes. */
+ * Out of scope: exact (Broadie-Kaya) schemes; QE's martingale correction and a caller-chosen psi_c or gamma weights;
+ * sensitivities to the Heston parameters; Heston in the batch rows, the coalescing layer and the drop-in classes. */
 int mcg_paths_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
                      double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
                      mcg_paths** out, mcg_paths** var_out);
 int mcg_paths_heston_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
                             double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
                             double K, int is_call, mcg_paths** out, mcg_paths** var_out);
+
+/* Heston by Andersen's quadratic-exponential (QE) scheme (Andersen 2008, without the martingale correction; central
+ * weights gamma1 = gamma2 = 1/2).  Unlike the Euler scheme above it is unbiased at a few steps a year, also where
+ * 2 kappa theta < sigma_v^2.  Constants, computed once on the host in binary64:
+ *   E  = exp(-kappa dt)
+ *   c1 = sigma_v^2 E (1-E)/kappa
+ *   c2 = theta sigma_v^2 (1-E)^2 / (2 kappa)        kappa == 0: c1 = sigma_v^2 dt, c2 = 0
+ *   g  = kappa rho / sigma_v - 1/2
+ *   K0 = -rho kappa theta dt / sigma_v
+ *   K1 = dt g/2 - rho/sigma_v
+ *   K2 = dt g/2 + rho/sigma_v
+ *   K3 = K4 = dt (1 - rho^2)/2
+ *   psi_c = 1.5
+ * For step n = 0 .. n_steps-1, with S_0 = S0 and v_0 = v0 >= 0:
+ *   z1 = draw n of Philox stream 0,  z2 = draw n of Philox stream 1    (as above: block n >> 2, element n & 3)
+ *   u  = (word (n & 3) of block (n >> 2) of Philox stream 3 + 0.5) * 2^-32      in (0, 1)
+ *        (stream 2 belongs to the branching-process kernels)
+ *   m  = theta + (v_n - theta) E
+ *   s2 = v_n c1 + c2
+ *   psi = s2 / m^2
+ *   m == 0          : v' = 0
+ *   psi <= psi_c    : q = 2/psi;  b2 = q - 1 + sqrt(q) sqrt(q - 1);  v' = m/(1 + b2) * (sqrt(b2) + z2)^2
+ *   psi >  psi_c    : p = (psi - 1)/(psi + 1);  beta = (1 - p)/m;  v' = 0 if u <= p else ln((1 - p)/(1 - u)) / beta
+ *   S_{n+1} = S_n * exp(r dt + K0 + K1 v_n + K2 v' + sqrt(K3 v_n + K4 v') z1)
+ *   v_{n+1} = v'
+ * u is used only where psi > psi_c; a path's result does not depend on whether its neighbours needed theirs.
+ * Everything else is the contract of mcg_paths_heston*: row n of *out is S_n; var_out may be NULL, otherwise row n of *var_out
+ * is v_n, which is never negative here; ownership, the `generated` mark of the price matrix (mcg_greeks_european with
+ * sigma <= 0: price, delta, rho and dual delta), shard and repeat bit-identity, an odd path_begin, the sums the _payoff form
+ * leaves (all-reduced on a ctx with a collective) and the accounting under MCG_K_HESTON are the same.
+ * MCG_ERR_INVALID with a message: everything mcg_paths_heston rejects, and sigma_v <= 0 (the K's divide by it: use
+ * mcg_paths_heston there).  kappa = 0, theta = 0, v0 = 0 and |rho| = 1 are valid and give finite matrices. */
+int mcg_paths_heston_qe(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                        double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                        mcg_paths** out, mcg_paths** var_out);
+int mcg_paths_heston_qe_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                               double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                               double K, int is_call, mcg_paths** out, mcg_paths** var_out);
 
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,

@@ -147,6 +147,8 @@ def load_library():
     L.mcg_paths_heston.argtypes = [vp, C.c_uint64] + [C.c_double] * 8 + [C.c_int, C.c_uint64, C.c_int64, C.POINTER(vp), C.POINTER(vp)]
     L.mcg_paths_heston_payoff.argtypes = [vp, C.c_uint64] + [C.c_double] * 8 + [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_int,
                                           C.POINTER(vp), C.POINTER(vp)]
+    L.mcg_paths_heston_qe.argtypes = L.mcg_paths_heston.argtypes
+    L.mcg_paths_heston_qe_payoff.argtypes = L.mcg_paths_heston_payoff.argtypes
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

@@ -414,7 +414,7 @@ int mcg_paths_rbergomi_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
 
 static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
                       double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call,
-                      mcg_paths** out, mcg_paths** var_out) {
+                      mcg_paths** out, mcg_paths** var_out, bool qe = false) {
     if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
     const double args[] = {S0, r, v0, kappa, theta, sigma_v, rho, dt};
     const char* names[] = {"S0", "r", "v0", "kappa", "theta", "sigma_v", "rho", "dt"};
@@ -429,6 +429,8 @@ static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v
     if (!(theta >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: theta must be >= 0");
     if (!(sigma_v >= 0.0)) return fail(MCG_ERR_INVALID, "Heston: sigma_v must be >= 0");
     if (!(std::fabs(rho) <= 1.0)) return fail(MCG_ERR_INVALID, "Heston: |rho| must be <= 1");
+    if (qe && !(sigma_v > 0.0))
+        return fail(MCG_ERR_INVALID, "Heston QE: sigma_v must be > 0 (the scheme divides by it); mcg_paths_heston takes sigma_v = 0");
     mcg_paths *P = nullptr, *V = nullptr;
     rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
     if (rc) return rc;
@@ -440,7 +442,7 @@ static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v
         }
     }
     if (n_paths > 0) {
-        rc = launch_heston(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
+        rc = (qe ? launch_heston_qe : launch_heston)(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
         if (rc) {
             mcg_paths_free(P);
             if (V) mcg_paths_free(V);
@@ -465,6 +467,20 @@ int mcg_paths_heston_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, do
                             double K, int is_call, mcg_paths** out, mcg_paths** var_out) {
     return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, true, K, is_call,
                       out, var_out);
+}
+
+int mcg_paths_heston_qe(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                        double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                        mcg_paths** out, mcg_paths** var_out) {
+    return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out,
+                      var_out, true);
+}
+
+int mcg_paths_heston_qe_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                               double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                               double K, int is_call, mcg_paths** out, mcg_paths** var_out) {
+    return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, true, K, is_call,
+                      out, var_out, true);
 }
 
 // ---- host <-> device ---------------------------------------------------------------------------

@@ -133,7 +133,7 @@ struct mcg_paths {
     int n_steps = 0;
     int64_t ld = 0;
     uint64_t path_begin = 0;
-    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
+    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
     bool generated = false;
     // fused terminal-payoff sums left by *_payoff generators
     bool has_sums = false;
@@ -199,6 +199,9 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
 // V: the variance matrix (same shape as P), or null
 int launch_heston(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double r, double v0, double kappa,
                   double theta, double sigma_v, double rho, double dt, bool want_payoff, double K, int is_call);
+// the same by Andersen's QE scheme (kernels_heston_qe.hip); sigma_v > 0
+int launch_heston_qe(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double r, double v0, double kappa,
+                     double theta, double sigma_v, double rho, double dt, bool want_payoff, double K, int is_call);
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);

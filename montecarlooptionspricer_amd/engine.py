@@ -219,18 +219,24 @@ class PathEngine:
 
     def heston(self, seed: int, S0: float, r: float, v0: float, kappa: float, theta: float, sigma_v: float, rho: float,
                dt: float, n_steps: int, n_paths: int, path_begin: int = 0,
-               payoff: Optional[Tuple[float, bool]] = None, want_variance: bool = False):
-        """Heston paths by the full-truncation log-Euler scheme of include/mcgpu.h (mcg_paths_heston*): the price matrix,
-        or (prices, variances) when want_variance; row n of the variances is v_n, untruncated."""
+               payoff: Optional[Tuple[float, bool]] = None, want_variance: bool = False, scheme: str = "euler"):
+        """Heston paths by one of the schemes of include/mcgpu.h: "euler", the full-truncation log-Euler scheme
+        (mcg_paths_heston*), or "qe", Andersen's quadratic-exponential scheme (mcg_paths_heston_qe*: sigma_v > 0).  Returns the
+        price matrix, or (prices, variances) when want_variance; row n of the variances is v_n (Euler: untruncated; QE: never
+        negative)."""
+        if scheme not in ("euler", "qe"):
+            raise ValueError(f'scheme must be "euler" or "qe", not {scheme!r}')
+        plain, fused = ((self._L.mcg_paths_heston, self._L.mcg_paths_heston_payoff) if scheme == "euler" else
+                        (self._L.mcg_paths_heston_qe, self._L.mcg_paths_heston_qe_payoff))
         h, hv = C.c_void_p(), C.c_void_p()
         var_out = C.byref(hv) if want_variance else None
         if payoff is None:
-            check(self._L.mcg_paths_heston(self._ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin,
-                                           n_paths, C.byref(h), var_out))
+            check(plain(self._ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, C.byref(h),
+                        var_out))
         else:
             K, is_call = payoff
-            check(self._L.mcg_paths_heston_payoff(self._ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps,
-                                                  path_begin, n_paths, K, int(bool(is_call)), C.byref(h), var_out))
+            check(fused(self._ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, K,
+                        int(bool(is_call)), C.byref(h), var_out))
         return (PathMatrix(self, h), PathMatrix(self, hv)) if want_variance else PathMatrix(self, h)
 
     def from_host(self, row_major: np.ndarray) -> PathMatrix:

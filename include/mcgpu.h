@@ -225,6 +225,36 @@ int mcg_price_european(mcg_ctx* ctx, const mcg_paths* paths, double K, double r,
 int mcg_price_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, double maturity,
                   double dt, int is_call, int poly_order, double* mean, double* std_err);
 
+/* LSM with TWO regressors: the continuation value is fitted on (S_j, F_j), F = `state`, any per-path state of the same
+ * shape as the price matrix (the variance matrix of mcg_paths_heston* / mcg_paths_heston_qe*: under stochastic volatility
+ * the continuation value depends on both).  The sweep, the exercise rule and its constants are mcg_price_lsm's: terminal
+ * payoff at row n_steps; dates with j dt > maturity only discount; a path whose payoff exceeds 1e-14, on a date with at
+ * least one such path, gets V = max(payoff, fit); a path with payoff < 1e-14 gets V e^{-r dt}, any other 0; the price is
+ * mean(V_0), std_err as mcg_price_lsm computes it.  Only the fit differs.  At a date with the in-the-money set I, |I| >= 1:
+ *   1. standardise: for u = S_j and for u = F_j over I:  mu = mean(u), m2 = mean(u^2), var = max(m2 - mu^2, 0);
+ *        the regressor is constant on this date iff !(var > 1e-12 m2): then z = 0 for every path;
+ *        otherwise z = (u - mu)/sqrt(var).
+ *      K does not enter; the fit is invariant under affine changes of either regressor.
+ *   2. basis: the monomials zx^a zw^b, a + b <= poly_order, by total degree and within a degree by descending a:
+ *        1; zx, zw; zx^2, zx zw, zw^2; zx^3, zx^2 zw, zx zw^2, zw^3      (poly_order in [0, 3]: nb = 1, 3, 6, 10)
+ *   3. moments: the power sums sum zx^a zw^b, a + b <= 2 poly_order (28 at order 3), and the nb cross sums
+ *        sum phi_k e^{-r dt} V, over I in a fixed order.
+ *   4. solve: the Gram matrix G from the power sums; d_k = G_kk^-1/2 (0 where G_kk <= 0); LDL^T of d G d in basis order:
+ *        a column whose d_k is 0, or whose pivot (in these equilibrated units) is <= 1e-8, is DROPPED: its coefficient
+ *        is 0 and it takes no part in later columns.  The fit is the kept columns' combination.
+ * *n_dropped (may be NULL) receives the number of dropped columns over all dates that had an in-the-money path; a date
+ * with none fits nothing and drops nothing.  The one rule covers date 0 (both regressors constant: the fit is the mean),
+ * a state that is constant or collinear with S, and fewer in-the-money paths than basis functions.
+ * Repeated calls are bit-identical (fixed-order reductions, no floating-point atomics).  One launch sequence queued by the
+ * host, four launches per exercise date, no read-back before the final sums; booked under MCG_K_LSM_SWEEP.
+ * MCG_ERR_INVALID with a message: a NULL ctx, paths, state or mean; a state whose n_paths or n_steps differ from the
+ * paths'; either matrix of another ctx; poly_order outside [0, 3]; a non-finite r, K, maturity or dt; K <= 0; dt <= 0;
+ * a ctx that holds a collective.  An empty matrix is MCG_ERR_EMPTY_PATHS.
+ * Out of scope: collectives (sharded matrices); the one-launch sweeps; Greeks; the batch rows, the coalescing layer and
+ * the drop-in classes; more than one extra state; orders above 3. */
+int mcg_price_lsm2(mcg_ctx* ctx, const mcg_paths* paths, const mcg_paths* state, double r, double K, double maturity,
+                   double dt, int is_call, int poly_order, double* mean, double* std_err, int64_t* n_dropped);
+
 /* ---- Greeks ----------------------------------------------------------------------------- */
 /* Price sensitivities with Monte Carlo standard errors.  Every field an entry point does not fill is NaN, and so is its
  * std error.  dual_delta = dP/dK.  Repeated calls on the same matrix are bit-identical (fixed-order reductions).

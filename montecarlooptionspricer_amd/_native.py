@@ -156,6 +156,8 @@ def load_library():
     L.mcg_paths_free.argtypes = [vp]
     L.mcg_price_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, dp, dp]
     L.mcg_price_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp]
+    L.mcg_price_lsm2.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp,
+                                 C.POINTER(C.c_int64)]
     L.mcg_lsm_one_launch_enabled.argtypes = [vp, C.POINTER(C.c_int)]
     L.mcg_greeks_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.POINTER(Greeks)]
     L.mcg_greeks_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Greeks)]

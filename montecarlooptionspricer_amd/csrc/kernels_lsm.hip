@@ -1542,14 +1542,17 @@ int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturit
     }
     rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, grid, nullptr);
     if (rc) return rc;
+    return lsm_finish(ctx, grid, N, mean, std_err);
+}
 
+int lsm_finish(mcg_ctx* ctx, int grid, int64_t N, double* mean, double* std_err) {
     {
         TimedLaunch t(ctx, MCG_K_LSM_SWEEP);
         hipLaunchKernelGGL(k_lsm_final, dim3(grid), dim3(256), 0, ctx->stream, ctx->lsm_v, N, ctx->partials);
     }
     MCG_HIP(hipGetLastError());
     double s[3];
-    rc = finish_sums(ctx, grid, N, s);
+    int rc = finish_sums(ctx, grid, N, s);
     if (rc) return rc;
     const double n = s[2];
     if (!(n >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");

@@ -626,6 +626,26 @@ int mcg_price_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
     return run_lsm(ctx, P, r, K, maturity, dt, is_call, poly_order, mean, std_err);
 }
 
+int mcg_price_lsm2(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* F, double r, double K, double maturity, double dt,
+                   int is_call, int poly_order, double* mean, double* std_err, int64_t* n_dropped) {
+    if (!ctx || !P || !F || !mean) return fail(MCG_ERR_INVALID, "ctx/paths/state/mean is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    if (F->ctx != ctx) return fail(MCG_ERR_INVALID, "state belongs to a different ctx");
+    if (F->n_paths != P->n_paths || F->n_steps != P->n_steps)
+        return fail(MCG_ERR_INVALID, "state must have the shape of paths: %lld paths x %d steps (got %lld x %d)", (long long)P->n_paths,
+                    P->n_steps, (long long)F->n_paths, F->n_steps);
+    if (poly_order < 0 || poly_order > 3) return fail(MCG_ERR_INVALID, "poly_order must be in [0,3] for two regressors (got %d)", poly_order);
+    if (!std::isfinite(r) || !std::isfinite(K) || !std::isfinite(maturity) || !std::isfinite(dt))
+        return fail(MCG_ERR_INVALID, "r, K, maturity and dt must be finite");
+    if (!(K > 0.0)) return fail(MCG_ERR_INVALID, "K must be > 0 (got %g)", K);
+    if (!(dt > 0.0)) return fail(MCG_ERR_INVALID, "dt must be > 0 (got %g)", dt);
+    if (ctx->allreduce || ctx->rccl_comm || ctx->shm)
+        return fail(MCG_ERR_INVALID, "sharded two-regressor LSM is not supported: this ctx holds a collective");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_lsm2(ctx, P, F, r, K, maturity, dt, is_call, poly_order, mean, std_err, n_dropped);
+}
+
 // ---- Greeks ----------------------------------------------------------------------------------
 static int greeks_args(mcg_ctx* ctx, const mcg_paths* P, mcg_greeks* out) {
     if (!ctx || !P || !out) return fail(MCG_ERR_INVALID, "ctx/paths/out is NULL");

@@ -216,6 +216,11 @@ inline void sums_to_mean_stderr(double sum, double sum2, double n, double* mean,
 }
 int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
             int poly_order, double* mean, double* std_err);
+// mean and std error of the value vector ctx->lsm_v a per-date sweep left (k_lsm_final over `grid` workgroups + finish_sums)
+int lsm_finish(mcg_ctx* ctx, int grid, int64_t n_paths, double* mean, double* std_err);
+// the two-regressor sweep (kernels_lsm2.hip): F has P's shape
+int run_lsm2(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* F, double r, double K, double maturity, double dt, int is_call,
+             int poly_order, double* mean, double* std_err, int64_t* n_dropped);
 // Greeks (kernels_greeks.hip; the LSM tangent sweep in kernels_lsm.hip)
 int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,
                         mcg_greeks* out);

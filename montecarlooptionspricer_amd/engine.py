@@ -264,6 +264,18 @@ class PathEngine:
                                     C.byref(m), C.byref(se)))
         return m.value, se.value
 
+    def price_lsm2(self, paths: PathMatrix, state: PathMatrix, r: float, K: float, maturity: float, dt: float, is_call: bool,
+                   poly_order: int, return_dropped: bool = False):
+        """LSM with the continuation value regressed on the price AND a second per-path state of the same shape (the
+        variance matrix of heston(..., want_variance=True)): mcg_price_lsm2, poly_order in [0, 3].  Returns (mean, std_err),
+        plus the number of basis columns the fit dropped over all dates when return_dropped."""
+        paths._alive()
+        state._alive()
+        m, se, nd = C.c_double(), C.c_double(), C.c_int64()
+        check(self._L.mcg_price_lsm2(self._ctx, paths._h, state._h, r, K, maturity, dt, int(bool(is_call)), int(poly_order),
+                                     C.byref(m), C.byref(se), C.byref(nd)))
+        return (m.value, se.value, nd.value) if return_dropped else (m.value, se.value)
+
     def greeks_european(self, paths: PathMatrix, K: float, r: float, T: float, is_call: bool,
                         sigma: Optional[float] = None) -> dict:
         """European price, delta, gamma, vega, rho, dual delta and their std errors (mcg_greeks_european); NaN where a

@@ -1,0 +1,204 @@
+// The Heston path generator's skeleton for gfx950, shared by its variance schemes (kernels_heston.hip: full-truncation
+// log-Euler; kernels_heston_qe.hip: Andersen's QE): two adjacent paths per lane with S and v in registers, fm::Tables in LDS,
+// two Philox streams per path (price driver and volatility driver, philox.hpp), step-major 16-byte nontemporal stores of the
+// price row and -- optionally -- of the variance row, the terminal payoff partials of the fused form, and the launcher.
+//
+// A scheme is a struct the kernel holds one object of:
+//   Consts                     the eight doubles the host derives from the model's parameters (HestonArgs::c)
+//   new_block()                called once per Philox block, after the draws of its four steps
+//   step(a, i, block, elem, tab, z1, z2, S, v)
+//                              advances S[] and v[] in place by step 4*block + elem, from the draws z1 (price driver) and
+//                              z2 (volatility driver); i = first column of this lane
+// Rows, row pointers and stores belong to the kernel.
+#pragma once
+#include "devmath.hpp"
+#include "fastmath.hpp"
+#include "mcg_internal.hpp"
+
+namespace mcg {
+
+constexpr int HESTON_PPL = 2;  // paths per lane
+
+template <class Consts>
+struct HestonArgs {
+    double* out;       // [n_steps+1][ld] prices
+    double* var;       // [n_steps+1][ld] variances (VAR kernels only)
+    int64_t ld;
+    int64_t n_paths;
+    int n_steps;
+    uint64_t path_begin;
+    uint32_t k0, k1;   // Philox key = seed
+    double S0, v0;
+    Consts c;          // the scheme's constants
+    double K;
+    int is_call;
+    double* partials;  // [gridDim.x][2]
+    const double2* tabs;  // fm::Tables on the device
+};
+
+// sqrt(x) for x >= 0: fm::sqrt_pos where it holds, 0 for 0 (a truncated variance; QE: |rho| = 1, or v = v' = 0).  Below
+// 2^-1000 the root is that of 2^-1000 (1e-150: nothing a price step or a variance step can see).
+__device__ __forceinline__ double sqrt_nonneg(double x) {
+    const double s = fm::sqrt_pos(__builtin_fmax(x, 0x1p-1000));
+    return x > 0.0 ? s : 0.0;
+}
+
+template <class Scheme, bool PAYOFF, bool VAR>
+__global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme::Consts> a) {
+    constexpr int PPL = HESTON_PPL;
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    __shared__ fm::Tables tabs;
+    fm::load_tables(&tabs, a.tabs);
+    const fm::Tables* tab = &tabs;
+    __syncthreads();
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * PPL;  // first column of this lane
+    // rows are padded to 256 columns and a workgroup covers 512: the upper two waves of the last one may lie beyond the row
+    const bool in_row = i < a.ld;  // (wave-uniform)
+    double S[PPL], v[PPL];
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        S[p] = a.S0;
+        v[p] = a.v0;
+    }
+    if (in_row) {
+        // The generator's store pattern (kernels_gbm.hip): a wave-uniform row pointer that advances by ld on the scalar unit
+        // plus a lane offset that never changes.  The `s_nop 1` belongs to the store: a store of more than 64 bits reads its
+        // data registers after issue, and the next step's FMA overwrites them right behind it (tools/check_asm_hazards.py).
+        double* row = a.out + (int64_t)blockIdx.x * (256 * PPL);
+        double* vrow = VAR ? a.var + (int64_t)blockIdx.x * (256 * PPL) : nullptr;
+        const unsigned lane_bytes = threadIdx.x * (8u * PPL);
+        // The `s_nop 4` in front belongs to it too: these kernels hold more scalars than there are registers (eight model
+        // constants beside the polynomials'), so hipcc keeps some in spare vector lanes, and where the row pointer is one of
+        // them its v_readlane lands right before the store -- a VMEM instruction must not read an SGPR as its address within 5
+        // wait states of a VALU write (the same checker found it).  Seven idle cycles per row against ~10^3 of arithmetic.
+        auto store_pair = [&](double* r, const double (&x)[PPL]) {
+            const v2d d = {x[0], x[1]};
+            asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(d), "s"(r) : "memory");
+        };
+        store_pair(row, S);
+        if (VAR) store_pair(vrow, v);
+        PhiloxLane rng_s[PPL], rng_v[PPL];
+#pragma unroll
+        for (int p = 0; p < PPL; ++p) {
+            const uint64_t path = a.path_begin + (uint64_t)(i + p);
+            rng_s[p] = philox_lane_setup(path, STREAM_PRICE, a.k1);
+            rng_v[p] = philox_lane_setup(path, STREAM_VOL, a.k1);
+        }
+        Scheme scheme;
+        uint32_t block = 0;  // the Philox block of the current four steps
+        // one step of both paths, elem = step & 3, and its rows
+        auto step = [&](const double (&z1)[PPL], const double (&z2)[PPL], const int elem) {
+            scheme.step(a, i, block, elem, tab, z1, z2, S, v);
+            row += a.ld;
+            store_pair(row, S);
+            if (VAR) {
+                vrow += a.ld;
+                store_pair(vrow, v);
+            }
+        };
+        // One Philox block per stream feeds two Box-Muller pairs = four steps.  The main loop takes whole blocks; the
+        // tail runs pair by pair over the last <= 3 steps.
+        auto pairs = [&](const Philox4 (&ws)[PPL], const Philox4 (&wv)[PPL], bool second, double (&z1a)[PPL], double (&z1b)[PPL],
+                         double (&z2a)[PPL], double (&z2b)[PPL]) {
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) {
+                fm::box_muller_pair(second ? ws[p].w2 : ws[p].w0, second ? ws[p].w3 : ws[p].w1, tab, z1a[p], z1b[p]);
+                fm::box_muller_pair(second ? wv[p].w2 : wv[p].w0, second ? wv[p].w3 : wv[p].w1, tab, z2a[p], z2b[p]);
+            }
+        };
+        auto draw = [&](Philox4 (&ws)[PPL], Philox4 (&wv)[PPL]) {
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) {
+                ws[p] = philox4x32_10_lane(rng_s[p], block, a.k0, a.k1);
+                wv[p] = philox4x32_10_lane(rng_v[p], block, a.k0, a.k1);
+            }
+            scheme.new_block();
+        };
+        const int n_blocks = a.n_steps >> 2;
+        Philox4 ws[PPL], wv[PPL];
+        double z1a[PPL], z1b[PPL], z2a[PPL], z2b[PPL];
+#pragma unroll 1
+        for (; block < (uint32_t)n_blocks; ++block) {
+            draw(ws, wv);
+            pairs(ws, wv, false, z1a, z1b, z2a, z2b);
+            step(z1a, z2a, 0);
+            step(z1b, z2b, 1);
+            pairs(ws, wv, true, z1a, z1b, z2a, z2b);
+            step(z1a, z2a, 2);
+            step(z1b, z2b, 3);
+        }
+        const int rest = a.n_steps & 3;
+        if (rest) {  // wave-uniform
+            draw(ws, wv);
+            pairs(ws, wv, false, z1a, z1b, z2a, z2b);
+            step(z1a, z2a, 0);
+            if (rest >= 2) step(z1b, z2b, 1);
+            if (rest == 3) {
+                pairs(ws, wv, true, z1a, z1b, z2a, z2b);
+                step(z1a, z2a, 2);
+            }
+        }
+    }
+    if (PAYOFF) {
+        __shared__ double red[2 * 4];
+        double acc[2] = {0.0, 0.0};
+#pragma unroll
+        for (int p = 0; p < PPL; ++p) {
+            const double pay = (in_row && i + p < a.n_paths) ? payoff_of(a.is_call != 0, S[p], a.K) : 0.0;
+            acc[0] += pay;
+            acc[1] += pay * pay;
+        }
+        block_sum<2, 4>(acc, red);
+        if (threadIdx.x == 0) {
+            a.partials[2 * (int64_t)blockIdx.x] = acc[0];
+            a.partials[2 * (int64_t)blockIdx.x + 1] = acc[1];
+        }
+    }
+}
+
+// One launch of k_heston_paths<Scheme, ...> over P (and V: the variance matrix, or null) from the scheme's constants c.
+template <class Scheme>
+int launch_heston_scheme(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double v0,
+                         const typename Scheme::Consts& c, bool want_payoff, double K, int is_call) {
+    const int64_t n_blocks = (P->n_paths + 511) / 512;
+    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
+    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    if (V && (V->ld != P->ld || V->n_steps != P->n_steps))
+        return fail(MCG_ERR_INVALID, "the variance matrix must have the shape of the price matrix");
+    if (want_payoff) {
+        int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
+        if (rc) return rc;
+    }
+    HestonArgs<typename Scheme::Consts> a;
+    a.out = P->data;
+    a.var = V ? V->data : nullptr;
+    a.ld = P->ld;
+    a.n_paths = P->n_paths;
+    a.n_steps = P->n_steps;
+    a.path_begin = P->path_begin;
+    a.k0 = (uint32_t)seed;
+    a.k1 = (uint32_t)(seed >> 32);
+    a.S0 = S0;
+    a.v0 = v0;
+    a.c = c;
+    a.K = K;
+    a.is_call = is_call;
+    a.partials = ctx->partials;
+    a.tabs = (const double2*)ctx->log_tab;
+    {
+        TimedLaunch t(ctx, MCG_K_HESTON);
+        const dim3 grid((unsigned)n_blocks), block(256);
+        if (want_payoff) {
+            if (V) hipLaunchKernelGGL((k_heston_paths<Scheme, true, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_heston_paths<Scheme, true, false>), grid, block, 0, ctx->stream, a);
+        } else {
+            if (V) hipLaunchKernelGGL((k_heston_paths<Scheme, false, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_heston_paths<Scheme, false, false>), grid, block, 0, ctx->stream, a);
+        }
+    }
+    MCG_HIP(hipGetLastError());
+    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
+    return MCG_OK;
+}
+
+}  // namespace mcg

@@ -342,14 +342,7 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
         }
     }
     MCG_HIP(hipGetLastError());
-    if (want_payoff) {
-        int rc = finish_sums(ctx, n_blocks, P->n_paths, P->sums);
-        if (rc) return rc;
-        // sums[] now holds the (all-reduced, if a collective is installed) totals
-        P->has_sums = true;
-        P->sums_K = K;
-        P->sums_is_call = is_call;
-    }
+    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
     return MCG_OK;
 }
 

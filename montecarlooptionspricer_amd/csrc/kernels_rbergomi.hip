@@ -282,13 +282,8 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
             rc = launch_rbergomi_generic(ctx, a);
         }
         if (rc) return rc;
-        if (want_payoff) {  // (not fused on this route: one more read of the last row)
-            rc = launch_payoff_sums(ctx, P, K, is_call, P->sums);
-            if (rc) return rc;
-            P->has_sums = true;
-            P->sums_K = K;
-            P->sums_is_call = is_call;
-        }
+        // (not fused on this route: one more read of the last row)
+        if (want_payoff) return keep_sums(launch_payoff_sums(ctx, P, K, is_call, P->sums), P, K, is_call);
         return MCG_OK;
     }
     if (M >= 32) MCG_HIP(hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), ctx->stream));
@@ -299,13 +294,7 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
         else launch_variant<false>(ctx, a, (unsigned)grid, smem);
     }
     MCG_HIP(hipGetLastError());
-    if (want_payoff) {
-        rc = finish_sums(ctx, n_blocks, P->n_paths, P->sums);
-        if (rc) return rc;
-        P->has_sums = true;
-        P->sums_K = K;
-        P->sums_is_call = is_call;
-    }
+    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
     return MCG_OK;
 }
 

@@ -191,7 +191,8 @@ int peer_arm(mcg_ctx* ctx, double* mbox, int rounds, int n, uint64_t sentinel); 
 
 int paths_new(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, mcg_paths** out);
 
-// kernel launchers (one per .hip file)
+// generator launchers, each in the .hip file of its name; the two Heston ones derive their scheme's constants and share
+// heston_device.hpp's launch_heston_scheme
 int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double sigma, double dt,
                bool want_payoff, double K, int is_call);
 int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double xi, double H,
@@ -205,6 +206,15 @@ int launch_heston_qe(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, do
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);
+// the end of a *_payoff generator: rc is what finish_sums or launch_payoff_sums returned for P->sums; on success P
+// holds the (all-reduced, if a collective is installed) totals of the (K, is_call) payoff
+inline int keep_sums(int rc, mcg_paths* P, double K, int is_call) {
+    if (rc) return rc;
+    P->has_sums = true;
+    P->sums_K = K;
+    P->sums_is_call = is_call;
+    return MCG_OK;
+}
 // {sum, sum of squares, n} of an estimator -> its mean and (std_err may be null) standard error
 inline void sums_to_mean_stderr(double sum, double sum2, double n, double* mean, double* std_err) {
     const double m = sum / n;

@@ -202,6 +202,47 @@ int mcg_paths_heston_qe_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r,
                                double sigma_v, double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
                                double K, int is_call, mcg_paths** out, mcg_paths** var_out);
 
+/* Bates: Heston plus compound-Poisson log-normal jumps in the price (Merton's jumps; with kappa = sigma_v = rho = 0 and
+ * v0 = theta = sigma^2 under MCG_HESTON_EULER the model is Merton's jump-diffusion).  The jump component is applied per step
+ * on top of either variance scheme above and is exact in law: a compound-Poisson increment is independent of the diffusion,
+ * so the only time-stepping bias is the base scheme's.  Constants, computed once on the host in binary64:
+ *   L     = lambda * dt                       (required: 0 <= L <= 1)
+ *   kbar  = exp(mu_J + sigma_J^2 / 2) - 1
+ *   comp  = -lambda * kbar * dt               (martingale compensator, per step)
+ *   t_0 = exp(-L);  t_j = t_{j-1} * L / j;  c_k = c_{k-1} + t_k   (c_0 = t_0),  k = 0..15     Poisson CDF, summed in this order
+ * For step n = 0 .. n_steps-1 (block n >> 2, element n & 3, the RNG contract of DESIGN.md):
+ *   uN = (word (n & 3) of block (n >> 2) of Philox stream 4 + 0.5) * 2^-32
+ *   N  = #{ k in 0..15 : uN > c_k }                                         number of jumps in the step
+ *   z3 = draw n of Philox stream 5  (two Box-Muller pairs per block, exactly as streams 0 and 1 are turned into normals)
+ *   J  = comp + N mu_J + sigma_J sqrt(N) z3
+ *   S_{n+1} = S_n * exp( <the base scheme's exponent of this step> + J )    one exponential
+ *   v_{n+1}   as the base scheme gives it (jumps do not touch the variance)
+ * z3 is used only where N > 0; a path's result never depends on whether its neighbours jumped.  Streams 0, 1 and 3 are used
+ * exactly as by the base scheme; stream 2 stays the branching-process kernels'.  With L <= 1, 1 - c_15 < 2^-33: no uniform
+ * lies above c_15 and the count never reaches a cap.  (The device decides uN > c_k as word > floor(c_k 2^32 - 1/2), which is
+ * the same statement: c_k 2^32 - 1/2 is exact in binary64.)
+ * scheme: MCG_HESTON_EULER, the step of mcg_paths_heston*, or MCG_HESTON_QE, that of mcg_paths_heston_qe*.
+ * Everything else is the contract of mcg_paths_heston*: row n of *out is S_n; var_out may be NULL, otherwise row n of *var_out
+ * is v_n; ownership, an odd path_begin, shard and repeat bit-identity, the sums the _payoff form leaves (all-reduced on a ctx
+ * with a collective), the accounting under MCG_K_HESTON and the `generated` mark of the price matrix (S_T is still proportional
+ * to e^{rT} and to S0: mcg_greeks_european with sigma <= 0 fills price, delta, rho and dual delta) are the same.
+ * lambda = 0 reproduces mcg_paths_heston* / mcg_paths_heston_qe* bit for bit, both matrices and the sums (comp is then a zero and
+ * every N is 0).  lambda = 0, sigma_j = 0 and mu_j = 0 are valid and give finite matrices.
+ * MCG_ERR_INVALID with a message: everything the chosen base scheme rejects (sigma_v <= 0 for QE); a non-finite lambda, mu_j or
+ * sigma_j; lambda < 0; sigma_j < 0; lambda * dt > 1 (use more steps); |mu_j| > 1 or sigma_j > 1 (log-jump sizes far beyond any
+ * calibrated equity model; within the range a step's |J| stays below 50, and the summed exponent inside the domain of the
+ * device's exponential, which is any finite argument); a scheme that is neither value.
+ * Out of scope: jumps in the variance (SVJJ); double-exponential (Kou) jump sizes; sensitivities to the jump parameters; jumps
+ * in the rBergomi generator; Bates in the batch rows, the coalescing layer and the drop-in classes. */
+enum mcg_heston_scheme { MCG_HESTON_EULER = 0, MCG_HESTON_QE = 1 };
+int mcg_paths_bates(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
+                    double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps, uint64_t path_begin,
+                    int64_t n_paths, int scheme, mcg_paths** out, mcg_paths** var_out);
+int mcg_paths_bates_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                           double sigma_v, double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps,
+                           uint64_t path_begin, int64_t n_paths, int scheme, double K, int is_call, mcg_paths** out,
+                           mcg_paths** var_out);
+
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,
                         mcg_paths** out);

@@ -149,6 +149,10 @@ def load_library():
                                           C.POINTER(vp), C.POINTER(vp)]
     L.mcg_paths_heston_qe.argtypes = L.mcg_paths_heston.argtypes
     L.mcg_paths_heston_qe_payoff.argtypes = L.mcg_paths_heston_payoff.argtypes
+    L.mcg_paths_bates.argtypes = [vp, C.c_uint64] + [C.c_double] * 11 + [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.POINTER(vp),
+                                                                          C.POINTER(vp)]
+    L.mcg_paths_bates_payoff.argtypes = [vp, C.c_uint64] + [C.c_double] * 11 + [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_double,
+                                                                                 C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

@@ -1,11 +1,13 @@
 // The Heston path generator's skeleton for gfx950, shared by its variance schemes (kernels_heston.hip: full-truncation
-// log-Euler; kernels_heston_qe.hip: Andersen's QE): two adjacent paths per lane with S and v in registers, fm::Tables in LDS,
-// two Philox streams per path (price driver and volatility driver, philox.hpp), step-major 16-byte nontemporal stores of the
-// price row and -- optionally -- of the variance row, the terminal payoff partials of the fused form, and the launcher.
+// log-Euler; kernels_heston_qe.hip: Andersen's QE; kernels_bates.hip: either with compound-Poisson jumps): two adjacent
+// paths per lane with S and v in registers, fm::Tables in LDS, two Philox streams per path (price driver and volatility
+// driver, philox.hpp), step-major 16-byte nontemporal stores of the price row and -- optionally -- of the variance row, the
+// terminal payoff partials of the fused form, and the launcher.
 //
-// A scheme is a struct the kernel holds one object of:
-//   Consts                     the eight doubles the host derives from the model's parameters (HestonArgs::c)
-//   new_block()                called once per Philox block, after the draws of its four steps
+// A scheme is a struct the kernel holds one object of (heston_schemes.hpp: the two variance schemes; kernels_bates.hip: either
+// of them with jumps):
+//   Consts                     what the host derives from the model's parameters (HestonArgs::c; eight doubles for a variance scheme)
+//   new_block(a, i, block, tab)  called once per Philox block, after the draws of its four steps
 //   step(a, i, block, elem, tab, z1, z2, S, v)
 //                              advances S[] and v[] in place by step 4*block + elem, from the draws z1 (price driver) and
 //                              z2 (volatility driver); i = first column of this lane
@@ -43,6 +45,9 @@ __device__ __forceinline__ double sqrt_nonneg(double x) {
     return x > 0.0 ? s : 0.0;
 }
 
+// HestonArgs stays the kernel's first and only argument: a scheme may read parts of a.c straight from the kernel's argument
+// block, at offsetof(HestonArgs, c) from its start (kernels_bates.hip: WithJumps::rare); the static_assert there and this note
+// are what holds the two together.
 template <class Scheme, bool PAYOFF, bool VAR>
 __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme::Consts> a) {
     constexpr int PPL = HESTON_PPL;
@@ -112,7 +117,7 @@ __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme
                 ws[p] = philox4x32_10_lane(rng_s[p], block, a.k0, a.k1);
                 wv[p] = philox4x32_10_lane(rng_v[p], block, a.k0, a.k1);
             }
-            scheme.new_block();
+            scheme.new_block(a, i, block, tab);
         };
         const int n_blocks = a.n_steps >> 2;
         Philox4 ws[PPL], wv[PPL];

@@ -414,7 +414,8 @@ int mcg_paths_rbergomi_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
 
 static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
                       double rho, double dt, int n_steps, uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call,
-                      mcg_paths** out, mcg_paths** var_out, bool qe = false) {
+                      mcg_paths** out, mcg_paths** var_out, bool qe = false, const double* jump = nullptr) {
+    // jump: {lambda, mu_j, sigma_j} of mcg_paths_bates*, or null
     if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
     const double args[] = {S0, r, v0, kappa, theta, sigma_v, rho, dt};
     const char* names[] = {"S0", "r", "v0", "kappa", "theta", "sigma_v", "rho", "dt"};
@@ -431,6 +432,19 @@ static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v
     if (!(std::fabs(rho) <= 1.0)) return fail(MCG_ERR_INVALID, "Heston: |rho| must be <= 1");
     if (qe && !(sigma_v > 0.0))
         return fail(MCG_ERR_INVALID, "Heston QE: sigma_v must be > 0 (the scheme divides by it); mcg_paths_heston takes sigma_v = 0");
+    if (jump) {
+        const double lambda = jump[0], mu_j = jump[1], sigma_j = jump[2];
+        if (!std::isfinite(lambda)) return fail(MCG_ERR_INVALID, "Bates: lambda must be finite");
+        if (!std::isfinite(mu_j)) return fail(MCG_ERR_INVALID, "Bates: mu_j must be finite");
+        if (!std::isfinite(sigma_j)) return fail(MCG_ERR_INVALID, "Bates: sigma_j must be finite");
+        if (!(lambda >= 0.0)) return fail(MCG_ERR_INVALID, "Bates: lambda must be >= 0");
+        if (!(sigma_j >= 0.0)) return fail(MCG_ERR_INVALID, "Bates: sigma_j must be >= 0");
+        if (!(lambda * dt <= 1.0))
+            return fail(MCG_ERR_INVALID, "Bates: lambda * dt = %g exceeds the bound lambda * dt <= 1 of the jump count: use more steps",
+                        lambda * dt);
+        if (!(std::fabs(mu_j) <= 1.0)) return fail(MCG_ERR_INVALID, "Bates: |mu_j| must be <= 1");
+        if (!(sigma_j <= 1.0)) return fail(MCG_ERR_INVALID, "Bates: sigma_j must be <= 1");
+    }
     mcg_paths *P = nullptr, *V = nullptr;
     rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
     if (rc) return rc;
@@ -442,7 +456,11 @@ static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v
         }
     }
     if (n_paths > 0) {
-        rc = (qe ? launch_heston_qe : launch_heston)(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
+        if (jump)
+            rc = launch_bates(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, jump[0], jump[1], jump[2], dt, qe, payoff, K,
+                              is_call);
+        else
+            rc = (qe ? launch_heston_qe : launch_heston)(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
         if (rc) {
             mcg_paths_free(P);
             if (V) mcg_paths_free(V);
@@ -481,6 +499,32 @@ int mcg_paths_heston_qe_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r,
                                double K, int is_call, mcg_paths** out, mcg_paths** var_out) {
     return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, true, K, is_call,
                       out, var_out, true);
+}
+
+static int gen_bates(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
+                     double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps, uint64_t path_begin,
+                     int64_t n_paths, int scheme, bool payoff, double K, int is_call, mcg_paths** out, mcg_paths** var_out) {
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    if (scheme != MCG_HESTON_EULER && scheme != MCG_HESTON_QE)
+        return fail(MCG_ERR_INVALID, "Bates: scheme must be MCG_HESTON_EULER (0) or MCG_HESTON_QE (1), not %d", scheme);
+    const double jump[3] = {lambda, mu_j, sigma_j};
+    return gen_heston(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, path_begin, n_paths, payoff, K, is_call, out,
+                      var_out, scheme == MCG_HESTON_QE, jump);
+}
+
+int mcg_paths_bates(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta, double sigma_v,
+                    double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps, uint64_t path_begin,
+                    int64_t n_paths, int scheme, mcg_paths** out, mcg_paths** var_out) {
+    return gen_bates(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, lambda, mu_j, sigma_j, dt, n_steps, path_begin, n_paths,
+                     scheme, false, 0.0, 0, out, var_out);
+}
+
+int mcg_paths_bates_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
+                           double sigma_v, double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps,
+                           uint64_t path_begin, int64_t n_paths, int scheme, double K, int is_call, mcg_paths** out,
+                           mcg_paths** var_out) {
+    return gen_bates(ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, lambda, mu_j, sigma_j, dt, n_steps, path_begin, n_paths,
+                     scheme, true, K, is_call, out, var_out);
 }
 
 // ---- host <-> device ---------------------------------------------------------------------------

@@ -133,7 +133,7 @@ struct mcg_paths {
     int n_steps = 0;
     int64_t ld = 0;
     uint64_t path_begin = 0;
-    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
+    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe* / mcg_paths_bates*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
     bool generated = false;
     // fused terminal-payoff sums left by *_payoff generators
     bool has_sums = false;
@@ -191,7 +191,7 @@ int peer_arm(mcg_ctx* ctx, double* mbox, int rounds, int n, uint64_t sentinel); 
 
 int paths_new(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, mcg_paths** out);
 
-// generator launchers, each in the .hip file of its name; the two Heston ones derive their scheme's constants and share
+// generator launchers, each in the .hip file of its name; the Heston and Bates ones derive their scheme's constants and share
 // heston_device.hpp's launch_heston_scheme
 int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double sigma, double dt,
                bool want_payoff, double K, int is_call);
@@ -203,6 +203,10 @@ int launch_heston(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, doubl
 // the same by Andersen's QE scheme (kernels_heston_qe.hip); sigma_v > 0
 int launch_heston_qe(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double r, double v0, double kappa,
                      double theta, double sigma_v, double rho, double dt, bool want_payoff, double K, int is_call);
+// either scheme with compound-Poisson log-normal jumps (kernels_bates.hip); 0 <= lambda dt <= 1
+int launch_bates(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double r, double v0, double kappa,
+                 double theta, double sigma_v, double rho, double lambda, double mu_j, double sigma_j, double dt, bool qe,
+                 bool want_payoff, double K, int is_call);
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);

@@ -239,6 +239,33 @@ class PathEngine:
                         int(bool(is_call)), C.byref(h), var_out))
         return (PathMatrix(self, h), PathMatrix(self, hv)) if want_variance else PathMatrix(self, h)
 
+    def bates(self, seed: int, S0: float, r: float, v0: float, kappa: float, theta: float, sigma_v: float, rho: float,
+              jump_intensity: float, jump_mean: float, jump_std: float, dt: float, n_steps: int, n_paths: int, path_begin: int = 0,
+              payoff: Optional[Tuple[float, bool]] = None, want_variance: bool = False, scheme: str = "euler"):
+        """Bates paths (mcg_paths_bates*): heston(scheme=...) plus compound-Poisson jumps in the price, jump_intensity a year
+        (lambda; lambda dt <= 1), each log-normal with mean jump_mean and std deviation jump_std of the log-size.  Returns what
+        heston returns; jump_intensity = 0 gives heston's matrices bit for bit."""
+        if scheme not in ("euler", "qe"):
+            raise ValueError(f'scheme must be "euler" or "qe", not {scheme!r}')
+        h, hv = C.c_void_p(), C.c_void_p()
+        var_out = C.byref(hv) if want_variance else None
+        model = (self._ctx, seed, S0, r, v0, kappa, theta, sigma_v, rho, jump_intensity, jump_mean, jump_std, dt, n_steps, path_begin,
+                 n_paths, int(scheme == "qe"))
+        if payoff is None:
+            check(self._L.mcg_paths_bates(*model, C.byref(h), var_out))
+        else:
+            K, is_call = payoff
+            check(self._L.mcg_paths_bates_payoff(*model, K, int(bool(is_call)), C.byref(h), var_out))
+        return (PathMatrix(self, h), PathMatrix(self, hv)) if want_variance else PathMatrix(self, h)
+
+    def merton(self, seed: int, S0: float, r: float, sigma: float, jump_intensity: float, jump_mean: float, jump_std: float,
+               dt: float, n_steps: int, n_paths: int, path_begin: int = 0,
+               payoff: Optional[Tuple[float, bool]] = None) -> PathMatrix:
+        """Merton's jump-diffusion: GBM with volatility sigma plus the jumps of bates -- the Euler scheme at
+        v0 = theta = sigma^2, kappa = sigma_v = rho = 0."""
+        return self.bates(seed, S0, r, sigma * sigma, 0.0, sigma * sigma, 0.0, 0.0, jump_intensity, jump_mean, jump_std, dt, n_steps,
+                          n_paths, path_begin=path_begin, payoff=payoff)
+
     def from_host(self, row_major: np.ndarray) -> PathMatrix:
         """Upload [n_paths][n_steps+1] (the reference's pricePaths layout)."""
         a = np.ascontiguousarray(row_major, dtype=np.float64)

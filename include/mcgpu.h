@@ -56,7 +56,8 @@ enum mcg_kernel {
     MCG_K_BATCH = 9,      /* the six kernels of mcg_batch_price_rows (one span) */
     MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics */
     MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
-    MCG_K_COUNT = 12
+    MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
+    MCG_K_COUNT = 13
 };
 
 const char* mcg_last_error(void);
@@ -242,6 +243,68 @@ int mcg_paths_bates_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, dou
                            double sigma_v, double rho, double lambda, double mu_j, double sigma_j, double dt, int n_steps,
                            uint64_t path_begin, int64_t n_paths, int scheme, double K, int is_call, mcg_paths** out,
                            mcg_paths** var_out);
+
+/* Multi-asset GBM: n_assets correlated geometric Brownian motions per path, and the reduction of the n_assets matrices to one
+ * -- a basket (negative weights: a spread), the best or the worst of the weighted assets (rainbows; weights 1 / S0_a give
+ * performance options).  Every pricer takes the combined matrix as it takes any other: European, the exotics book, LSM,
+ * LSM2 (paths = best-of, state = worst-of), Greeks, sharded prices.
+ *
+ * mcg_cholesky_corr (host only, no ctx): the lower Cholesky factor L of the correlation matrix `corr`, both row-major n x n;
+ * the part of L above the diagonal is written as 0.  Cholesky-Banachiewicz order, in binary64 with no fused multiply-add:
+ * for j = 0 .. n-1
+ *   d_j  = C_jj - sum_{k<j} L_jk^2                       (the sum from 0, in increasing k, then one subtraction)
+ *   L_jj = sqrt(d_j)
+ *   L_ij = (C_ij - sum_{k<j} L_ik L_jk) / L_jj   for i > j  (likewise)
+ * MCG_ERR_INVALID with a message: NULL corr or L; n outside [1, 8]; a non-finite entry; C_jj != 1; C_ij != C_ji; |C_ij| > 1;
+ * some d_j <= 1e-10 ("not positive definite": perfectly correlated assets are out of scope).
+ *
+ * mcg_paths_gbm_multi.  Constants, computed once on the host in binary64 (L = mcg_cholesky_corr(corr)):
+ *   drift_a = (r - q_a - sigma_a^2 / 2) dt                  q: dividend yields, NULL = zeros
+ *   A_ab    = sigma_a sqrt(dt) L_ab,  b <= a
+ * For step n = 0 .. n_steps-1, S^a_0 = S0_a:
+ *   z_b = draw n of Philox stream s(b) of (seed, global path id): block n >> 2, element n & 3, two Box-Muller pairs per block
+ *         (the RNG contract of DESIGN.md);  s(0) = 0, the price driver;  s(b) = 15 + b for b >= 1: streams 16..22.  Streams
+ *         1..5 stay with the Heston, QE, branching-process and Bates kernels.
+ *   e_a = drift_a + sum_{b<=a} A_ab z_b                     (added in increasing b; the device fuses each multiply-add)
+ *   S^a_{n+1} = S^a_n * exp(e_a)                            one exponential per asset and step
+ * Combined row, every row including row 0, with x_a = w_a S^a_n (weights NULL: all 1):
+ *   MCG_C_BASKET    acc = x_0, then acc = fma(w_a, S^a_n, acc) for a = 1 .. in asset order
+ *   MCG_C_BEST_OF   max_a x_a
+ *   MCG_C_WORST_OF  min_a x_a
+ * assets_out: an array of n_assets handles (row n of assets_out[a] is S^a_n), or NULL; combined_out: one handle of the same
+ * shape, or NULL -- not both NULL; a non-NULL combined_out needs combine != MCG_C_NONE (and weights are unused for
+ * MCG_C_NONE).  With assets_out NULL the d prices of a path never leave the registers: 8 B per path-step are stored however
+ * many assets there are.  The combined matrix of the fused call equals mcg_paths_combine of the asset matrices bit for bit, and
+ * the asset matrices have the same bits whether or not a combination was asked for.  A path depends on (seed, global path id)
+ * only: any split into shards reproduces the one-call matrices bit for bit, repeated calls are bit-identical, path_begin may
+ * be odd, n_paths = 0 gives empty matrices.  n_assets = 1 is valid: the asset matrix is then the law of mcg_paths_gbm, from the
+ * same stream (not its bits: that kernel folds sigma into the logarithm).  Asset matrices are marked `generated`; a combined
+ * matrix is `generated` iff all its inputs are, for both entry points: dS_T/dr = T S_T holds for sums, max and min
+ * (mcg_greeks_european's rho).  One launch, booked under MCG_K_MULTI.
+ * On any error every output handle is NULL (the n_assets entries of assets_out where n_assets is in range) and nothing stays
+ * allocated.
+ * MCG_ERR_INVALID with a message: NULL ctx, S0, sigma or corr; both outputs NULL; n_assets outside [1, 8]; a non-finite S0_a,
+ * r, q_a, sigma_a, dt, weight or correlation; S0_a <= 0; sigma_a < 0 (0 is valid); dt <= 0; n_steps < 1; n_paths < 0; everything
+ * mcg_cholesky_corr rejects; a combine that is none of the four values, or MCG_C_NONE with combined_out; a weight <= 0 for
+ * best-of / worst-of.  combine and weights are checked whenever combine != MCG_C_NONE, also where combined_out is NULL and
+ * nothing uses them.
+ *
+ * mcg_paths_combine: *out = the combination `kind` of n_assets matrices of this ctx with equal n_paths and n_steps -- from any
+ * generator (Heston, rBergomi, ...) or uploaded.  One launch of a streaming kernel ((n_assets + 1) * 8 B per path-step), booked
+ * under MCG_K_MULTI.  MCG_ERR_INVALID with a message: NULL ctx, assets, an assets[a] or out; n_assets outside [1, 8]; a kind
+ * other than the three combinations; a non-finite weight, or one <= 0 for best-of / worst-of; a matrix of another ctx; mismatched
+ * shapes.  *out is NULL on error.
+ *
+ * Out of scope: fused terminal payoff sums; correlated Heston or rBergomi assets; perfectly correlated (semi-definite)
+ * matrices; more than 8 assets; Greeks with respect to individual spots or correlations; multi-asset rows in the batch rows,
+ * the coalescing layer and the drop-in classes. */
+enum mcg_combine_kind { MCG_C_NONE = -1, MCG_C_BASKET = 0, MCG_C_BEST_OF = 1, MCG_C_WORST_OF = 2 };
+int mcg_cholesky_corr(const double* corr, int n, double* L);
+int mcg_paths_gbm_multi(mcg_ctx* ctx, uint64_t seed, int n_assets, const double* S0, double r, const double* q,
+                        const double* sigma, const double* corr, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                        int combine, const double* weights, mcg_paths** assets_out, mcg_paths** combined_out);
+int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
+                      mcg_paths** out);
 
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,

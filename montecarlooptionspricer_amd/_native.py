@@ -9,10 +9,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("MCG_LIB") or os.path.join(_HERE, "lib", "libmcgpu.so")  # MCG_LIB: A/B experiments with another build
 
 MCG_OK = 0
-K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC, K_HESTON = range(12)
+K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC, K_HESTON, K_MULTI = range(13)
 KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_SWEEP: "lsm_sweep",
                 K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
-                K_EXOTIC: "exotic", K_HESTON: "heston"}
+                K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi"}
 
 # enum mcg_exotic_kind (include/mcgpu.h)
 (X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXED, X_ASIAN_GEO_FLOAT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT,
@@ -22,6 +22,10 @@ EXOTIC_KINDS = {"asian_arith_fixed": X_ASIAN_ARITH_FIXED, "asian_arith_float": X
                 "lookback_fixed": X_LOOKBACK_FIXED, "lookback_float": X_LOOKBACK_FLOAT,
                 "barrier_up_out": X_BARRIER_UP_OUT, "barrier_up_in": X_BARRIER_UP_IN,
                 "barrier_down_out": X_BARRIER_DOWN_OUT, "barrier_down_in": X_BARRIER_DOWN_IN}
+
+# enum mcg_combine_kind (include/mcgpu.h)
+C_NONE, C_BASKET, C_BEST_OF, C_WORST_OF = -1, 0, 1, 2
+COMBINE_KINDS = {"basket": C_BASKET, "best_of": C_BEST_OF, "worst_of": C_WORST_OF}
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
@@ -153,6 +157,10 @@ def load_library():
                                                                           C.POINTER(vp)]
     L.mcg_paths_bates_payoff.argtypes = [vp, C.c_uint64] + [C.c_double] * 11 + [C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_double,
                                                                                  C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.mcg_cholesky_corr.argtypes = [dp, C.c_int, dp]
+    L.mcg_paths_gbm_multi.argtypes = [vp, C.c_uint64, C.c_int, dp, C.c_double, dp, dp, dp, C.c_double, C.c_int, C.c_uint64, C.c_int64,
+                                      C.c_int, dp, C.POINTER(vp), C.POINTER(vp)]
+    L.mcg_paths_combine.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, dp, C.POINTER(vp)]
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

@@ -527,6 +527,114 @@ int mcg_paths_bates_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, dou
                      scheme, true, K, is_call, out, var_out);
 }
 
+// ---- multi-asset GBM and combinations ------------------------------------------------------------
+// The weights of a combination as the kernels take them: `weights` checked, or ones.
+static int combine_weights(int n_assets, int kind, const double* weights, double (&w)[8]) {
+    if (kind != MCG_C_BASKET && kind != MCG_C_BEST_OF && kind != MCG_C_WORST_OF)
+        return fail(MCG_ERR_INVALID, "combine: kind must be MCG_C_BASKET (0), MCG_C_BEST_OF (1) or MCG_C_WORST_OF (2), not %d", kind);
+    for (int a = 0; a < n_assets; ++a) {
+        w[a] = weights ? weights[a] : 1.0;
+        if (!std::isfinite(w[a])) return fail(MCG_ERR_INVALID, "combine: weight %d must be finite", a);
+        if (kind != MCG_C_BASKET && !(w[a] > 0.0))
+            return fail(MCG_ERR_INVALID, "combine: weight %d must be > 0 for best-of / worst-of (got %g)", a, w[a]);
+    }
+    return MCG_OK;
+}
+
+int mcg_paths_gbm_multi(mcg_ctx* ctx, uint64_t seed, int n_assets, const double* S0, double r, const double* q,
+                        const double* sigma, const double* corr, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                        int combine, const double* weights, mcg_paths** assets_out, mcg_paths** combined_out) {
+    // (every output handle is NULL on any error, whichever check fails)
+    if (combined_out) *combined_out = nullptr;
+    if (assets_out && n_assets >= 1 && n_assets <= 8)
+        for (int a = 0; a < n_assets; ++a) assets_out[a] = nullptr;
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    if (n_assets < 1 || n_assets > 8) return fail(MCG_ERR_INVALID, "GBM multi: n_assets must be in [1, 8] (got %d)", n_assets);
+    if (!S0 || !sigma || !corr) return fail(MCG_ERR_INVALID, "GBM multi: S0/sigma/corr is NULL");
+    if (!assets_out && !combined_out) return fail(MCG_ERR_INVALID, "GBM multi: assets_out and combined_out are both NULL");
+    if (n_steps < 1) return fail(MCG_ERR_INVALID, "n_steps must be >= 1 (got %d)", n_steps);
+    if (n_paths < 0) return fail(MCG_ERR_INVALID, "n_paths must be >= 0 (got %lld)", (long long)n_paths);
+    if (!std::isfinite(r)) return fail(MCG_ERR_INVALID, "GBM multi: r must be finite");
+    if (!std::isfinite(dt)) return fail(MCG_ERR_INVALID, "GBM multi: dt must be finite");
+    if (!(dt > 0.0)) return fail(MCG_ERR_INVALID, "dt must be > 0");
+    double zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0}, w[8] = {1, 1, 1, 1, 1, 1, 1, 1}, L[64];
+    for (int a = 0; a < n_assets; ++a) {
+        if (!std::isfinite(S0[a])) return fail(MCG_ERR_INVALID, "GBM multi: S0[%d] must be finite", a);
+        if (!std::isfinite(sigma[a])) return fail(MCG_ERR_INVALID, "GBM multi: sigma[%d] must be finite", a);
+        if (q && !std::isfinite(q[a])) return fail(MCG_ERR_INVALID, "GBM multi: q[%d] must be finite", a);
+        if (!(S0[a] > 0.0)) return fail(MCG_ERR_INVALID, "GBM multi: S0[%d] must be > 0", a);
+        if (!(sigma[a] >= 0.0)) return fail(MCG_ERR_INVALID, "GBM multi: sigma[%d] must be >= 0", a);
+    }
+    if (combine != MCG_C_NONE) {
+        int rc = combine_weights(n_assets, combine, weights, w);
+        if (rc) return rc;
+    } else if (combined_out) {
+        return fail(MCG_ERR_INVALID, "GBM multi: combined_out needs a combine other than MCG_C_NONE");
+    }
+    int rc = mcg_cholesky_corr(corr, n_assets, L);
+    if (rc) return rc;
+    MCG_HIP(hipSetDevice(ctx->device));
+    mcg_paths* A[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    mcg_paths* Cm = nullptr;
+    auto drop = [&]() {
+        for (int a = 0; a < n_assets; ++a) mcg_paths_free(A[a]);
+        mcg_paths_free(Cm);
+    };
+    if (assets_out)
+        for (int a = 0; a < n_assets && rc == MCG_OK; ++a) rc = paths_new(ctx, n_paths, n_steps, path_begin, &A[a]);
+    if (rc == MCG_OK && combined_out) rc = paths_new(ctx, n_paths, n_steps, path_begin, &Cm);
+    if (rc == MCG_OK && n_paths > 0)
+        rc = launch_gbm_multi(ctx, assets_out ? A : nullptr, Cm, n_assets, seed, S0, r, q ? q : zeros, sigma, L, dt, combine, w);
+    if (rc) {
+        drop();
+        return rc;
+    }
+    if (assets_out)
+        for (int a = 0; a < n_assets; ++a) {
+            A[a]->generated = true;
+            assets_out[a] = A[a];
+        }
+    if (combined_out) {
+        Cm->generated = true;
+        *combined_out = Cm;
+    }
+    return MCG_OK;
+}
+
+int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
+                      mcg_paths** out) {
+    if (out) *out = nullptr;
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    if (!assets || !out) return fail(MCG_ERR_INVALID, "combine: assets/out is NULL");
+    if (n_assets < 1 || n_assets > 8) return fail(MCG_ERR_INVALID, "combine: n_assets must be in [1, 8] (got %d)", n_assets);
+    double w[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    int rc = combine_weights(n_assets, kind, weights, w);
+    if (rc) return rc;
+    bool generated = true;
+    for (int a = 0; a < n_assets; ++a) {
+        if (!assets[a]) return fail(MCG_ERR_INVALID, "combine: assets[%d] is NULL", a);
+        if (assets[a]->ctx != ctx) return fail(MCG_ERR_INVALID, "combine: assets[%d] belongs to a different ctx", a);
+        if (assets[a]->n_paths != assets[0]->n_paths || assets[a]->n_steps != assets[0]->n_steps)
+            return fail(MCG_ERR_INVALID, "combine: assets[%d] is %lld paths x %d steps, assets[0] %lld x %d", a, (long long)assets[a]->n_paths,
+                        assets[a]->n_steps, (long long)assets[0]->n_paths, assets[0]->n_steps);
+        generated = generated && assets[a]->generated;
+    }
+    MCG_HIP(hipSetDevice(ctx->device));
+    mcg_paths* P = nullptr;
+    rc = paths_new(ctx, assets[0]->n_paths, assets[0]->n_steps, assets[0]->path_begin, &P);
+    if (rc) return rc;
+    if (P->n_paths > 0) {
+        rc = launch_paths_combine(ctx, assets, n_assets, kind, w, P);
+        if (rc) {
+            mcg_paths_free(P);
+            return rc;
+        }
+    }
+    P->generated = generated;
+    *out = P;
+    return MCG_OK;
+}
+
 // ---- host <-> device ---------------------------------------------------------------------------
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols, mcg_paths** out) {
     if (!ctx || !out) return fail(MCG_ERR_INVALID, "ctx/out is NULL");

@@ -133,7 +133,7 @@ struct mcg_paths {
     int n_steps = 0;
     int64_t ld = 0;
     uint64_t path_begin = 0;
-    // made by a generator (mcg_paths_gbm* / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe* / mcg_paths_bates*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
+    // made by a generator (mcg_paths_gbm* / mcg_paths_gbm_multi and combinations of generated matrices / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe* / mcg_paths_bates*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
     bool generated = false;
     // fused terminal-payoff sums left by *_payoff generators
     bool has_sums = false;
@@ -207,6 +207,13 @@ int launch_heston_qe(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, do
 int launch_bates(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double r, double v0, double kappa,
                  double theta, double sigma_v, double rho, double lambda, double mu_j, double sigma_j, double dt, bool qe,
                  bool want_payoff, double K, int is_call);
+// multi-asset GBM (kernels_gbm_multi.hip): assets (n_assets matrices) or comb may be null, not both; L: the lower Cholesky factor
+// of the correlation matrix; q and weights: n_assets values each
+int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, int n_assets, uint64_t seed, const double* S0,
+                     double r, const double* q, const double* sigma, const double* L, double dt, int kind,
+                     const double* weights);
+int launch_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
+                         mcg_paths* out);
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);

@@ -266,6 +266,45 @@ class PathEngine:
         return self.bates(seed, S0, r, sigma * sigma, 0.0, sigma * sigma, 0.0, 0.0, jump_intensity, jump_mean, jump_std, dt, n_steps,
                           n_paths, path_begin=path_begin, payoff=payoff)
 
+    def gbm_multi(self, seed: int, S0, r: float, sigma, corr, dt: float, n_steps: int, n_paths: int, path_begin: int = 0, q=None,
+                  combine=None, weights=None, want_assets: bool = True):
+        """Correlated multi-asset GBM paths (mcg_paths_gbm_multi): S0, sigma, q (dividend yields; None: zeros) and weights
+        (None: ones) hold one value per asset, corr is the n x n correlation matrix.  combine: None, or "basket", "best_of",
+        "worst_of" (or _native.C_*) -- the combined matrix is built in the same launch from the prices in registers.  Returns
+        (assets, combined): a list of PathMatrix, one per asset (None unless want_assets), and the combined PathMatrix (None
+        unless combine is given)."""
+        S0, sigma = _vec(S0), _vec(sigma)
+        n = len(S0)
+        corr = np.ascontiguousarray(corr, dtype=np.float64)
+        if len(sigma) != n or corr.shape != (n, n):
+            raise McgError(f"gbm_multi: {n} spots need {n} volatilities and an {n} x {n} correlation matrix", 1)
+        q, weights = (None if v is None else _vec(v) for v in (q, weights))
+        if any(v is not None and len(v) != n for v in (q, weights)):
+            raise McgError(f"gbm_multi: q and weights hold one value per asset ({n})", 1)
+        kind = N.C_NONE if combine is None else _combine_kind(combine)
+        dp = C.POINTER(C.c_double)
+        ptr = lambda v: None if v is None else v.ctypes.data_as(dp)  # noqa: E731
+        handles, hc = (C.c_void_p * max(n, 1))(), C.c_void_p()
+        check(self._L.mcg_paths_gbm_multi(self._ctx, seed, n, ptr(S0), r, ptr(q), ptr(sigma), ptr(corr), dt, n_steps, path_begin, n_paths,
+                                          kind, ptr(weights), handles if want_assets else None, C.byref(hc) if combine is not None else None))
+        assets = [PathMatrix(self, C.c_void_p(h)) for h in handles] if want_assets else None
+        return assets, (PathMatrix(self, hc) if combine is not None else None)
+
+    def combine(self, paths, kind, weights=None) -> PathMatrix:
+        """One matrix from up to eight of this engine's matrices of equal shape, whatever made them (mcg_paths_combine):
+        kind "basket" (sum of w_a S^a; negative weights give spreads), "best_of" (max) or "worst_of" (min)."""
+        paths = list(paths)
+        for P in paths:
+            P._alive()
+        weights = None if weights is None else _vec(weights)
+        if weights is not None and len(weights) != len(paths):
+            raise McgError(f"combine: {len(paths)} matrices need {len(paths)} weights", 1)
+        handles = (C.c_void_p * max(len(paths), 1))(*[P._h.value for P in paths])
+        h = C.c_void_p()
+        check(self._L.mcg_paths_combine(self._ctx, handles, len(paths), _combine_kind(kind),
+                                        None if weights is None else weights.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
+        return PathMatrix(self, h)
+
     def from_host(self, row_major: np.ndarray) -> PathMatrix:
         """Upload [n_paths][n_steps+1] (the reference's pricePaths layout)."""
         a = np.ascontiguousarray(row_major, dtype=np.float64)
@@ -466,6 +505,31 @@ class PathEngine:
         ms, n = C.c_double(), C.c_int64()
         check(self._L.mcg_timing_get(self._ctx, kernel, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def _vec(x) -> np.ndarray:
+    return np.ascontiguousarray(np.atleast_1d(np.asarray(x, dtype=np.float64)))
+
+
+def _combine_kind(kind) -> int:
+    """enum mcg_combine_kind from its name or number; an unknown number goes to the library, which rejects it."""
+    if isinstance(kind, str):
+        if kind.lower() not in N.COMBINE_KINDS:
+            raise McgError(f"unknown combination {kind!r}: one of {sorted(N.COMBINE_KINDS)}", 1)
+        return N.COMBINE_KINDS[kind.lower()]
+    return int(kind)
+
+
+def cholesky_corr(corr) -> np.ndarray:
+    """Lower Cholesky factor of a correlation matrix, as the multi-asset generator takes it (mcg_cholesky_corr; host only)."""
+    L = N.load_library()
+    c = np.ascontiguousarray(corr, dtype=np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise McgError("cholesky_corr: corr must be a square matrix", 1)
+    out = np.empty_like(c)
+    dp = C.POINTER(C.c_double)
+    check(L.mcg_cholesky_corr(c.ctypes.data_as(dp), c.shape[0], out.ctypes.data_as(dp)))
+    return out
 
 
 def make_rows(rows):

@@ -57,7 +57,8 @@ enum mcg_kernel {
     MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics */
     MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
     MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
-    MCG_K_COUNT = 13
+    MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
+    MCG_K_COUNT = 14
 };
 
 const char* mcg_last_error(void);
@@ -305,6 +306,57 @@ int mcg_paths_gbm_multi(mcg_ctx* ctx, uint64_t seed, int n_assets, const double*
                         int combine, const double* weights, mcg_paths** assets_out, mcg_paths** combined_out);
 int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
                       mcg_paths** out);
+
+/* Local volatility (Dupire): dS = (r - q) S dt + sigma(t, S) S dW, with sigma given on a rectangular grid in time and spot
+ * log-moneyness x = ln(S / S0) -- the model that prices barriers, Asians and lookbacks consistently with a quoted smile.
+ *
+ * The surface: n_t time knots times[0] < ... < times[n_t - 1], n_t in [1, 64]; n_x equidistant nodes
+ * x_j = x_min + j (x_max - x_min) / (n_x - 1), n_x in [2, 128]; values sigma[i * n_x + j] >= 0 at (times[i], x_j).  Bilinear in
+ * (t, x), flat beyond the first and the last knot and outside [x_min, x_max].
+ *
+ * mcg_localvol_table (host only, no ctx): the surface as the steps read it, in binary64 with no fused multiply-add.
+ *   n_slices = 1 if n_t == 1, else n_steps
+ *   slice n belongs to step n at t = (double)n * dt -- the left end of the step decides:
+ *     t <= times[0]: row 0;   t >= times[n_t - 1]: the last row;   otherwise the i with times[i] <= t < times[i + 1],
+ *     g = (t - times[i]) / (times[i + 1] - times[i]),  sigma_{n,j} = sigma_{i,j} + g * (sigma_{i+1,j} - sigma_{i,j})
+ *   a_{n,j} = sigma_{n,j} * sqrt(dt)
+ *   d_{n,j} = a_{n,j+1} - a_{n,j},  j = 0 .. n_x - 2
+ *   table_out[(n * (n_x - 1) + j) * 2 + {0, 1}] = {a_{n,j}, d_{n,j}}       n_slices * (n_x - 1) * 2 doubles: one 16-byte entry
+ *                                                                          holds all a path-step needs of the surface
+ * Further constants of the generator, likewise:  inv_dx = (n_x - 1) / (x_max - x_min),  u0 = -x_min * inv_dx,  m = (r - q) * dt.
+ *
+ * mcg_paths_localvol.  For step n = 0 .. n_steps-1, with S_0 = S0 and X_0 = 0:
+ *   z = draw n of Philox stream 0 of (seed, global path id): block n >> 2, element n & 3   (the RNG contract of DESIGN.md)
+ *   u = min(max(fma(X_n, inv_dx, u0), 0), n_x - 1)
+ *   j = min((int)u, n_x - 2);  f = u - j
+ *   a = fma(f, d_{s,j}, a_{s,j})                      s = n, or 0 when n_slices == 1
+ *   e = fma(a, z, fma(-0.5 a, a, m))
+ *   X_{n+1} = X_n + e
+ *   S_{n+1} = S_n * exp(e)                            one exponential
+ * Row n of *out is S_n.  X is the path's own running log-moneyness, never recomputed from S.  a is continuous in X, so a
+ * last-bit difference in u at a node moves the result by a last bit only.  A flat surface gives the law of mcg_paths_gbm (and
+ * of mcg_paths_gbm_multi with one asset and the same q) from the same stream -- not its bits: the exponent is grouped
+ * differently.
+ * A path depends on (seed, global path id) only: any split into shards reproduces the one-call matrix bit for bit, repeated
+ * calls are bit-identical, path_begin may be odd, n_paths = 0 gives an empty matrix.
+ * The matrix is NOT marked as generated: S_T is homogeneous in S0 but not proportional to e^{rT}, so for mcg_greeks_european
+ * it is a plain matrix (rho NaN).
+ * The _payoff form also leaves {sum payoff, sum payoff^2, n} for mcg_price_european, as mcg_paths_gbm_payoff does (all-reduced
+ * on a ctx with a collective).  One launch per call, booked under MCG_K_LOCALVOL, behind the upload of the table on the ctx's
+ * stream.
+ * MCG_ERR_INVALID with a message, *out NULL and nothing left allocated: a NULL ctx, out, times, sigma (or table_out); n_t outside
+ * [1, 64]; n_x outside [2, 128]; times that are not finite or not strictly increasing; a non-finite or negative sigma (zero is
+ * valid); a non-finite S0, r, q, dt, x_min, x_max (or K); S0 <= 0; dt <= 0; x_min >= x_max; n_steps < 1; n_paths < 0.
+ * Out of scope: building the surface from implied volatilities (Dupire's formula); term structures of r and q; interpolation
+ * other than bilinear in (t, x); stochastic-local-volatility; local volatility in the multi-asset generator, the batch rows,
+ * the coalescing layer and the drop-in classes; sensitivities to surface nodes. */
+int mcg_localvol_table(const double* times, int n_t, int n_x, const double* sigma, double dt, int n_steps, double* table_out);
+int mcg_paths_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
+                       double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                       mcg_paths** out);
+int mcg_paths_localvol_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t,
+                              double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
+                              uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out);
 
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,

@@ -9,10 +9,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.environ.get("MCG_LIB") or os.path.join(_HERE, "lib", "libmcgpu.so")  # MCG_LIB: A/B experiments with another build
 
 MCG_OK = 0
-K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC, K_HESTON, K_MULTI = range(13)
+K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MARTINGALE, K_BRANCHING, K_BATCH, K_EXOTIC, K_HESTON, K_MULTI, K_LOCALVOL = range(14)
 KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_SWEEP: "lsm_sweep",
                 K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
-                K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi"}
+                K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi", K_LOCALVOL: "localvol"}
 
 # enum mcg_exotic_kind (include/mcgpu.h)
 (X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXED, X_ASIAN_GEO_FLOAT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT,
@@ -161,6 +161,11 @@ def load_library():
     L.mcg_paths_gbm_multi.argtypes = [vp, C.c_uint64, C.c_int, dp, C.c_double, dp, dp, dp, C.c_double, C.c_int, C.c_uint64, C.c_int64,
                                       C.c_int, dp, C.POINTER(vp), C.POINTER(vp)]
     L.mcg_paths_combine.argtypes = [vp, C.POINTER(vp), C.c_int, C.c_int, dp, C.POINTER(vp)]
+    lv = [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, dp, C.c_int, C.c_double, C.c_double, C.c_int, dp, C.c_double, C.c_int,
+          C.c_uint64, C.c_int64]
+    L.mcg_localvol_table.argtypes = [dp, C.c_int, C.c_int, dp, C.c_double, C.c_int, dp]
+    L.mcg_paths_localvol.argtypes = lv + [C.POINTER(vp)]
+    L.mcg_paths_localvol_payoff.argtypes = lv + [C.c_double, C.c_int, C.POINTER(vp)]
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

@@ -1,0 +1,266 @@
+// Local-volatility paths for gfx950 (include/mcgpu.h: mcg_paths_localvol, mcg_paths_localvol_payoff).
+//
+// k_localvol_paths<PAYOFF, ONE_SLICE> follows the skeleton of heston_device.hpp and k_gbm_multi: two adjacent paths per lane
+// with S and the running log-moneyness X in registers, fm::Tables in LDS, one Philox block of the price stream per four steps,
+// a wave-uniform row pointer plus a constant lane offset, the 16-byte nontemporal store with its `s_nop` guards,
+// fm::scaled_exp for the price and the payoff partials of heston_device.hpp.
+//
+// What is new is the surface lookup: one 16-byte gather {a_j, d_j} per path-step at a per-lane index, from LDS.
+//   ONE_SLICE  (a surface without a time axis) the slice, <= 127 entries, is staged once behind the tables.
+//   otherwise  the workgroup stages the slices of the NEXT Philox block (<= 4 * 127 entries) into one of two buffers while it
+//              steps through the other: the loads are issued at the top of a block and land in LDS at its end, one barrier
+//              per block.  The last block stages only the slices that exist.
+// Every wave of a workgroup walks through all blocks, so that the barriers match; the waves of the last workgroup that lie
+// beyond the row keep their stores to themselves.
+//
+// Roofline: HBM write, 8 B per path-step; the table (n_steps * (n_x - 1) * 16 B, 0.5 MB at 252 x 128) is read once per
+// workgroup and stays in L2.
+#include "devmath.hpp"
+#include "fastmath.hpp"
+#include "mcg_internal.hpp"
+
+namespace mcg {
+
+constexpr int LV_PPL = 2;                          // paths per lane
+constexpr int LV_SLICE_MAX = LOCALVOL_MAX_NX - 1;  // entries of a slice
+constexpr int LV_STAGE = 4 * LV_SLICE_MAX;         // entries of one staging buffer: the slices of a Philox block
+constexpr int LV_STAGE_PER_LANE = (LV_STAGE + 255) / 256;
+// Timing study (tools/build_variant.sh ... -DMCG_LV_GLOBAL_GATHER): the multi-slice kernel gathers straight from the table in
+// global memory (L2) instead of staging slices into LDS; DESIGN.md has its time.  The product stages.
+#ifdef MCG_LV_GLOBAL_GATHER
+constexpr bool LV_STAGED = false;
+#else
+constexpr bool LV_STAGED = true;
+#endif
+
+struct LocalVolArgs {
+    double* out;            // [n_steps+1][ld] prices
+    int64_t ld;
+    int64_t n_paths;
+    int n_steps;
+    int nx1;                // n_x - 1: entries of a slice
+    uint64_t path_begin;
+    uint32_t k0, k1;        // Philox key = seed
+    double S0;
+    double inv_dx, u0, m;   // LocalVolScalars
+    double u_max;           // (double)(n_x - 1)
+    const double2* surf;    // [n_slices][nx1] {a_j, d_j}
+    double K;
+    int is_call;
+    double* partials;       // [gridDim.x][2]
+    const double2* tabs;    // fm::Tables on the device
+};
+
+// One step of the contract from the slice `sl` (LDS) and the draw z.
+__device__ __forceinline__ void localvol_step(const LocalVolArgs& a, const double2* sl, double z, double& S, double& X) {
+    const double u = __builtin_fmin(__builtin_fmax(__builtin_fma(X, a.inv_dx, a.u0), 0.0), a.u_max);
+    const int j = min((int)u, a.nx1 - 1);
+    const double f = u - (double)j;
+    const double2 ad = sl[j];
+    const double s = __builtin_fma(f, ad.y, ad.x);
+    const double e = __builtin_fma(s, z, __builtin_fma(-0.5 * s, s, a.m));
+    X = X + e;
+    S = fm::scaled_exp(S, e);
+}
+
+template <bool PAYOFF, bool ONE_SLICE>
+__global__ __launch_bounds__(256) void k_localvol_paths(LocalVolArgs a) {
+    constexpr int PPL = LV_PPL;
+    constexpr bool STAGED = LV_STAGED;
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    __shared__ fm::Tables tabs;
+    __shared__ double2 slices[ONE_SLICE ? LV_SLICE_MAX : STAGED ? 2 * LV_STAGE : 1];
+    fm::load_tables(&tabs, a.tabs);
+    const fm::Tables* tab = &tabs;
+    const int nx1 = a.nx1;
+    // entries of the staging buffer of `block`: four slices, fewer in the tail
+    auto stage_count = [&](const uint32_t block) { return min(4, a.n_steps - (int)(block << 2)) * nx1; };
+    if (ONE_SLICE) {
+        if ((int)threadIdx.x < nx1) slices[threadIdx.x] = a.surf[threadIdx.x];
+    } else if (STAGED) {
+        const int cnt = stage_count(0);
+#pragma unroll
+        for (int k = 0; k < LV_STAGE_PER_LANE; ++k) {
+            const int e = (int)threadIdx.x + 256 * k;
+            if (e < cnt) slices[e] = a.surf[e];
+        }
+    }
+    __syncthreads();
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * PPL;  // first column of this lane
+    // rows are padded to 256 columns and a workgroup covers 512: the upper two waves of the last one may lie beyond the row
+    const bool in_row = i < a.ld;  // (wave-uniform)
+    double S[PPL], X[PPL];
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        S[p] = a.S0;
+        X[p] = 0.0;
+    }
+    if (in_row || !ONE_SLICE) {
+        double* row = a.out + (int64_t)blockIdx.x * (256 * PPL);
+        const unsigned lane_bytes = threadIdx.x * (8u * PPL);
+        // (the store of heston_device.hpp, with both of its guards)
+        auto store_pair = [&](double* r, const double (&x)[PPL]) {
+            if (in_row) {
+                const v2d d = {x[0], x[1]};
+                asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(d), "s"(r) : "memory");
+            }
+        };
+        store_pair(row, S);
+        PhiloxLane rng[PPL];
+#pragma unroll
+        for (int p = 0; p < PPL; ++p) rng[p] = philox_lane_setup(a.path_begin + (uint64_t)(i + p), STREAM_PRICE, a.k1);
+        uint32_t block = 0;  // the Philox block of the current four steps
+        const double2* cur = slices;
+        auto step = [&](const double (&z)[PPL], const int elem) {
+            const double2* sl = ONE_SLICE ? cur : cur + elem * nx1;
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) localvol_step(a, sl, z[p], S[p], X[p]);
+            row += a.ld;
+            store_pair(row, S);
+        };
+        auto pairs = [&](const Philox4 (&w)[PPL], bool second, double (&za)[PPL], double (&zb)[PPL]) {
+#pragma unroll
+            for (int p = 0; p < PPL; ++p)
+                fm::box_muller_pair(second ? w[p].w2 : w[p].w0, second ? w[p].w3 : w[p].w1, tab, za[p], zb[p]);
+        };
+        // Staging of the slices of block + 1 (multi-slice kernels): fetch() issues the global loads, land() writes them into the
+        // buffer the workgroup is not stepping through.  The barrier at the top of the next block orders land() against
+        // that block's reads, and this block's reads against the land() of the block after.
+        double2 held[LV_STAGE_PER_LANE];
+        auto fetch = [&]() {
+            const int cnt = stage_count(block + 1);  // <= 0 behind the last block
+            const double2* src = a.surf + (size_t)(block + 1) * 4 * nx1;
+#pragma unroll
+            for (int k = 0; k < LV_STAGE_PER_LANE; ++k) {
+                const int e = (int)threadIdx.x + 256 * k;
+                double2 v = make_double2(0.0, 0.0);  // (every element assigned: a half-written array would live in a private segment)
+                if (e < cnt) v = src[e];
+                held[k] = v;
+            }
+        };
+        auto land = [&]() {
+            const int cnt = stage_count(block + 1);
+            double2* dst = slices + ((block + 1) & 1u) * LV_STAGE;
+#pragma unroll
+            for (int k = 0; k < LV_STAGE_PER_LANE; ++k) {
+                const int e = (int)threadIdx.x + 256 * k;
+                if (e < cnt) dst[e] = held[k];
+            }
+        };
+        // The barrier between two blocks.  The wait in front of it is written out: the land() of the block before reaches this
+        // barrier over the loop's back edge, and hipcc put no wait for its LDS writes there (it does in front of the tail's).
+        auto stage_barrier = [&]() {
+            if (STAGED) {
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+        };
+        const int n_blocks = a.n_steps >> 2;
+        const int rest = a.n_steps & 3;
+        Philox4 w[PPL];
+        double za[PPL], zb[PPL];
+#pragma unroll 1
+        for (; block < (uint32_t)n_blocks; ++block) {
+            if (!ONE_SLICE) {
+                if (block) stage_barrier();
+                cur = STAGED ? slices + (block & 1u) * LV_STAGE : a.surf + (size_t)block * 4 * nx1;
+                if (STAGED) fetch();
+            }
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, a.k0, a.k1);
+            pairs(w, false, za, zb);
+            step(za, 0);
+            step(zb, 1);
+            pairs(w, true, za, zb);
+            step(za, 2);
+            step(zb, 3);
+            if (!ONE_SLICE && STAGED) land();
+        }
+        if (rest) {  // wave-uniform
+            if (!ONE_SLICE) {
+                if (block) stage_barrier();
+                cur = STAGED ? slices + (block & 1u) * LV_STAGE : a.surf + (size_t)block * 4 * nx1;
+            }
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, a.k0, a.k1);
+            pairs(w, false, za, zb);
+            step(za, 0);
+            if (rest >= 2) step(zb, 1);
+            if (rest == 3) {
+                pairs(w, true, za, zb);
+                step(za, 2);
+            }
+        }
+    }
+    if (PAYOFF) {
+        __shared__ double red[2 * 4];
+        double acc[2] = {0.0, 0.0};
+#pragma unroll
+        for (int p = 0; p < PPL; ++p) {
+            const double pay = (in_row && i + p < a.n_paths) ? payoff_of(a.is_call != 0, S[p], a.K) : 0.0;
+            acc[0] += pay;
+            acc[1] += pay * pay;
+        }
+        block_sum<2, 4>(acc, red);
+        if (threadIdx.x == 0) {
+            a.partials[2 * (int64_t)blockIdx.x] = acc[0];
+            a.partials[2 * (int64_t)blockIdx.x + 1] = acc[1];
+        }
+    }
+}
+
+// One launch of k_localvol_paths over P.  table: n_slices * (n_x - 1) entries {a, d} on the host (mcg_localvol_table), n_slices
+// = 1 or P->n_steps; it goes into the ctx's cached buffer on the ctx's stream ahead of the launch.
+int launch_localvol(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, const LocalVolScalars& c, int n_x, const double* table,
+                    int n_slices, bool want_payoff, double K, int is_call) {
+    const int64_t n_blocks = (P->n_paths + 256 * LV_PPL - 1) / (256 * LV_PPL);
+    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
+    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    if (n_x < 2 || n_x > LOCALVOL_MAX_NX || (n_slices != 1 && n_slices != P->n_steps))
+        return fail(MCG_ERR_INVALID, "local vol: a table of %d slices x %d nodes does not fit %d steps", n_slices, n_x, P->n_steps);
+    const size_t table_doubles = (size_t)n_slices * (size_t)(n_x - 1) * 2;
+    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, table_doubles);
+    if (rc) return rc;
+    if (want_payoff) {
+        rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
+        if (rc) return rc;
+    }
+    MCG_HIP(hipMemcpyAsync(ctx->weights, table, table_doubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    // the caller's table may die at return: make sure the copy has been consumed (as launch_rbergomi does)
+    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    LocalVolArgs a;
+    a.out = P->data;
+    a.ld = P->ld;
+    a.n_paths = P->n_paths;
+    a.n_steps = P->n_steps;
+    a.nx1 = n_x - 1;
+    a.path_begin = P->path_begin;
+    a.k0 = (uint32_t)seed;
+    a.k1 = (uint32_t)(seed >> 32);
+    a.S0 = S0;
+    a.inv_dx = c.inv_dx;
+    a.u0 = c.u0;
+    a.m = c.m;
+    a.u_max = (double)(n_x - 1);
+    a.surf = (const double2*)ctx->weights;
+    a.K = K;
+    a.is_call = is_call;
+    a.partials = ctx->partials;
+    a.tabs = (const double2*)ctx->log_tab;
+    {
+        TimedLaunch t(ctx, MCG_K_LOCALVOL);
+        const dim3 grid((unsigned)n_blocks), block(256);
+        if (n_slices == 1) {
+            if (want_payoff) hipLaunchKernelGGL((k_localvol_paths<true, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_localvol_paths<false, true>), grid, block, 0, ctx->stream, a);
+        } else {
+            if (want_payoff) hipLaunchKernelGGL((k_localvol_paths<true, false>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((k_localvol_paths<false, false>), grid, block, 0, ctx->stream, a);
+        }
+    }
+    MCG_HIP(hipGetLastError());
+    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
+    return MCG_OK;
+}
+
+}  // namespace mcg

@@ -635,6 +635,52 @@ int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets
     return MCG_OK;
 }
 
+// ---- local volatility ------------------------------------------------------------------------------
+static int gen_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
+                        double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                        bool payoff, double K, int is_call, mcg_paths** out) {
+    // (the model is checked before the ctx: what is wrong with a surface is reported on a machine without a GPU too)
+    if (!out) return fail(MCG_ERR_INVALID, "local vol: out is NULL");
+    *out = nullptr;
+    int rc = localvol_check_surface(times, n_t, n_x, sigma, dt, n_steps);
+    if (rc) return rc;
+    rc = localvol_check_model(S0, r, q, x_min, x_max, payoff, K);
+    if (rc) return rc;
+    if (n_paths < 0) return fail(MCG_ERR_INVALID, "n_paths must be >= 0 (got %lld)", (long long)n_paths);
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    MCG_HIP(hipSetDevice(ctx->device));
+    mcg_paths* P = nullptr;
+    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
+    if (rc) return rc;
+    if (n_paths > 0) {
+        const int n_slices = n_t == 1 ? 1 : n_steps;
+        std::vector<double> table((size_t)n_slices * (size_t)(n_x - 1) * 2);
+        localvol_fill_table(times, n_t, n_x, sigma, dt, n_steps, table.data());
+        rc = launch_localvol(ctx, P, seed, S0, localvol_scalars(r, q, x_min, x_max, n_x, dt), n_x, table.data(), n_slices, payoff, K,
+                             is_call);
+        if (rc) {
+            mcg_paths_free(P);
+            return rc;
+        }
+    }
+    *out = P;  // (not marked `generated`: mcg_internal.hpp)
+    return MCG_OK;
+}
+
+int mcg_paths_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
+                       double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
+                       mcg_paths** out) {
+    return gen_localvol(ctx, seed, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0,
+                        out);
+}
+
+int mcg_paths_localvol_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t,
+                              double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
+                              uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
+    return gen_localvol(ctx, seed, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, true, K,
+                        is_call, out);
+}
+
 // ---- host <-> device ---------------------------------------------------------------------------
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols, mcg_paths** out) {
     if (!ctx || !out) return fail(MCG_ERR_INVALID, "ctx/out is NULL");

@@ -133,7 +133,8 @@ struct mcg_paths {
     int n_steps = 0;
     int64_t ld = 0;
     uint64_t path_begin = 0;
-    // made by a generator (mcg_paths_gbm* / mcg_paths_gbm_multi and combinations of generated matrices / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe* / mcg_paths_bates*): S_T is proportional to e^{rT} (mcg_greeks_european's rho)
+    // made by a generator (mcg_paths_gbm* / mcg_paths_gbm_multi and combinations of generated matrices / mcg_paths_rbergomi* / the price matrix of mcg_paths_heston* / mcg_paths_heston_qe* / mcg_paths_bates*): S_T is proportional to e^{rT} (mcg_greeks_european's rho).
+    // Not mcg_paths_localvol*: under sigma(t, S) S_T is homogeneous in S0 but not proportional to e^{rT}; its matrix is a plain one.
     bool generated = false;
     // fused terminal-payoff sums left by *_payoff generators
     bool has_sums = false;
@@ -214,6 +215,14 @@ int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, in
                      const double* weights);
 int launch_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
                          mcg_paths* out);
+// local volatility (kernels_localvol.hip): table = the n_slices * (n_x - 1) entries {a, d} of mcg_localvol_table, on the host;
+// it is uploaded on the ctx's stream.  The scalars come from host/localvol.cpp.
+constexpr int LOCALVOL_MAX_NT = 64, LOCALVOL_MAX_NX = 128;
+struct LocalVolScalars {
+    double inv_dx, u0, m;  // (n_x - 1) / (x_max - x_min);  -x_min inv_dx;  (r - q) dt
+};
+int launch_localvol(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, const LocalVolScalars& c, int n_x, const double* table,
+                    int n_slices, bool want_payoff, double K, int is_call);
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);
@@ -277,5 +286,10 @@ int host_row_build(const double* hist, size_t n, double underlying_last, double 
                    double dividend, mcg_row* row, double features2[2]);
 int host_rbergomi_spectrum(double H, double eta, double dt, int n_steps, std::vector<double>& amp,
                            std::vector<double>& comp);
+// host/localvol.cpp: what mcg_localvol_table and mcg_paths_localvol* reject alike, the table, and the step's scalars
+int localvol_check_surface(const double* times, int n_t, int n_x, const double* sigma, double dt, int n_steps);
+int localvol_check_model(double S0, double r, double q, double x_min, double x_max, bool payoff, double K);
+void localvol_fill_table(const double* times, int n_t, int n_x, const double* sigma, double dt, int n_steps, double* table);
+LocalVolScalars localvol_scalars(double r, double q, double x_min, double x_max, int n_x, double dt);
 
 }  // namespace mcg

@@ -8,6 +8,7 @@ cross-rank all-reduce.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import weakref
 from typing import Callable, Optional, Tuple
 
@@ -305,6 +306,21 @@ class PathEngine:
                                         None if weights is None else weights.ctypes.data_as(C.POINTER(C.c_double)), C.byref(h)))
         return PathMatrix(self, h)
 
+    def local_vol(self, seed: int, S0: float, r: float, surface: "LocalVolSurface", dt: float, n_steps: int, n_paths: int,
+                  path_begin: int = 0, q: float = 0.0, payoff: Optional[Tuple[float, bool]] = None) -> PathMatrix:
+        """Local-volatility paths (mcg_paths_localvol*): dS = (r - q) S dt + sigma(t, S) S dW with sigma from `surface`, bilinear
+        in time and ln(S / S0) and flat outside its grid.  The matrix is a plain one for greeks_european (no rho)."""
+        dp = C.POINTER(C.c_double)
+        model = (self._ctx, seed, S0, r, q, surface.times.ctypes.data_as(dp), surface.n_t, surface.x_min, surface.x_max, surface.n_x,
+                 surface.sigma.ctypes.data_as(dp), dt, n_steps, path_begin, n_paths)
+        h = C.c_void_p()
+        if payoff is None:
+            check(self._L.mcg_paths_localvol(*model, C.byref(h)))
+        else:
+            K, is_call = payoff
+            check(self._L.mcg_paths_localvol_payoff(*model, K, int(bool(is_call)), C.byref(h)))
+        return PathMatrix(self, h)
+
     def from_host(self, row_major: np.ndarray) -> PathMatrix:
         """Upload [n_paths][n_steps+1] (the reference's pricePaths layout)."""
         a = np.ascontiguousarray(row_major, dtype=np.float64)
@@ -529,6 +545,46 @@ def cholesky_corr(corr) -> np.ndarray:
     out = np.empty_like(c)
     dp = C.POINTER(C.c_double)
     check(L.mcg_cholesky_corr(c.ctypes.data_as(dp), c.shape[0], out.ctypes.data_as(dp)))
+    return out
+
+
+class LocalVolSurface:
+    """A local-volatility surface sigma(t, x) on a rectangular grid (include/mcgpu.h): time knots `times` (strictly increasing,
+    1 to 64 of them), n_x equidistant nodes of the log-moneyness x = ln(S / S0) from x_min to x_max (2 to 128), and
+    sigma[i][j] >= 0 at (times[i], x_j).  A one-dimensional sigma is a surface without a time axis.  The library checks it."""
+
+    def __init__(self, times, x_min: float, x_max: float, sigma):
+        self.times = _vec(times)
+        self.sigma = np.ascontiguousarray(np.atleast_2d(np.asarray(sigma, dtype=np.float64)))
+        if self.sigma.ndim != 2 or self.sigma.shape[0] != len(self.times):
+            raise McgError(f"LocalVolSurface: {len(self.times)} time knots need {len(self.times)} rows of sigma, "
+                           f"not an array of shape {self.sigma.shape}", 1)
+        self.x_min, self.x_max = float(x_min), float(x_max)
+
+    n_t = property(lambda self: self.sigma.shape[0])
+    n_x = property(lambda self: self.sigma.shape[1])
+
+    @classmethod
+    def flat(cls, sigma: float) -> "LocalVolSurface":
+        """sigma everywhere: the law of PathEngine.gbm."""
+        return cls([0.0], -1.0, 1.0, [[sigma, sigma]])
+
+    @classmethod
+    def cev(cls, sigma0: float, beta: float, x_min: float, x_max: float, n_x: int) -> "LocalVolSurface":
+        """The CEV model dS = mu S dt + sigma0 S0^(1 - beta) S^beta dW sampled at the nodes: sigma(x) = sigma0 exp((beta - 1) x)."""
+        x = [x_min + j * (x_max - x_min) / (n_x - 1) for j in range(n_x)]
+        return cls([0.0], x_min, x_max, [[sigma0 * math.exp((beta - 1.0) * xj) for xj in x]])
+
+
+def local_vol_table(surface: LocalVolSurface, dt: float, n_steps: int) -> np.ndarray:
+    """The per-step slices of a surface as the path kernel reads them (mcg_localvol_table; host only):
+    [n_slices][n_x - 1][2] = {a_j, a_{j+1} - a_j}, a = sigma sqrt(dt); one slice for a surface with one time knot, else n_steps."""
+    L = N.load_library()
+    n_slices = 1 if surface.n_t == 1 else max(int(n_steps), 0)
+    out = np.empty((n_slices, max(surface.n_x - 1, 0), 2), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    check(L.mcg_localvol_table(surface.times.ctypes.data_as(dp), surface.n_t, surface.n_x, surface.sigma.ctypes.data_as(dp), dt, n_steps,
+                               out.ctypes.data_as(dp)))
     return out
 
 

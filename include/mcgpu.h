@@ -492,6 +492,82 @@ int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double T, 
                       const mcg_exotic* book, int n_contracts,
                       double* price, double* std_err /* may be NULL */, double* sums /* may be NULL: {sum, sum^2} per contract, then n */);
 
+/* ---- control variates for the exotics book ---------------------------------------------------- */
+/* mcg_price_exotics_cv prices the book of mcg_price_exotics with up to two control variates a contract, in the SAME one
+ * pass: the statistics, then one book kernel that keeps nine sums per contract, then host arithmetic on those sums.
+ * A control is a function of a path's five statistics (the paths' own, or a TWIN's: another matrix of the same shape, or a
+ * GBM path computed in registers from the same (seed, path id)) whose undiscounted expectation `mean` the caller knows:
+ *   MCG_CV_PAYOFF   exotic_payoff(x) as above          MCG_CV_VANILLA  max(S_T - x.K, 0) / max(x.K - S_T, 0) by x.is_call
+ *   MCG_CV_ST / MCG_CV_A / MCG_CV_G                     the statistic itself
+ * The estimator.  For contract c with payoff Y and its m in {0, 1, 2} controls a = controls[ctrl[2c]], b = controls[ctrl[2c+1]],
+ * centred on their means (d = C - mean), the nine sums over the paths, taken in a fixed order with no floating-point atomics,
+ *   sums[9c + k] = {sum Y, sum Y^2, sum d_a, sum d_a^2, sum Y d_a, sum d_b, sum d_b^2, sum Y d_b, sum d_a d_b}   (unused: 0)
+ *   sums[9 n_contracts] = n
+ * go through mcg_exotics_cv_from_sums (host only; this arithmetic and nothing else):
+ *   Ybar = sum Y / n, dbar = sum d / n;  S_yy = sum Y^2 - n Ybar^2, S_aa = sum d_a^2 - n dbar_a^2, S_ya = sum Y d_a - n Ybar dbar_a,
+ *   S_ab = sum d_a d_b - n dbar_a dbar_b (S_bb, S_yb alike).
+ *   Control a is kept iff S_aa > 1e-12 sum d_a^2 (a control that is constant on the sample is dropped), b alike.  With both kept,
+ *   rho = S_ab / sqrt(S_aa S_bb), and b is dropped if 1 - rho^2 <= 1e-8.  If a was dropped and b kept, b takes a's place in the
+ *   formulas (its beta is still reported in b's slot).  If n - 1 - (number kept) < 1, every control is dropped.
+ *   beta solves the kept normal equations in equilibrated units: u_a = S_ya / sqrt(S_aa), u_b = S_yb / sqrt(S_bb),
+ *   g_b = (u_b - rho u_a) / (1 - rho^2), g_a = u_a - rho g_b, beta = g / sqrt(S); one control: beta_a = S_ya / S_aa.
+ *   price = e^{-rT} (Ybar - sum beta dbar);  RSS = max(S_yy - sum g u, 0);  std_err = e^{-rT} sqrt(RSS / (n - 1 - kept) / n)
+ *   (0 when n - 1 - kept < 1: one path).  beta[2c], beta[2c+1]: a dropped or absent control reports 0.
+ *   plain_price, plain_se: what mcg_price_exotics computes from sum Y and sum Y^2.  n < 1 is MCG_ERR_EMPTY_PATHS.
+ * beta is estimated on the sample it corrects: the usual O(1/n) bias, far below the std error at the path counts of this
+ * library.  A contract's nine sums do not depend on the rest of the book, on where it stands, or on what else `controls` holds.
+ * The GBM twin (mcg_gbm_twin): a = sigma sqrt(dt), m = (r - q - sigma^2/2) dt; z_n = draw n of Philox stream 0 of
+ * (seed, path_begin + p) (block n >> 2, element n & 3, the usual Box-Muller pairs); X_{n+1} = X_n + fma(a, z_n, m), X_0 = 0,
+ * S_n = S0 exp(X_n); over rows first_row .. n_steps: S_T = S0 exp(X_{n_steps}), A = mean S_n, G = S0 exp(mean X_n),
+ * min = S0 exp(min X_n), max = S0 exp(max X_n).  No matrix is stored.  The twin is GBM in law from the generators' own price
+ * stream -- every generator draws its price driver from stream 0 of (seed, global path id), so it is strongly correlated with a
+ * local-volatility path of that seed -- but it is NOT mcg_paths_gbm's bits (another step formula and exponential).  A path
+ * depends on (seed, global path id) only: shards and repeats are bit-identical; odd path_begin and ids >= 2^32 are valid.
+ * Under Heston / Bates the price driver is rho z2 + sqrt(1 - rho^2) z1 with z1 from stream 0: a twin correlates with the path
+ * at most sqrt(1 - rho^2), so the gain there is modest (variance ratio <= 1 / rho^2).
+ * mcg_gbm_expectation (host only, binary64): the closed-form mean of a control under GBM on the dates t_j = j dt,
+ * j = first_row .. n_steps (N of them): MCG_CV_ST S0 e^{(r-q) n_steps dt}; MCG_CV_A (S0 / N) sum e^{(r-q) t_j} (both model-free:
+ * they hold for every generator here with that r and q; sigma is not read); ln G ~ N(mu_G, v_G), mu_G = ln S0 +
+ * (r - q - sigma^2/2) mean(t_j), v_G = sigma^2 sum_{j,k} min(t_j, t_k) / N^2: MCG_CV_G e^{mu_G + v_G/2}; MCG_CV_PAYOFF with
+ * MCG_X_ASIAN_GEO_FIXED Black's formula on (mu_G, v_G); MCG_CV_VANILLA Black-Scholes without the discount factor.  A zero
+ * variance (sigma = 0) or a strike <= 0 returns the deterministic payoff.  Any other payoff is MCG_ERR_INVALID, "no closed
+ * form".  It fills *mean and leaves c->mean alone.
+ * Rules (MCG_ERR_INVALID with a message): everything mcg_price_exotics rejects; both twins given; a control with on_twin and
+ * no twin; a twin matrix of another ctx or another shape; non-finite twin parameters or a non-finite mean; twin S0 <= 0,
+ * dt <= 0 or sigma < 0; a form out of range; a control whose payoff fields fail the book's own rules (MCG_CV_PAYOFF: as a
+ * contract; MCG_CV_VANILLA: K finite); n_controls outside [0, 1024]; a ctrl index outside [-1, n_controls);
+ * ctrl[2c+1] >= 0 with ctrl[2c] < 0.
+ * Collectives: as mcg_price_exotics -- the 9 n_contracts + 1 sums are all-reduced in one call (the node-local shm collective:
+ * in pieces of 62), every rank returns the global answer, an empty shard still takes part; a sharded in-register twin takes
+ * the shard's path_begin.  Timed under MCG_K_EXOTIC: 3 launches without a twin, 4 with either.
+ * Out of scope: antithetic or quasi-random paths; control variates for LSM and the other American pricers; more than two
+ * controls a contract; a Heston or rBergomi twin; fusing the statistics into the existing generators; the batched driver
+ * rows, the coalescing layer and the drop-in classes. */
+enum mcg_control_form { MCG_CV_PAYOFF = 0,   /* exotic_payoff(x) on the statistics            */
+                        MCG_CV_VANILLA = 1,  /* max(S_T - x.K, 0) / max(x.K - S_T, 0) by x.is_call */
+                        MCG_CV_ST = 2, MCG_CV_A = 3, MCG_CV_G = 4 };  /* the statistic itself  */
+typedef struct mcg_control { int form; int on_twin; mcg_exotic x; double mean; } mcg_control;
+/* mean: the control's known UNDISCOUNTED expectation.
+   on_twin: evaluate on the twin's statistics instead of the paths'. */
+typedef struct mcg_gbm_twin { uint64_t seed; double S0, r, q, sigma, dt; uint64_t path_begin; } mcg_gbm_twin;
+
+int mcg_price_exotics_cv(mcg_ctx* ctx, const mcg_paths* paths,
+        const mcg_paths* twin_paths /* NULL, or any matrix of this ctx and the same shape */,
+        const mcg_gbm_twin* gbm_twin /* NULL, or a twin computed in registers; not both */,
+        double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
+        const mcg_control* controls, int n_controls /* 0..1024 */,
+        const int* ctrl /* [2*n_contracts]: indices into controls, -1 = none; ctrl[2c+1] >= 0 needs ctrl[2c] >= 0 */,
+        double* price, double* std_err, double* beta /* [2*n_contracts], may be NULL */,
+        double* plain_price, double* plain_se /* may be NULL */, double* sums /* may be NULL: 9 per contract, then n */);
+/* host only: only whether a ctrl entry is >= 0 is read; std_err, beta, plain_price, plain_se may be NULL */
+int mcg_exotics_cv_from_sums(const double* sums, int n_contracts, const int* ctrl, double r, double T,
+        double* price, double* std_err, double* beta, double* plain_price, double* plain_se);
+/* the twin's statistics alone, out5[q*n_paths + p] as mcg_path_stats; n_steps >= 1, 0 <= first_row <= n_steps, n_paths >= 1 */
+int mcg_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* twin, int n_steps, int first_row, int64_t n_paths, double* host_out5);
+/* host only */
+int mcg_gbm_expectation(const mcg_control* c, double S0, double r, double q, double sigma, double dt,
+        int n_steps, int first_row, double* mean);
+
 /* Whether this ctx currently uses the one-launch LSM sweep (one launch per price up to 8.37M paths per GPU, order <= 4):
  * it is switched off for the next eight LSM prices when the in-kernel hand-shake between workgroups times out
  * (another process holding part of the GPU); mcg_price_lsm answers those -- and the call that timed out -- from the

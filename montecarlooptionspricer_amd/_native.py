@@ -23,6 +23,10 @@ EXOTIC_KINDS = {"asian_arith_fixed": X_ASIAN_ARITH_FIXED, "asian_arith_float": X
                 "barrier_up_out": X_BARRIER_UP_OUT, "barrier_up_in": X_BARRIER_UP_IN,
                 "barrier_down_out": X_BARRIER_DOWN_OUT, "barrier_down_in": X_BARRIER_DOWN_IN}
 
+# enum mcg_control_form (include/mcgpu.h)
+CV_PAYOFF, CV_VANILLA, CV_ST, CV_A, CV_G = range(5)
+CONTROL_FORMS = {"payoff": CV_PAYOFF, "vanilla": CV_VANILLA, "st": CV_ST, "a": CV_A, "g": CV_G}
+
 # enum mcg_combine_kind (include/mcgpu.h)
 C_NONE, C_BASKET, C_BEST_OF, C_WORST_OF = -1, 0, 1, 2
 COMBINE_KINDS = {"basket": C_BASKET, "best_of": C_BEST_OF, "worst_of": C_WORST_OF}
@@ -60,6 +64,17 @@ class Greeks(C.Structure):
 class Exotic(C.Structure):
     """mcg_exotic (include/mcgpu.h): one path-dependent European contract."""
     _fields_ = [("kind", C.c_int), ("is_call", C.c_int), ("K", C.c_double), ("barrier", C.c_double), ("rebate", C.c_double)]
+
+
+class Control(C.Structure):
+    """mcg_control (include/mcgpu.h): one control variate of mcg_price_exotics_cv."""
+    _fields_ = [("form", C.c_int), ("on_twin", C.c_int), ("x", Exotic), ("mean", C.c_double)]
+
+
+class GbmTwin(C.Structure):
+    """mcg_gbm_twin (include/mcgpu.h): the GBM path computed in registers from the generators' own price stream."""
+    _fields_ = [("seed", C.c_uint64), ("S0", C.c_double), ("r", C.c_double), ("q", C.c_double), ("sigma", C.c_double),
+                ("dt", C.c_double), ("path_begin", C.c_uint64)]
 
 
 class McgError(RuntimeError):
@@ -180,6 +195,11 @@ def load_library():
     L.mcg_greeks_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Greeks)]
     newer("mcg_path_stats", [vp, vp, C.c_int, dp])
     newer("mcg_price_exotics", [vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
+    newer("mcg_price_exotics_cv", [vp, vp, vp, C.POINTER(GbmTwin), C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,
+                                   C.POINTER(Control), C.c_int, C.POINTER(C.c_int), dp, dp, dp, dp, dp, dp])
+    newer("mcg_exotics_cv_from_sums", [dp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, dp, dp, dp, dp, dp])
+    newer("mcg_gbm_twin_stats", [vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
+    newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_compat_asymptotic_price.argtypes = [dp, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_price_martingale.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_int, dp, dp, dp]

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "devmath.hpp"
+#include "exotic_device.hpp"
 #include "mcg_internal.hpp"
 
 namespace mcg {
@@ -137,26 +138,6 @@ __global__ __launch_bounds__(256) void k_path_stats(const double* data, int64_t 
     else path_stats_scan<GEO, W>(col, ld, n_rows, n_paths, p0, out5);
 }
 
-// The undiscounted payoffs of include/mcgpu.h, on one path's statistics.  Strike and barrier tests are plain comparisons
-// of the stored doubles.
-__device__ __forceinline__ double exotic_payoff(const mcg_exotic& c, double st, double A, double G, double mn, double mx) {
-    const bool call = c.is_call != 0;
-    switch (c.kind) {
-        case MCG_X_ASIAN_ARITH_FIXED: return payoff_of(call, A, c.K);
-        case MCG_X_ASIAN_ARITH_FLOAT: return payoff_of(call, st, A);
-        case MCG_X_ASIAN_GEO_FIXED: return payoff_of(call, G, c.K);
-        case MCG_X_ASIAN_GEO_FLOAT: return payoff_of(call, st, G);
-        case MCG_X_LOOKBACK_FIXED: return call ? fmax(0.0, mx - c.K) : fmax(0.0, c.K - mn);
-        case MCG_X_LOOKBACK_FLOAT: return call ? st - mn : mx - st;
-        default: {
-            const bool up = c.kind == MCG_X_BARRIER_UP_OUT || c.kind == MCG_X_BARRIER_UP_IN;
-            const bool in = c.kind == MCG_X_BARRIER_UP_IN || c.kind == MCG_X_BARRIER_DOWN_IN;
-            const bool hit = up ? mx >= c.barrier : mn <= c.barrier;
-            return hit == in ? payoff_of(call, st, c.K) : c.rebate;
-        }
-    }
-}
-
 // blockIdx.y: a chunk of XB_CH contracts; blockIdx.x strides over the paths (a grid that depends on the path count only:
 // a contract's partial sums are the same whatever else the book holds and wherever it stands).
 // partials[(chunk * gridDim.x + blockIdx.x) * XB_NF + {q: sum, XB_CH + q: sum of squares}]
@@ -202,7 +183,7 @@ __global__ __launch_bounds__(256) void k_exotic_reduce(const double* partials, i
     if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * n_contracts] = n_local;
 }
 
-static int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats) {
+int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats) {
     const int n_rows = P->n_steps - first_row + 1;
     const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0;
     const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
@@ -239,7 +220,7 @@ int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host
 }
 
 // The all-reduce of a payload that may exceed what the node-local collective carries in one call.
-static int allreduce_sums(mcg_ctx* ctx, double* d, int count) {
+int exotic_allreduce_sums(mcg_ctx* ctx, double* d, int count) {
     const int piece = ctx->shm ? SHM_ALLREDUCE_MAX : count;
     for (int at = 0; at < count; at += piece)
         if (ctx->allreduce(ctx->allreduce_user, d + at, std::min(piece, count - at), (void*)ctx->stream) != 0)
@@ -278,7 +259,7 @@ static int exotic_sums(mcg_ctx* ctx, const mcg_paths* P, int first_row, const mc
             MCG_HIP(hipMemsetAsync(d_sums, 0, n_sums * sizeof(double), ctx->stream));  // an empty shard still takes part in the collective
         }
         if (ctx->allreduce) {
-            const int r2 = allreduce_sums(ctx, d_sums, n_sums);
+            const int r2 = exotic_allreduce_sums(ctx, d_sums, n_sums);
             if (r2) return r2;
         }
         h.resize(n_sums);

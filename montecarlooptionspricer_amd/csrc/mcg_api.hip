@@ -873,13 +873,28 @@ int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
 }
 
 // ---- path-dependent European payoffs ---------------------------------------------------------
-static int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row) {
+} // extern "C"
+namespace mcg {
+int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row) {
     if (!ctx || !P) return fail(MCG_ERR_INVALID, "ctx/paths is NULL");
     if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
     if (first_row < 0 || first_row > P->n_steps)
         return fail(MCG_ERR_INVALID, "first_row must be in [0, n_steps = %d] (got %d)", P->n_steps, first_row);
     return MCG_OK;
 }
+
+int exotic_contract_check(const mcg_exotic& x, const char* what, int c) {
+    if (x.kind < MCG_X_ASIAN_ARITH_FIXED || x.kind > MCG_X_BARRIER_DOWN_IN)
+        return fail(MCG_ERR_INVALID, "%s %d: kind must be in [0, 9] (got %d)", what, c, x.kind);
+    const bool barrier = x.kind >= MCG_X_BARRIER_UP_OUT;
+    const bool strike = barrier || x.kind == MCG_X_ASIAN_ARITH_FIXED || x.kind == MCG_X_ASIAN_GEO_FIXED || x.kind == MCG_X_LOOKBACK_FIXED;
+    if (strike && !std::isfinite(x.K)) return fail(MCG_ERR_INVALID, "%s %d: K must be finite", what, c);
+    if (barrier && !std::isfinite(x.barrier)) return fail(MCG_ERR_INVALID, "%s %d: barrier must be finite", what, c);
+    if (barrier && !std::isfinite(x.rebate)) return fail(MCG_ERR_INVALID, "%s %d: rebate must be finite", what, c);
+    return MCG_OK;
+}
+}  // namespace mcg
+extern "C" {
 
 int mcg_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5) {
     int rc = exotic_args(ctx, P, first_row);
@@ -897,14 +912,8 @@ int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int 
     if (!book || !price) return fail(MCG_ERR_INVALID, "book/price is NULL");
     if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
     for (int c = 0; c < n_contracts; ++c) {
-        const mcg_exotic& x = book[c];
-        if (x.kind < MCG_X_ASIAN_ARITH_FIXED || x.kind > MCG_X_BARRIER_DOWN_IN)
-            return fail(MCG_ERR_INVALID, "contract %d: kind must be in [0, 9] (got %d)", c, x.kind);
-        const bool barrier = x.kind >= MCG_X_BARRIER_UP_OUT;
-        const bool strike = barrier || x.kind == MCG_X_ASIAN_ARITH_FIXED || x.kind == MCG_X_ASIAN_GEO_FIXED || x.kind == MCG_X_LOOKBACK_FIXED;
-        if (strike && !std::isfinite(x.K)) return fail(MCG_ERR_INVALID, "contract %d: K must be finite", c);
-        if (barrier && !std::isfinite(x.barrier)) return fail(MCG_ERR_INVALID, "contract %d: barrier must be finite", c);
-        if (barrier && !std::isfinite(x.rebate)) return fail(MCG_ERR_INVALID, "contract %d: rebate must be finite", c);
+        rc = exotic_contract_check(book[c], "contract", c);
+        if (rc) return rc;
     }
     if (P->n_paths < 1 && !ctx->allreduce) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
     MCG_HIP(hipSetDevice(ctx->device));

@@ -261,6 +261,14 @@ int greeks_lsm_final(mcg_ctx* ctx, const mcg_paths* P, double K, const double* V
 int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5);
 int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
                 double* price, double* std_err, double* sums);
+// ... their pieces, shared with the control-variate pricer (kernels_exotic_cv.hip):
+// k_path_stats over rows first_row .. n_steps of P into d_stats[5][n_paths] (G only with geo); one launch under MCG_K_EXOTIC
+int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats);
+// the all-reduce of a payload that may exceed what the node-local collective carries in one call
+int exotic_allreduce_sums(mcg_ctx* ctx, double* d, int count);
+// mcg_api.hip: what mcg_price_exotics rejects of (ctx, paths, first_row) and of one contract (`what` names it in the message)
+int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row);
+int exotic_contract_check(const mcg_exotic& x, const char* what, int index);
 
 // MartingaleOptimization's refit (its driver re-accumulates on request): mo_mode 1 = first pass, leave the refinement
 // request in the coefficient block; 2 = the moments are about mo_mu, solve them with lsm_solve_centered.

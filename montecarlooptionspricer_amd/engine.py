@@ -399,6 +399,40 @@ class PathEngine:
                                         se.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
         return (price, se, sums) if return_sums else (price, se)
 
+    def gbm_twin_stats(self, twin, n_steps: int, n_paths: int, first_row: int = 1) -> np.ndarray:
+        """The five statistics of path_stats for the GBM twin computed in registers (mcg_gbm_twin_stats): twin is a dict or
+        tuple of the mcg_gbm_twin fields (seed, S0, r, q, sigma, dt, path_begin).  No matrix is stored."""
+        tw = make_twin(twin)
+        out = np.empty((5, max(int(n_paths), 0)), dtype=np.float64)
+        check(self._L.mcg_gbm_twin_stats(self._ctx, C.byref(tw), int(n_steps), int(first_row), int(n_paths),
+                                         out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def price_exotics_cv(self, paths: PathMatrix, r: float, T: float, book, controls, ctrl, first_row: int = 1, twin=None,
+                         return_sums: bool = False):
+        """price_exotics with up to two control variates a contract, in the same pass (mcg_price_exotics_cv).  controls: a
+        sequence of control(...) tuples; ctrl: per contract a pair (a, b) of indices into controls, -1 or None for none (a
+        single int means (a, -1)).  twin: None, a PathMatrix of the same shape, or a dict / tuple of the mcg_gbm_twin fields
+        (the twin computed in registers) -- what controls with on_twin read.  Returns a CvResult (price, std_err, beta[n][2],
+        plain_price, plain_se, and sums[9 n + 1] when return_sums)."""
+        paths._alive()
+        arr = make_book(book)
+        n = len(arr)
+        ctl = make_controls(controls)
+        idx = make_ctrl(ctrl, n)
+        twin_h, twin_s = None, None
+        if isinstance(twin, PathMatrix):
+            twin._alive()
+            twin_h = twin._h
+        elif twin is not None:
+            twin_s = C.byref(make_twin(twin))
+        dp = C.POINTER(C.c_double)
+        price, se, beta, pp, ps, sums = np.empty(n), np.empty(n), np.empty((n, 2)), np.empty(n), np.empty(n), np.empty(9 * n + 1)
+        check(self._L.mcg_price_exotics_cv(self._ctx, paths._h, twin_h, twin_s, r, T, int(first_row), arr, n, ctl, len(ctl), idx,
+                                           price.ctypes.data_as(dp), se.ctypes.data_as(dp), beta.ctypes.data_as(dp),
+                                           pp.ctypes.data_as(dp), ps.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
+        return CvResult(price, se, beta, pp, ps, sums if return_sums else None)
+
     def lsm_one_launch_enabled(self) -> bool:
         """False once the one-launch LSM sweep's hand-shake has timed out on this ctx (mcg_lsm_one_launch_enabled)."""
         v = C.c_int()
@@ -617,6 +651,117 @@ def make_book(book):
         vals = [c.get(k, 0) for k in names] if isinstance(c, dict) else c
         arr[i] = N.Exotic(int(vals[0]), int(bool(vals[1])), float(vals[2]), float(vals[3]), float(vals[4]))
     return arr
+
+
+class CvResult(tuple):
+    """What price_exotics_cv and exotics_cv_from_sums return: (price, std_err, beta, plain_price, plain_se), each an array over
+    the contracts (beta: [n][2]), with the same by name and .sums (None unless asked for)."""
+    FIELDS = ("price", "std_err", "beta", "plain_price", "plain_se")
+
+    def __new__(cls, price, std_err, beta, plain_price, plain_se, sums=None):
+        self = super().__new__(cls, (price, std_err, beta, plain_price, plain_se))
+        self.sums = sums
+        return self
+
+    price, std_err, beta, plain_price, plain_se = (property(lambda self, i=i: self[i]) for i in range(5))
+
+    @property
+    def variance_ratio(self):
+        """(plain_se / std_err)^2: the factor in path count the controls are worth (inf where std_err is 0)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (self.plain_se / self.std_err) ** 2
+
+
+def control(form, mean: Optional[float] = None, on_twin: bool = False, **exotic_fields) -> tuple:
+    """One control of price_exotics_cv: (form, on_twin, (kind, is_call, K, barrier, rebate), mean).  form: "payoff", "vanilla",
+    "st", "a", "g" or _native.CV_*; exotic_fields: the exotic(...) arguments the form reads (payoff: kind, is_call, K, ...;
+    vanilla: is_call, K).  mean: the control's known undiscounted expectation; None leaves it to be filled (gbm_expectation
+    returns the tuple completed)."""
+    f = N.CONTROL_FORMS.get(form.lower()) if isinstance(form, str) else (int(form) if int(form) in N.CONTROL_FORMS.values() else None)
+    if f is None:
+        raise McgError(f"unknown control form {form!r}: one of {sorted(N.CONTROL_FORMS)} or 0..4", 1)
+    unknown = set(exotic_fields) - {"kind", "is_call", "K", "barrier", "rebate"}
+    if unknown:
+        raise McgError(f"control: unknown fields {sorted(unknown)}", 1)
+    if f == N.CV_PAYOFF and "kind" not in exotic_fields:
+        raise McgError('control: form "payoff" needs kind=...', 1)
+    x = exotic(exotic_fields.get("kind", N.X_ASIAN_ARITH_FIXED), exotic_fields.get("is_call", True), exotic_fields.get("K", 0.0),
+               exotic_fields.get("barrier", 0.0), exotic_fields.get("rebate", 0.0))
+    return (f, bool(on_twin), x, None if mean is None else float(mean))
+
+
+def _control_struct(c, need_mean=True) -> "N.Control":
+    form, on_twin, x, mean = (c.get("form"), c.get("on_twin", False), c.get("x"), c.get("mean")) if isinstance(c, dict) else c
+    if mean is None and need_mean:
+        raise McgError("control: mean is not set (pass mean=..., or complete the control with gbm_expectation)", 1)
+    x = x if x is not None else (0, True, 0.0, 0.0, 0.0)
+    return N.Control(int(form), int(bool(on_twin)), N.Exotic(int(x[0]), int(bool(x[1])), float(x[2]), float(x[3]), float(x[4])),
+                     0.0 if mean is None else float(mean))
+
+
+def make_controls(controls):
+    """ctypes array of mcg_control from a sequence of control(...) tuples (at least one element long: an empty sequence gives
+    an array the library is told holds none)."""
+    arr = (N.Control * len(controls))()
+    for i, c in enumerate(controls):
+        arr[i] = _control_struct(c)
+    return arr
+
+
+def make_ctrl(ctrl, n_contracts: int):
+    """ctypes int array [2 n] from per-contract pairs (a, b), single indices a, or None."""
+    if len(ctrl) != n_contracts:
+        raise McgError(f"ctrl holds {len(ctrl)} entries for {n_contracts} contracts", 1)
+    arr = (C.c_int * (2 * max(n_contracts, 1)))()
+    for i, pair in enumerate(ctrl):
+        a, b = (pair, -1) if pair is None or isinstance(pair, (int, np.integer)) else (tuple(pair) + (-1, -1))[:2]
+        arr[2 * i], arr[2 * i + 1] = (-1 if a is None else int(a)), (-1 if b is None else int(b))
+    return arr
+
+
+def make_twin(twin) -> "N.GbmTwin":
+    """mcg_gbm_twin from a dict (seed, S0, r, sigma, dt; q and path_begin default to 0) or a tuple in the struct's order."""
+    if isinstance(twin, N.GbmTwin):
+        return twin
+    if isinstance(twin, dict):
+        unknown = set(twin) - {k for k, _ in N.GbmTwin._fields_}
+        if unknown:
+            raise McgError(f"twin: unknown fields {sorted(unknown)}", 1)
+        try:
+            return N.GbmTwin(int(twin["seed"]), float(twin["S0"]), float(twin["r"]), float(twin.get("q", 0.0)), float(twin["sigma"]),
+                             float(twin["dt"]), int(twin.get("path_begin", 0)))
+        except KeyError as e:
+            raise McgError(f"twin: field {e.args[0]!r} is missing", 1) from None
+    if len(twin) != 7:
+        raise McgError("twin: a tuple holds (seed, S0, r, q, sigma, dt, path_begin)", 1)
+    return N.GbmTwin(int(twin[0]), *(float(v) for v in twin[1:6]), int(twin[6]))
+
+
+def gbm_expectation(ctl, S0: float, r: float, sigma: float, dt: float, n_steps: int, first_row: int = 1, q: float = 0.0) -> tuple:
+    """The control completed with its closed-form mean under GBM on the dates first_row .. n_steps (mcg_gbm_expectation; host
+    only): forms "st" and "a" (model-free: sigma is not read), "g", "vanilla", and "payoff" with kind asian_geo_fixed."""
+    L = N.load_library()
+    c = _control_struct(ctl, need_mean=False)
+    m = C.c_double()
+    check(L.mcg_gbm_expectation(C.byref(c), S0, r, q, sigma, dt, int(n_steps), int(first_row), C.byref(m)))
+    form, on_twin, x, _ = (ctl.get("form"), ctl.get("on_twin", False), ctl.get("x"), None) if isinstance(ctl, dict) else ctl
+    return (form, on_twin, x, m.value)
+
+
+def exotics_cv_from_sums(sums, ctrl, r: float, T: float) -> CvResult:
+    """The estimator of price_exotics_cv from its sums[9 n + 1] (mcg_exotics_cv_from_sums; host only) -- how a caller combines
+    the sums of shards by hand.  ctrl as in price_exotics_cv (only which entries are set is read)."""
+    L = N.load_library()
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 1 or len(s) < 10 or (len(s) - 1) % 9:
+        raise McgError(f"sums holds 9 values per contract and then n, not {s.shape}", 1)
+    n = (len(s) - 1) // 9
+    idx = make_ctrl(ctrl, n)
+    dp = C.POINTER(C.c_double)
+    price, se, beta, pp, ps = np.empty(n), np.empty(n), np.empty((n, 2)), np.empty(n), np.empty(n)
+    check(L.mcg_exotics_cv_from_sums(s.ctypes.data_as(dp), n, idx, r, T, price.ctypes.data_as(dp), se.ctypes.data_as(dp),
+                                     beta.ctypes.data_as(dp), pp.ctypes.data_as(dp), ps.ctypes.data_as(dp)))
+    return CvResult(price, se, beta, pp, ps, s)
 
 
 def row_features(hist) -> Tuple[float, float]:

@@ -58,7 +58,8 @@ enum mcg_kernel {
     MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
     MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
     MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
-    MCG_K_COUNT = 14
+    MCG_K_LSM_APPLY = 14, /* mcg_lsm_apply: the forward pass of an exercise policy over a stored matrix */
+    MCG_K_COUNT = 15
 };
 
 const char* mcg_last_error(void);
@@ -410,6 +411,61 @@ int mcg_price_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, doub
  * the drop-in classes; more than one extra state; orders above 3. */
 int mcg_price_lsm2(mcg_ctx* ctx, const mcg_paths* paths, const mcg_paths* state, double r, double K, double maturity,
                    double dt, int is_call, int poly_order, double* mean, double* std_err, int64_t* n_dropped);
+
+/* ---- LSM exercise policies: fit on one path set, apply out of sample ------------------------ */
+/* mcg_price_lsm's number is mean(V_0) of a sweep that sets V = max(payoff, FITTED continuation) on the paths it was fitted
+ * on: neither a lower nor an upper bound on the American value.  A POLICY is the fitted exercise rule as plain host data;
+ * applied to independent paths (stop at the first date the rule says exercise, take the discounted payoff there) it prices
+ * a stopping time, and the value of any stopping time is a lower bound.
+ *
+ * A policy is a header and (n_steps + 1) rows of MCG_LSM_POLICY_STRIDE = 20 doubles, owned by the caller (no handle, no
+ * lifetime).  Row j:
+ *   [0..15]  c_t, the coefficients of y^t, y = (S/K - 1) - centre; entries above poly_order are 0
+ *   [16]     the number of regression rows (in-the-money paths) at the fit
+ *   [17]     the centre: 0 unless the date was re-fitted about the mean of its regressor
+ *   [18]     the kind (enum mcg_lsm_policy_kind, as a double)          [19]  0
+ * The continuation value of an EXERCISE_RULE row at price S is Horner in y with fused multiply-adds, x = fma(S, 1/K, -1),
+ * y = x - centre, cont = c_p; cont = fma(cont, y, c_t) for t = p-1 .. 0: the arithmetic the sweep itself evaluates a fit with.
+ *
+ * mcg_lsm_fit: mcg_price_lsm's estimator (mean, std_err) on the per-date route whatever the path count (as mcg_greeks_lsm:
+ * equal to mcg_price_lsm up to the summation order of the regression moments), and for every date the coefficient block
+ * that date's update actually used -- after the re-fit where there was one.  Kinds: row n_steps is TERMINAL; a date with
+ * j dt > maturity (the sweep only discounts there) is CONTINUE; a date with no in-the-money path at the fit is CONTINUE; every
+ * other date is EXERCISE_RULE.  hdr_out receives the arguments, coef_out (n_steps + 1) * 20 doubles.  poly_order in [0, 15].
+ *
+ * mcg_lsm_apply: for each path of `paths`, tau = the first j < n_steps whose row is EXERCISE_RULE with payoff(S_j) > 1e-14
+ * and !(continuation_j(S_j) > payoff(S_j)), else n_steps; v = payoff(S_tau) exp(-r dt tau) (the table exp(-r dt j) is formed
+ * on the host in binary64); mean = sum v / n, std_err from {sum v, sum v^2, n} as mcg_price_lsm forms it.  sums3 (may be NULL)
+ * receives {sum v, sum v^2, n}, tau_hist (may be NULL; n_steps + 1 counts) the number of paths with tau = j.  is_call, r, K
+ * and dt are the header's; its maturity is not read (the kinds carry it).  One forward pass over the matrix, booked under
+ * MCG_K_LSM_APPLY: 8 B per path and date at most -- a wavefront whose paths have all exercised stops reading.  Repeated calls
+ * are bit-identical (fixed-order sums, integer counts).  Sharded matrices are combined by hand: add the shards' sums3 and
+ * tau_hist.
+ *
+ * mcg_lsm_policy_continuation: host only, no ctx.  cont_out[i] = the continuation value of row `date` at S[i] for an
+ * EXERCISE_RULE row, +infinity for a CONTINUE row (the rule never exercises there), 0 for the TERMINAL row.  It checks the
+ * whole policy first, so it also serves as a policy's validator.
+ *
+ * MCG_ERR_INVALID with a message: a NULL ctx, paths, hdr, coef or mean (fit: hdr_out, coef_out); paths of another ctx;
+ * hdr.n_steps different from the matrix's; poly_order outside [0, 15]; a non-finite r, K, maturity or dt; K <= 0; dt <= 0;
+ * a kind outside {0, 1, 2}; row n_steps not TERMINAL, or another row TERMINAL; a non-finite coefficient or centre in an
+ * EXERCISE_RULE row; (continuation) a date outside [0, n_steps], n < 0, a NULL S or cont_out with n > 0; a ctx that holds a
+ * collective, for fit and apply alike.  An empty matrix is MCG_ERR_EMPTY_PATHS.
+ * Out of scope: two-regressor policies (mcg_price_lsm2); upper bounds; collectives; the one-launch sweeps; the batch rows, the
+ * coalescing layer and the drop-in classes; Greeks under a fixed policy. */
+#define MCG_LSM_POLICY_STRIDE 20
+enum mcg_lsm_policy_kind { MCG_POL_CONTINUE = 0, MCG_POL_EXERCISE_RULE = 1, MCG_POL_TERMINAL = 2 };
+typedef struct mcg_lsm_policy_hdr {
+    int n_steps, poly_order, is_call, reserved;
+    double r, K, maturity, dt;
+} mcg_lsm_policy_hdr;
+
+int mcg_lsm_fit(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, double maturity, double dt, int is_call,
+                int poly_order, double* mean, double* std_err, mcg_lsm_policy_hdr* hdr_out, double* coef_out);
+int mcg_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coef, const mcg_paths* paths, double* mean,
+                  double* std_err, double* sums3, int64_t* tau_hist);
+int mcg_lsm_policy_continuation(const mcg_lsm_policy_hdr* hdr, const double* coef, int date, const double* S, int64_t n,
+                                double* cont_out);
 
 /* ---- Greeks ----------------------------------------------------------------------------- */
 /* Price sensitivities with Monte Carlo standard errors.  Every field an entry point does not fill is NaN, and so is its

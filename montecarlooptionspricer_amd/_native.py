@@ -13,6 +13,11 @@ K_GBM, K_RBERGOMI, K_PAYOFF, K_LSM_SWEEP, K_LSM_SOLVE, K_TRANSPOSE, K_ASYM, K_MA
 KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_SWEEP: "lsm_sweep",
                 K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
                 K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi", K_LOCALVOL: "localvol"}
+K_LSM_APPLY = 14  # mcg_lsm_apply's forward pass (KERNEL_NAMES stays the table of the fourteen spans the bench tools tabulate)
+
+# LSM exercise policies (include/mcgpu.h): a row is LSM_POLICY_STRIDE doubles, slot 18 its kind
+LSM_POLICY_STRIDE = 20
+POL_CONTINUE, POL_EXERCISE_RULE, POL_TERMINAL = range(3)
 
 # enum mcg_exotic_kind (include/mcgpu.h)
 (X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXED, X_ASIAN_GEO_FLOAT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT,
@@ -59,6 +64,12 @@ class Greeks(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LsmPolicyHdr(C.Structure):
+    """mcg_lsm_policy_hdr (include/mcgpu.h): what an LSM exercise policy was fitted with."""
+    _fields_ = [("n_steps", C.c_int), ("poly_order", C.c_int), ("is_call", C.c_int), ("reserved", C.c_int),
+                ("r", C.c_double), ("K", C.c_double), ("maturity", C.c_double), ("dt", C.c_double)]
 
 
 class Exotic(C.Structure):
@@ -193,6 +204,9 @@ def load_library():
     L.mcg_lsm_one_launch_enabled.argtypes = [vp, C.POINTER(C.c_int)]
     L.mcg_greeks_european.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.POINTER(Greeks)]
     L.mcg_greeks_lsm.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Greeks)]
+    newer("mcg_lsm_fit", [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(LsmPolicyHdr), dp])
+    newer("mcg_lsm_apply", [vp, C.POINTER(LsmPolicyHdr), dp, vp, dp, dp, dp, C.POINTER(C.c_int64)])
+    newer("mcg_lsm_policy_continuation", [C.POINTER(LsmPolicyHdr), dp, C.c_int, dp, C.c_int64, dp])
     newer("mcg_path_stats", [vp, vp, C.c_int, dp])
     newer("mcg_price_exotics", [vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
     newer("mcg_price_exotics_cv", [vp, vp, vp, C.POINTER(GbmTwin), C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,

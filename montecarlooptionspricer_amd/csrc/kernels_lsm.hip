@@ -116,8 +116,9 @@ constexpr int LSM_DATE_GROUP = LSM_DATE_GROUP_N;
 constexpr int LSM_DATE_MAX_GROUPS = 2048 / LSM_DATE_GROUP;  // tickets: [0 .. MAX_GROUPS) the groups', [MAX_GROUPS] the top one
 static_assert((LSM_DATE_MAX_GROUPS + 1 + 1) / 2 <= SCALARS_DOUBLES - SC_LSM_TICKET, "the tickets fit the ctx's scalar workspace");
 
-// TAN: the K-tangent sweep's own instance, down to the block reduction (devmath.hpp: TAG).
-template <int NM, bool TAN = false>
+// TAN: the K-tangent sweep's own instance, down to the block reduction (devmath.hpp: TAG); the exporting sweep (k_lsm_date's
+// EXP) asks for a third one, TAG = 2, for the same reason.
+template <int NM, bool TAN = false, int TAG = (TAN ? 1 : 0)>
 __device__ __forceinline__ bool lsm_date_tail(const LsmDateArgs& a, bool have, double (&m)[NM], double* red, unsigned* sm_last, int date) {
     const unsigned G = gridDim.x, n_groups = (G + LSM_DATE_GROUP - 1) / LSM_DATE_GROUP;
     const unsigned grp = blockIdx.x / LSM_DATE_GROUP, first = grp * LSM_DATE_GROUP;
@@ -125,7 +126,7 @@ __device__ __forceinline__ bool lsm_date_tail(const LsmDateArgs& a, bool have, d
     double* gsum = a.partials + (int64_t)NM * G;  // [NM][n_groups]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     static_assert(LSM_DATE_GROUP <= 64, "one member per lane");
-    if (have) block_sum<NM, 4, TAN>(m, red);
+    if (have) block_sum<NM, 4, TAG>(m, red);
     if (threadIdx.x == 0) {
         const bool hooked = a.hook_mode != 0 && date == a.hook_date && (int)blockIdx.x == a.hook_wg;
         auto send = [&]() {
@@ -210,10 +211,21 @@ struct LsmDateTanArgs : LsmDateArgs {
     double* dV;   // dV/dK per path, laid out like V
 };
 
-template <int NB, bool TAN = false>
-__global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN, LsmDateTanArgs, LsmDateArgs>::type a) {
+// EXP (mcg_lsm_fit): the sweep also leaves, per date, the coefficient block that date's update was evaluated with -- the
+// block after the re-fit where the date took two launches -- in coef_out, row j (LSM_COEF_DOUBLES doubles each; dates the
+// sweep does not regress are left as the host zeroed them).  One thread of workgroup 0 stores it; like TAN, everything EXP
+// adds is under `if constexpr`, and the EXP = false instances are the kernels they were, instruction for instruction.
+struct LsmDateExpArgs : LsmDateArgs {
+    double* coef_out;
+};
+
+template <int NB, bool TAN = false, bool EXP = false>
+__global__ __launch_bounds__(256) void k_lsm_date(
+    typename std::conditional<EXP, LsmDateExpArgs, typename std::conditional<TAN, LsmDateTanArgs, LsmDateArgs>::type>::type a) {
     constexpr int NM = (TAN ? 4 : 3) * NB - 1;
     constexpr int D = LSM_DATE_DEPTH;
+    constexpr int TAIL_TAG = EXP ? 2 : (TAN ? 1 : 0);
+    static_assert(!(TAN && EXP), "the tangent sweep exports no policy");
     static_assert(!TAN || NM <= 48, "the tangent's moments fit sm_mom and the ctx's message slot");
     __shared__ double red[NM * 4];
     __shared__ double sm_mom[48];
@@ -304,7 +316,7 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
                     fetch(d, k0 + d + D, false);
                 }
             }
-            if (lsm_date_tail<NM, TAN>(a, true, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j, LSM_PH_REFINED, mu);
+            if (lsm_date_tail<NM, TAN, TAIL_TAG>(a, true, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j, LSM_PH_REFINED, mu);
             return;
         }
 #pragma unroll
@@ -314,6 +326,12 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
             for (int q = 0; q < NB; ++q) dc[q] = sm_dcoef[q];
         n_itm = sm_coef[LSM_C_COUNT];
         center = sm_coef[LSM_C_CENTER];
+        if constexpr (EXP) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+                for (int t = 0; t < LSM_COEF_DOUBLES; ++t) a.coef_out[(int64_t)j * LSM_COEF_DOUBLES + t] = sm_coef[t];
+            }
+        }
     }
     auto update = [&](double s_now, double v_old) {
         if (phase == LSM_PH_INIT) return payoff_of(call, s_now, a.K);  // LSMPricer.cpp:37-40
@@ -363,7 +381,7 @@ __global__ __launch_bounds__(256) void k_lsm_date(typename std::conditional<TAN,
             fetch(d, k0 + d + D, have);
         }
     }
-    if (lsm_date_tail<NM, TAN>(a, have, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j - 1, LSM_PH_REGULAR, 0.0);
+    if (lsm_date_tail<NM, TAN, TAIL_TAG>(a, have, m, red, &sm_last, j) && threadIdx.x == 0) lsm_date_advance(a, j - 1, LSM_PH_REGULAR, 0.0);
 }
 
 // What the solve needs to know about MartingaleOptimization's refit (its samples are not a row of the matrix, its driver
@@ -1447,6 +1465,7 @@ int lsm_reduce_allreduce_solve(mcg_ctx* ctx, int grid, int nm, int nb, double mi
 // k_lsm_date<nb> for nb = 1 .. LSM_MAX_NB (poly_order 0 .. 15); the K-tangent instances for nb = 1 .. LSM_TAN_MAX_NB
 typedef void (*LsmDateKernel)(LsmDateArgs);
 typedef void (*LsmDateTanKernel)(LsmDateTanArgs);
+typedef void (*LsmDateExpKernel)(LsmDateExpArgs);
 constexpr int LSM_TAN_MAX_NB = 9;  // poly_order <= 8: the 4p+3 moments fit the message slot and sm_mom
 static LsmDateKernel date_kernel(int nb) {
     static const LsmDateKernel k[LSM_MAX_NB] = {k_lsm_date<1>,  k_lsm_date<2>,  k_lsm_date<3>,  k_lsm_date<4>,
@@ -1462,12 +1481,22 @@ static LsmDateTanKernel date_kernel_tan(int nb) {
     return k[nb - 1];
 }
 
+static LsmDateExpKernel date_kernel_exp(int nb) {
+    static const LsmDateExpKernel k[LSM_MAX_NB] = {
+        k_lsm_date<1, false, true>,  k_lsm_date<2, false, true>,  k_lsm_date<3, false, true>,  k_lsm_date<4, false, true>,
+        k_lsm_date<5, false, true>,  k_lsm_date<6, false, true>,  k_lsm_date<7, false, true>,  k_lsm_date<8, false, true>,
+        k_lsm_date<9, false, true>,  k_lsm_date<10, false, true>, k_lsm_date<11, false, true>, k_lsm_date<12, false, true>,
+        k_lsm_date<13, false, true>, k_lsm_date<14, false, true>, k_lsm_date<15, false, true>, k_lsm_date<16, false, true>};
+    return k[nb - 1];
+}
+
 // Workgroups of k_lsm_date<nb> a CU holds at once: the per-date route launches exactly one resident wave of them.
-static int date_kernel_occupancy(int nb, bool tan = false) {
-    static std::atomic<int> cache[2][LSM_MAX_NB + 1];
-    int occ = cache[tan][nb].load(std::memory_order_relaxed);
+// flavour: 0 the price-only kernels, 1 the K-tangent ones, 2 the exporting ones.
+static int date_kernel_occupancy(int nb, int flavour = 0) {
+    static std::atomic<int> cache[3][LSM_MAX_NB + 1];
+    int occ = cache[flavour][nb].load(std::memory_order_relaxed);
     if (occ > 0) return occ;
-    const void* fn = tan ? (const void*)date_kernel_tan(nb) : (const void*)date_kernel(nb);
+    const void* fn = flavour == 1 ? (const void*)date_kernel_tan(nb) : flavour == 2 ? (const void*)date_kernel_exp(nb) : (const void*)date_kernel(nb);
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 256, 0) != hipSuccess || occ < 1) {
         (void)hipGetLastError();
         occ = 1;
@@ -1476,12 +1505,17 @@ static int date_kernel_occupancy(int nb, bool tan = false) {
     // tickets to the tail (C5 shard, span per pass: 10.86 ms at four, 10.69 at three and at two)
     const int want = std::max(1, study_switch("MCG_LSM_DATE_WGS_PER_CU", 3));
     occ = std::min(occ, want);
-    cache[tan][nb].store(occ, std::memory_order_relaxed);
+    cache[flavour][nb].store(occ, std::memory_order_relaxed);
     return occ;
 }
 
-static void launch_date(mcg_ctx* ctx, int nb, int grid, const LsmDateArgs& a, double* dV) {
-    if (dV) {
+static void launch_date(mcg_ctx* ctx, int nb, int grid, const LsmDateArgs& a, double* dV, double* coef_out) {
+    if (coef_out) {
+        LsmDateExpArgs t;
+        static_cast<LsmDateArgs&>(t) = a;
+        t.coef_out = coef_out;
+        hipLaunchKernelGGL(date_kernel_exp(nb), dim3(grid), dim3(256), 0, ctx->stream, t);
+    } else if (dV) {
         LsmDateTanArgs t;
         static_cast<LsmDateArgs&>(t) = a;
         t.dV = dV;
@@ -1492,20 +1526,20 @@ static void launch_date(mcg_ctx* ctx, int nb, int grid, const LsmDateArgs& a, do
 }
 
 // Grid of the per-date route: 512 paths per workgroup and trip, at most one resident wave, at most the tickets' groups.
-static int date_grid(mcg_ctx* ctx, int64_t N, int nb, bool tan) {
-    int grid = (int)std::min<int64_t>((N + 511) / 512, (int64_t)ctx->n_cus * date_kernel_occupancy(nb, tan));
+static int date_grid(mcg_ctx* ctx, int64_t N, int nb, int flavour) {
+    int grid = (int)std::min<int64_t>((N + 511) / 512, (int64_t)ctx->n_cus * date_kernel_occupancy(nb, flavour));
     grid = std::min(grid, LSM_DATE_GROUP * LSM_DATE_MAX_GROUPS);
     return grid < 1 ? 1 : grid;
 }
 
 static int run_lsm_dates(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int nb,
-                         int grid, double* dV);
+                         int grid, double* dV, double* coef_out = nullptr);
 
 int run_lsm(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
             int poly_order, double* mean, double* std_err) {
     const int nb = poly_order + 1;
     const int64_t N = P->n_paths;
-    const int grid = date_grid(ctx, N, nb, false);
+    const int grid = date_grid(ctx, N, nb, 0);
 
     int rc;
     bool done = false;
@@ -1562,8 +1596,10 @@ int lsm_finish(mcg_ctx* ctx, int grid, int64_t N, double* mean, double* std_err)
 
 // The per-date sweep: every date's launch (and, sharded, its collective) up to date 0, leaving V_0 in ctx->lsm_v.
 // dV != nullptr: the K-tangent sweep (k_lsm_date<nb, true>), leaving dV_0/dK in dV (N + 1 doubles, 16-byte aligned).
+// coef_out != nullptr (and dV == nullptr): the exporting sweep (k_lsm_date<nb, false, true>), leaving every regressed date's
+// coefficient block in coef_out (device, (n_steps + 1) * LSM_COEF_DOUBLES doubles, zeroed by the caller).
 static int run_lsm_dates(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int nb,
-                         int grid, double* dV) {
+                         int grid, double* dV, double* coef_out) {
     const int nm = (dV ? 4 : 3) * nb - 1;
     const int64_t N = P->n_paths;
     const int M = P->n_steps + 1;
@@ -1628,7 +1664,7 @@ static int run_lsm_dates(mcg_ctx* ctx, const mcg_paths* P, double r, double K, d
                         return fail(MCG_ERR_COMM, "all-reduce of regression moments failed");
                 }
                 first = false;
-                launch_date(ctx, nb, grid, a, dV);
+                launch_date(ctx, nb, grid, a, dV, coef_out);
             }
         }
         g_stats.lsm_per_date_launches.fetch_add(batch, std::memory_order_relaxed);
@@ -1675,9 +1711,32 @@ int run_lsm_greeks(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
     const int64_t N = P->n_paths;
     int rc = ensure_cap(ctx, &ctx->lsm_dv, &ctx->lsm_dv_cap, (size_t)std::max<int64_t>(N, 1) + 1);  // padded like V
     if (rc) return rc;
-    rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, date_grid(ctx, N, nb, true), ctx->lsm_dv);
+    rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, date_grid(ctx, N, nb, 1), ctx->lsm_dv);
     if (rc) return rc;
     return greeks_lsm_final(ctx, P, K, ctx->lsm_v, ctx->lsm_dv, out);
+}
+
+// mcg_lsm_fit: mcg_price_lsm's estimator on the per-date route whatever the path count (single GPU), with every date's
+// coefficient block exported (k_lsm_date's EXP) into the ctx's table workspace and downloaded ONCE after the sweep:
+// blocks_out receives (n_steps + 1) blocks of LSM_COEF_DOUBLES doubles as the solves wrote them (host/lsm_policy.cpp turns
+// them into policy rows).
+int run_lsm_fit(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int poly_order,
+                double* mean, double* std_err, double* blocks_out) {
+    static_assert(LSM_COEF_DOUBLES == MCG_LSM_POLICY_STRIDE, "an exported block is a policy row");
+    const int nb = poly_order + 1;
+    const int64_t N = P->n_paths;
+    const size_t doubles = (size_t)(P->n_steps + 1) * LSM_COEF_DOUBLES;
+    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, doubles);
+    if (rc) return rc;
+    MCG_HIP(hipMemsetAsync(ctx->weights, 0, doubles * sizeof(double), ctx->stream));
+    const int grid = date_grid(ctx, N, nb, 2);
+    rc = run_lsm_dates(ctx, P, r, K, maturity, dt, is_call, nb, grid, nullptr, ctx->weights);
+    if (rc) return rc;
+    rc = lsm_finish(ctx, grid, N, mean, std_err);
+    if (rc) return rc;
+    MCG_HIP(hipMemcpyAsync(blocks_out, ctx->weights, doubles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    return MCG_OK;
 }
 
 }  // namespace mcg

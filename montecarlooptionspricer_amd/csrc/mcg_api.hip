@@ -844,6 +844,52 @@ int mcg_price_lsm2(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* F, double 
     return run_lsm2(ctx, P, F, r, K, maturity, dt, is_call, poly_order, mean, std_err, n_dropped);
 }
 
+// ---- LSM exercise policies ---------------------------------------------------------------------
+int mcg_lsm_fit(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int poly_order,
+                double* mean, double* std_err, mcg_lsm_policy_hdr* hdr_out, double* coef_out) {
+    if (!ctx || !P || !mean || !hdr_out || !coef_out) return fail(MCG_ERR_INVALID, "ctx/paths/mean/hdr_out/coef_out is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    int rc = lsm_policy_check_header(P->n_steps, poly_order, r, K, maturity, dt);
+    if (rc) return rc;
+    if (ctx->allreduce || ctx->rccl_comm || ctx->shm)
+        return fail(MCG_ERR_INVALID, "sharded policy fits are not supported: this ctx holds a collective");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "LSM::PredictOptionPrice: Empty pricePaths.");
+    MCG_HIP(hipSetDevice(ctx->device));
+    rc = run_lsm_fit(ctx, P, r, K, maturity, dt, is_call, poly_order, mean, std_err, coef_out);
+    if (rc) return rc;
+    hdr_out->n_steps = P->n_steps;
+    hdr_out->poly_order = poly_order;
+    hdr_out->is_call = is_call != 0 ? 1 : 0;
+    hdr_out->reserved = 0;
+    hdr_out->r = r;
+    hdr_out->K = K;
+    hdr_out->maturity = maturity;
+    hdr_out->dt = dt;
+    lsm_policy_from_blocks(hdr_out, coef_out);
+    return MCG_OK;
+}
+
+int mcg_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coef, const mcg_paths* P, double* mean,
+                  double* std_err, double* sums3, int64_t* tau_hist) {
+    if (!ctx || !P || !hdr || !coef || !mean) return fail(MCG_ERR_INVALID, "ctx/paths/hdr/coef/mean is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    if (hdr->n_steps != P->n_steps)
+        return fail(MCG_ERR_INVALID, "the policy has %d steps, the matrix %d", hdr->n_steps, P->n_steps);
+    int rc = lsm_policy_check(hdr, coef);
+    if (rc) return rc;
+    if (ctx->allreduce || ctx->rccl_comm || ctx->shm)
+        return fail(MCG_ERR_INVALID, "this ctx holds a collective: apply the policy per shard and add the shards' sums3 and tau_hist");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    MCG_HIP(hipSetDevice(ctx->device));
+    double s[3];
+    rc = run_lsm_apply(ctx, hdr, coef, P, s, tau_hist);
+    if (rc) return rc;
+    if (sums3)
+        for (int q = 0; q < 3; ++q) sums3[q] = s[q];
+    sums_to_mean_stderr(s[0], s[1], s[2], mean, std_err);
+    return MCG_OK;
+}
+
 // ---- Greeks ----------------------------------------------------------------------------------
 static int greeks_args(mcg_ctx* ctx, const mcg_paths* P, mcg_greeks* out) {
     if (!ctx || !P || !out) return fail(MCG_ERR_INVALID, "ctx/paths/out is NULL");

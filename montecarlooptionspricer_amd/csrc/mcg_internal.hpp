@@ -251,6 +251,16 @@ int lsm_finish(mcg_ctx* ctx, int grid, int64_t n_paths, double* mean, double* st
 // the two-regressor sweep (kernels_lsm2.hip): F has P's shape
 int run_lsm2(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* F, double r, double K, double maturity, double dt, int is_call,
              int poly_order, double* mean, double* std_err, int64_t* n_dropped);
+// LSM exercise policies: the exporting per-date sweep (kernels_lsm.hip), the forward pass (kernels_lsm_policy.hip) and the
+// host side (host/lsm_policy.cpp: checks, the rows exported blocks become, the discount table exp(-r dt j))
+int run_lsm_fit(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call, int poly_order,
+                double* mean, double* std_err, double* blocks_out);
+int run_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coef, const mcg_paths* P, double out3[3],
+                  int64_t* tau_hist);
+int lsm_policy_check_header(int n_steps, int poly_order, double r, double K, double maturity, double dt);
+int lsm_policy_check(const mcg_lsm_policy_hdr* hdr, const double* coef);
+void lsm_policy_from_blocks(const mcg_lsm_policy_hdr* hdr, double* coef);
+void lsm_policy_discounts(const mcg_lsm_policy_hdr* hdr, double* disc);
 // Greeks (kernels_greeks.hip; the LSM tangent sweep in kernels_lsm.hip)
 int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,
                         mcg_greeks* out);

@@ -358,6 +358,37 @@ class PathEngine:
                                      C.byref(m), C.byref(se), C.byref(nd)))
         return (m.value, se.value, nd.value) if return_dropped else (m.value, se.value)
 
+    def fit_lsm(self, paths: PathMatrix, r: float, K: float, maturity: float, dt: float, is_call: bool, poly_order: int):
+        """price_lsm's estimator on the per-date route, and the exercise rule the sweep fitted (mcg_lsm_fit): returns
+        (price, std_err, LsmPolicy).  poly_order in [0, 15]."""
+        paths._alive()
+        m, se, hdr = C.c_double(), C.c_double(), N.LsmPolicyHdr()
+        coef = np.zeros((paths.n_steps + 1, N.LSM_POLICY_STRIDE))
+        check(self._L.mcg_lsm_fit(self._ctx, paths._h, r, K, maturity, dt, int(bool(is_call)), int(poly_order), C.byref(m),
+                                  C.byref(se), C.byref(hdr), coef.ctypes.data_as(C.POINTER(C.c_double))))
+        return m.value, se.value, LsmPolicy(hdr.n_steps, hdr.poly_order, hdr.is_call != 0, hdr.r, hdr.K, hdr.maturity, hdr.dt, coef)
+
+    def apply_lsm(self, policy: "LsmPolicy", paths: PathMatrix, return_hist: bool = False, return_sums: bool = False):
+        """The policy applied to (independent) paths: every path stops at the first date the rule says exercise and takes the
+        discounted payoff there -- a lower bound on the American value whatever the rule (mcg_lsm_apply).  Returns (price,
+        std_err), then tau_hist (n_steps + 1 counts of stopping dates) when return_hist, then sums3 = {sum v, sum v^2, n} when
+        return_sums."""
+        paths._alive()
+        m, se = C.c_double(), C.c_double()
+        dp = C.POINTER(C.c_double)
+        hist = np.zeros(policy.n_steps + 1, dtype=np.int64)
+        sums = np.zeros(3)
+        hdr = policy._hdr()
+        check(self._L.mcg_lsm_apply(self._ctx, C.byref(hdr), policy.coef.ctypes.data_as(dp), paths._h, C.byref(m), C.byref(se),
+                                    sums.ctypes.data_as(dp) if return_sums else None,
+                                    hist.ctypes.data_as(C.POINTER(C.c_int64)) if return_hist else None))
+        out = (m.value, se.value)
+        if return_hist:
+            out += (hist,)
+        if return_sums:
+            out += (sums,)
+        return out
+
     def greeks_european(self, paths: PathMatrix, K: float, r: float, T: float, is_call: bool,
                         sigma: Optional[float] = None) -> dict:
         """European price, delta, gamma, vega, rho, dual delta and their std errors (mcg_greeks_european); NaN where a
@@ -608,6 +639,63 @@ class LocalVolSurface:
         """The CEV model dS = mu S dt + sigma0 S0^(1 - beta) S^beta dW sampled at the nodes: sigma(x) = sigma0 exp((beta - 1) x)."""
         x = [x_min + j * (x_max - x_min) / (n_x - 1) for j in range(n_x)]
         return cls([0.0], x_min, x_max, [[sigma0 * math.exp((beta - 1.0) * xj) for xj in x]])
+
+
+class LsmPolicy:
+    """An LSM exercise policy (include/mcgpu.h): the header fields n_steps, poly_order, is_call, r, K, maturity, dt, and coef,
+    an (n_steps + 1, 20) array of rows {16 coefficients of y^t, y = (S/K - 1) - centre; regression rows at the fit; centre;
+    kind; 0}.  Plain host data: PathEngine.fit_lsm returns one, from_arrays builds one by hand, PathEngine.apply_lsm reads
+    one.  The library checks it where it is used."""
+
+    def __init__(self, n_steps: int, poly_order: int, is_call: bool, r: float, K: float, maturity: float, dt: float, coef):
+        self.n_steps, self.poly_order, self.is_call = int(n_steps), int(poly_order), bool(is_call)
+        self.r, self.K, self.maturity, self.dt = float(r), float(K), float(maturity), float(dt)
+        self.coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if self.coef.shape != (self.n_steps + 1, N.LSM_POLICY_STRIDE):
+            raise McgError(f"LsmPolicy: {self.n_steps} steps need coef of shape ({self.n_steps + 1}, {N.LSM_POLICY_STRIDE}), "
+                           f"not {self.coef.shape}", 1)
+
+    @classmethod
+    def from_arrays(cls, n_steps: int, poly_order: int, is_call: bool, r: float, K: float, maturity: float, dt: float,
+                    coefficients=None, kinds=None, centres=None, counts=None) -> "LsmPolicy":
+        """A hand-made policy.  coefficients: (n_steps + 1, <= 16), c_t of y^t per date (default 0); kinds: n_steps + 1 of
+        POL_CONTINUE / POL_EXERCISE_RULE / POL_TERMINAL (default: EXERCISE_RULE on every date, TERMINAL on the last row);
+        centres, counts: per date (default 0)."""
+        rows = int(n_steps) + 1
+        coef = np.zeros((max(rows, 0), N.LSM_POLICY_STRIDE))
+        if coefficients is not None:
+            c = np.atleast_2d(np.asarray(coefficients, dtype=np.float64))
+            if c.shape[0] != rows or c.shape[1] > 16:
+                raise McgError(f"LsmPolicy.from_arrays: coefficients must have shape ({rows}, <= 16), not {c.shape}", 1)
+            coef[:, :c.shape[1]] = c
+        if kinds is None:
+            kinds = [N.POL_EXERCISE_RULE] * (rows - 1) + [N.POL_TERMINAL]
+        coef[:, 18] = _vec(kinds)
+        if counts is not None:
+            coef[:, 16] = _vec(counts)
+        if centres is not None:
+            coef[:, 17] = _vec(centres)
+        return cls(n_steps, poly_order, is_call, r, K, maturity, dt, coef)
+
+    @property
+    def kinds(self) -> np.ndarray:
+        """Per date: POL_CONTINUE, POL_EXERCISE_RULE or POL_TERMINAL."""
+        return self.coef[:, 18].astype(np.int64)
+
+    def _hdr(self) -> "N.LsmPolicyHdr":
+        return N.LsmPolicyHdr(self.n_steps, self.poly_order, int(self.is_call), 0, self.r, self.K, self.maturity, self.dt)
+
+    def continuation(self, j: int, S) -> np.ndarray:
+        """The continuation value of date j at the prices S (mcg_lsm_policy_continuation; host only): Horner for an
+        EXERCISE_RULE date, +inf for a CONTINUE date, 0 for the terminal one."""
+        L = N.load_library()
+        s = _vec(S)
+        out = np.empty_like(s)
+        dp = C.POINTER(C.c_double)
+        hdr = self._hdr()
+        check(L.mcg_lsm_policy_continuation(C.byref(hdr), self.coef.ctypes.data_as(dp), int(j), s.ctypes.data_as(dp), s.size,
+                                            out.ctypes.data_as(dp)))
+        return out
 
 
 def local_vol_table(surface: LocalVolSurface, dt: float, n_steps: int) -> np.ndarray:

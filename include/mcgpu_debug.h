@@ -16,8 +16,16 @@ extern "C" {
  * fn 3: x holds a 32-bit Philox word wb as a double; y[0], y[1] = cos, sin(2 pi ((wb>>8)+1/2) 2^-24)
  * fn 4: x holds a path id as a double; y[0..3] = the four normals of block 0, stream 0, seed 1
  * fn 5: as 4 through the reference-grade (device library) implementation.
- * fn 6: y[0] = e^x for |x| <= 0.125 (the branch-free step exponential)   fn 7: the same for |x| <= 0.1. */
+ * fn 6: y[0] = e^x for |x| <= 0.125 (the branch-free step exponential)   fn 7: the same for |x| <= 0.1.
+ * fn 10: as 3 by the two 4096-entry tables (fm::sincos_two_level), read from device memory. */
 int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n);
+/* Test hook, host-only: the two tables of fm::sincos_two_level as the contexts upload them, 4096 {cos, sin} pairs each:
+ * coarse[i] = (cos, sin)(2 pi i / 4096), fine[j] = (cos, sin)(2 pi (j + 1/2) / 2^24). */
+int mcg_debug_sincos2_tables(double* coarse, double* fine);
+/* Test hook: which kernel the GBM generators of this context launch -- route 0 = by size (the product's choice), 1 = the
+ * narrow kernel (k_gbm_paths), 2 = the wide one (k_gbm_paths_wide), -1 = leave it as it is; *last_route (may be NULL) = what
+ * the last GBM launch took (1 or 2; 0 before the first). */
+int mcg_debug_gbm_route(mcg_ctx* ctx, int route, int* last_route);
 /* Test hooks of the one-launch LSM sweeps' hand-shake: spin_limit = polling rounds before a wait gives up (0: every
  * wait gives up at once, which drives the time-out -> per-date fall-back on a healthy device; < 0: the default);
  * poll_delay = units of ~4 us by which workgroups other than the reducing one reach their coefficient poll late. */

@@ -166,6 +166,8 @@ def load_library():
                             C.POINTER(Row), C.POINTER(C.c_double)])
     newer("mcg_batch_price_rows6", [vp, C.POINTER(Row), C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int,
                                     C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_double)])
+    newer("mcg_debug_sincos2_tables", [dp, dp])
+    newer("mcg_debug_gbm_route", [vp, C.c_int, C.POINTER(C.c_int)])
     L.mcg_paths_gbm.argtypes = [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                 C.c_uint64, C.c_int64, C.POINTER(vp)]
     L.mcg_paths_gbm_payoff.argtypes = [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -9,6 +9,7 @@
 //   neg2log(u, tab)         -2 ln u           u in (0, 1); 1024-entry {1/c, -2 ln c} table in LDS
 //   sqrt_pos(x)             sqrt(x)           x in [1e-300, 1e300], no denormal/negative handling
 //   sincos_table(wb, tab)   cos/sin(2 pi f)   f = ((wb >> 8) + 1/2) 2^-24, from the raw Philox word; 1024-entry table
+//   sincos_two_level(wb, coarse, fine)   the same from two 4096-entry tables and one complex product
 //   normal_quad_fast(...)   the four normals of one Philox block (philox.hpp's contract)
 //
 // Polynomials: interpolation at Chebyshev nodes in 60-digit arithmetic, rounded to binary64
@@ -375,6 +376,60 @@ __device__ __forceinline__ void box_muller_pair_affine_scaled(uint32_t wa, uint3
     const double rad = sqrt_pos(neg2log_scaled(radius_u01(wa, wb), tab->log, L));  // = vol * sqrt(-2 ln u)
     double c, s;
     sincos_table<T::SC_BITS>(wb, tab->sincos, c, s);
+    a0 = __builtin_fma(rad, c, shift);
+    a1 = __builtin_fma(rad, s, shift);
+}
+
+// ---- sin/cos from two tables -----------------------------------------------------------------------------------
+// The angle's 24 bits split 12 + 12: 2 pi f = 2 pi i / 4096 + 2 pi (j + 1/2) / 2^24 with i = wb >> 20 and
+// j = (wb >> 8) & 4095, both halves tabulated (host/sincos2.cpp: coarse[i], fine[j], each {cos, sin} within 0.51 ulp), so
+// cos/sin(2 pi f) is ONE complex product: 2 multiplies + 2 FMAs against the 12 fp64 instructions of sincos_table (no
+// series, no integer -> double conversion, no constants).  Exhaustively over the 2^24 angles: absolute error <= 1.64e-16,
+// |c^2 + s^2 - 1| <= 4.5e-16.  The price is 128 KiB of tables: in LDS that is one workgroup per CU (k_gbm_paths_wide).
+// Plain pointers: LDS or device memory.
+constexpr int SINCOS2_BITS = 12;
+constexpr int SINCOS2_ENTRIES = 1 << SINCOS2_BITS;
+__device__ __forceinline__ void sincos_two_level_entries(const double2 C, const double2 F, double& c_out, double& s_out) {
+    c_out = __builtin_fma(C.x, F.x, -(C.y * F.y));
+    s_out = __builtin_fma(C.y, F.x, C.x * F.y);
+}
+__device__ __forceinline__ void sincos_two_level(uint32_t wb, const double2* coarse, const double2* fine, double& c_out,
+                                                 double& s_out) {
+    sincos_two_level_entries(coarse[wb >> (32 - SINCOS2_BITS)], fine[(wb >> 8) & (SINCOS2_ENTRIES - 1u)], c_out, s_out);
+}
+
+// neg2log_scaled from a table entry already read
+__device__ __forceinline__ double neg2log_entry_scaled(const LogSplit& sp, const double2 e, const LogScale& L) {
+    const double r = __builtin_fma(sp.z, e.x, -1.0);
+    double q = L.q3;
+    q = fma_sc(q, r, L.q2);
+    q = fma_sc(q, r, L.q1);
+    q = fma_sc(q, r, L.q0);
+    const double P = __builtin_fma(r, q, L.c_l);
+    const double base = __builtin_fma((double)sp.k, L.c_k, e.y);
+    return __builtin_fma(r, P, base);
+}
+
+// box_muller_pair_affine / box_muller_pair_affine_scaled with the two-level sin/cos.  The pair's three table entries
+// (logarithm, coarse, fine) are requested together, before the first is used; the radius is the same bits as theirs.
+__device__ __forceinline__ void box_muller_pair_affine2(uint32_t wa, uint32_t wb, const double2* log_tab, const double2* coarse,
+                                                        const double2* fine, double scale, double shift, double& a0, double& a1) {
+    const LogSplit sp = log_split(radius_u01(wa, wb));
+    const double2 L = log_tab[sp.idx], C = coarse[wb >> (32 - SINCOS2_BITS)], F = fine[(wb >> 8) & (SINCOS2_ENTRIES - 1u)];
+    const double rad = scale * sqrt_pos(neg2log_entry(sp, L));
+    double c, s;
+    sincos_two_level_entries(C, F, c, s);
+    a0 = __builtin_fma(rad, c, shift);
+    a1 = __builtin_fma(rad, s, shift);
+}
+__device__ __forceinline__ void box_muller_pair_affine_scaled2(uint32_t wa, uint32_t wb, const double2* log_tab,
+                                                               const double2* coarse, const double2* fine, const LogScale& Ls,
+                                                               double shift, double& a0, double& a1) {
+    const LogSplit sp = log_split(radius_u01(wa, wb));
+    const double2 L = log_tab[sp.idx], C = coarse[wb >> (32 - SINCOS2_BITS)], F = fine[(wb >> 8) & (SINCOS2_ENTRIES - 1u)];
+    const double rad = sqrt_pos(neg2log_entry_scaled(sp, L, Ls));  // = vol * sqrt(-2 ln u)
+    double c, s;
+    sincos_two_level_entries(C, F, c, s);
     a0 = __builtin_fma(rad, c, shift);
     a1 = __builtin_fma(rad, s, shift);
 }

@@ -40,6 +40,10 @@ struct GbmArgs {
     // of them for the kernel's life, the stamps pushed Horner constants out into spilled lanes)
     unsigned long long* clk;
     unsigned clk_first, clk_shift;
+    // k_gbm_paths_wide only (there the stamping units are tiles, and partials is [n_tiles][2])
+    const double2* sincos2;  // host_sincos2_tables() on the device: coarse, then fine
+    unsigned* ticket;        // tile counter, zeroed on the stream before the launch
+    unsigned n_tiles;        // ld / 128
 };
 
 // MODE 0: any parameters.  MODE 1 (SMALL): the host has checked |drift| + vol * 7.55 <= 0.125, so every step's exponent
@@ -184,6 +188,151 @@ __global__ __launch_bounds__(256) void k_gbm_paths(GbmArgs a) {
     }
 }
 
+// The generator for large launches: sin/cos of the Box-Muller angle from TWO 4096-entry tables and one complex product
+// (fm::sincos_two_level: 4 fp64 instructions per pair instead of 12; the kernel's clock follows its fp64 count).  With the
+// logarithm's table that is 144 KiB of the CU's 160 KiB of LDS, so ONE workgroup of 16 waves owns a CU -- the 4 waves per SIMD
+// of k_gbm_paths<., ., 2> -- and the kernel is persistent: grid = number of CUs, the tables are staged once behind the only
+// barrier, and from there every WAVE is on its own.  A wave takes tiles of 128 columns (two adjacent paths per lane: 1 KiB
+// per row and store, as the narrow kernel's waves), the first by its position and every later one from a ticket counter,
+// runs all steps of the tile and stores every column of ld (a multiple of 256): the padded columns hold the stream's next
+// paths.  (Tickets, not a fixed stride: waves do not all run at the same speed, and the rBergomi generator's record has a
+// fixed stride 10 % slower.)  Nothing a tile writes
+// depends on which wave ran it: the payoff sums of a tile are reduced inside the wave and land in partials[tile].
+// A plain grid of such workgroups would leave the CU idle while each of them stages its tables and while its last wave
+// drains (nothing else is resident): about 19 times per 10M-path launch.
+struct WideTables {
+    double2 log[fm::LOG_TAB_ENTRIES];       // {1/c_i, -2 ln c_i}; the second column times vol^2 in modes 2 and 3
+    double2 coarse[fm::SINCOS2_ENTRIES];    // {cos, sin}(2 pi i / 4096)
+    double2 fine[fm::SINCOS2_ENTRIES];      // {cos, sin}(2 pi (j + 1/2) / 2^24)
+};
+constexpr int WIDE_WAVES = 16, WIDE_TILE = 128;
+static_assert(fm::SINCOS2_ENTRIES == SINCOS2_ENTRIES, "host/sincos2.cpp builds what fm::sincos_two_level indexes");
+static_assert(sizeof(WideTables) == 147456, "144 KiB: one workgroup per CU");
+
+template <bool PAYOFF, int MODE>
+__global__ __launch_bounds__(64 * WIDE_WAVES) void k_gbm_paths_wide(GbmArgs a) {
+    constexpr bool SMALL = MODE >= 1;
+    typedef double v2d __attribute__((ext_vector_type(2)));
+    __shared__ WideTables tabs;
+    __shared__ unsigned long long stamp0[WIDE_WAVES][2];  // a stamping tile's start stamps wait here, not in registers
+    {
+        const double scale = a.vol * a.vol;
+        for (int i = threadIdx.x; i < fm::LOG_TAB_ENTRIES; i += 64 * WIDE_WAVES) {
+            double2 e = a.log_tab[i];
+            if (MODE >= 2) e.y *= scale;   // (as fm::load_tables_scaled)
+            tabs.log[i] = e;
+        }
+        double2* sc = reinterpret_cast<double2*>(&tabs) + fm::LOG_TAB_ENTRIES;  // coarse and fine, back to back in both places
+        for (int i = threadIdx.x; i < 2 * fm::SINCOS2_ENTRIES; i += 64 * WIDE_WAVES) sc[i] = a.sincos2[i];
+    }
+    __syncthreads();
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned lane_bytes = lane * 16u;
+    // What only the start and the end of a tile need (matrix base, stream position, payoff, stamps, the counter) is re-read
+    // from the kernel-argument segment there -- scalar loads of cached lines, twice per 128 x (n_steps + 1) values -- instead
+    // of holding scalar registers across the steps: the Horner constants need those, and the kernel has none to spare (with
+    // everything carried, 23 of them went to spilled lanes).  The empty asm keeps the loads where they are written.
+    typedef const __attribute__((address_space(4))) GbmArgs* TileArgs;
+    auto tile_args = [] {
+        TileArgs p = (TileArgs)__builtin_amdgcn_kernarg_segment_ptr();  // (GbmArgs is the kernel's only argument)
+        asm volatile("" : "+s"(p));
+        return p;
+    };
+    auto stamping = [](TileArgs t, unsigned tile) {  // wave-uniform
+        return t->clk != nullptr && (tile & ((1u << t->clk_shift) - 1u)) == t->clk_first && (tile >> t->clk_shift) < (unsigned)GBM_CLK_SLOTS;
+    };
+    unsigned tile = blockIdx.x * WIDE_WAVES + wave;  // the first tile by position, every later one from the counter
+    while (tile < tile_args()->n_tiles) {
+        const TileArgs t = tile_args();
+        if (stamping(t, tile) && lane == 0) {
+            stamp0[wave][0] = __builtin_amdgcn_s_memtime();
+            stamp0[wave][1] = __builtin_amdgcn_s_memrealtime();
+        }
+        const int64_t col = (int64_t)tile * WIDE_TILE + lane * 2;  // first column of this lane
+        double S[2] = {t->S0, t->S0};
+        double* row = t->out + (int64_t)tile * WIDE_TILE;
+        // (the store of k_gbm_paths<., ., 2>, with its own `s_nop 1`: see there)
+        auto store_row = [&](double* r) {
+            const v2d v = {S[0], S[1]};
+            asm volatile("global_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(v), "s"(r) : "memory");
+        };
+        store_row(row);
+        PhiloxLane lane_rng[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) lane_rng[p] = philox_lane_setup(t->path_begin + (uint64_t)(col + p), STREAM_PRICE, a.k1);
+        auto step = [&](const double (&e)[2]) {
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+                S[p] = MODE == 3 ? fm::scaled_exp_small6(S[p], e[p]) : SMALL ? fm::scaled_exp_small(S[p], e[p]) : fm::scaled_exp(S[p], e[p]);
+            row += a.ld;
+            store_row(row);
+        };
+        auto pair_exponents = [&](uint32_t wa, uint32_t wb, double& e0, double& e1) {  // drift + vol*z of two steps
+            if (MODE >= 2) fm::box_muller_pair_affine_scaled2(wa, wb, tabs.log, tabs.coarse, tabs.fine, a.ls, a.drift, e0, e1);
+            else fm::box_muller_pair_affine2(wa, wb, tabs.log, tabs.coarse, tabs.fine, a.vol, a.drift, e0, e1);
+        };
+        const int n_blocks = a.n_steps >> 2;
+#pragma unroll 1
+        for (int b = 0; b < n_blocks; ++b) {
+            Philox4 w[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) w[p] = philox4x32_10_lane(lane_rng[p], (uint32_t)b, a.k0, a.k1);
+            double e0[2], e1[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) pair_exponents(w[p].w0, w[p].w1, e0[p], e1[p]);
+            step(e0);
+            step(e1);
+#pragma unroll
+            for (int p = 0; p < 2; ++p) pair_exponents(w[p].w2, w[p].w3, e0[p], e1[p]);
+            step(e0);
+            step(e1);
+        }
+        const int rest = tile_args()->n_steps & 3;  // (re-read: three branch conditions less to carry through the steps)
+        if (rest) {  // wave-uniform
+            Philox4 w[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) w[p] = philox4x32_10_lane(lane_rng[p], (uint32_t)n_blocks, a.k0, a.k1);
+            double e0[2], e1[2];
+#pragma unroll
+            for (int p = 0; p < 2; ++p) pair_exponents(w[p].w0, w[p].w1, e0[p], e1[p]);
+            step(e0);
+            if (rest >= 2) step(e1);
+            if (rest == 3) {
+#pragma unroll
+                for (int p = 0; p < 2; ++p) pair_exponents(w[p].w2, w[p].w3, e0[p], e1[p]);
+                step(e0);
+            }
+        }
+        const TileArgs e = tile_args();
+        if (stamping(e, tile) && lane == 0) {
+            const unsigned long long c1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+            unsigned long long* dst = e->clk + 2 * (tile >> e->clk_shift);
+            dst[0] = c1 - stamp0[wave][0];
+            dst[1] = r1 - stamp0[wave][1];
+        }
+        if (PAYOFF) {
+            double v[2] = {0.0, 0.0};
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const double pay = col + p < e->n_paths ? payoff_of(e->is_call != 0, S[p], e->K) : 0.0;
+                v[0] += pay;
+                v[1] += pay * pay;
+            }
+            wave_sum_all<2>(v);  // (a fixed butterfly: the tile's sums are the same bits whichever wave ran it)
+            if (lane == 0) {
+                e->partials[2 * (int64_t)tile] = v[0];
+                e->partials[2 * (int64_t)tile + 1] = v[1];
+            }
+        }
+        // one lane's atomic add, broadcast (a wave waits for it once per tile, behind its last stores; the SIMD's other
+        // three waves are in the middle of their tiles meanwhile)
+        unsigned drawn = 0;
+        if (lane == 0) drawn = atomicAdd(e->ticket, 1u);
+        tile = __builtin_amdgcn_readfirstlane(drawn) + gridDim.x * WIDE_WAVES;
+    }
+}
+
 // Terminal payoff over a stored matrix: reads the last row only (8 B per path).
 __global__ __launch_bounds__(256) void k_payoff_sums(const double* last_row, int64_t n_paths, double K,
                                                      int is_call, double* partials) {
@@ -279,6 +428,25 @@ static void launch_gbm_mode(mcg_ctx* ctx, const GbmArgs& a, int mode, unsigned n
     else hipLaunchKernelGGL((k_gbm_paths<PAYOFF, 0, PPL>), grid, block, 0, ctx->stream, a);
 }
 
+template <bool PAYOFF>
+static void launch_gbm_wide_mode(mcg_ctx* ctx, const GbmArgs& a, int mode) {
+    // (a launch with fewer tiles than the device has waves: only the workgroups whose first tile exists)
+    const unsigned n_groups = std::min<unsigned>((unsigned)ctx->n_cus, (a.n_tiles + WIDE_WAVES - 1) / WIDE_WAVES);
+    const dim3 grid(n_groups), block(64 * WIDE_WAVES);
+    if (mode == 3) hipLaunchKernelGGL((k_gbm_paths_wide<PAYOFF, 3>), grid, block, 0, ctx->stream, a);
+    else if (mode == 2) hipLaunchKernelGGL((k_gbm_paths_wide<PAYOFF, 2>), grid, block, 0, ctx->stream, a);
+    else if (mode == 1) hipLaunchKernelGGL((k_gbm_paths_wide<PAYOFF, 1>), grid, block, 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_gbm_paths_wide<PAYOFF, 0>), grid, block, 0, ctx->stream, a);
+}
+
+// The wide kernel (k_gbm_paths_wide) from GBM_WIDE_MIN_PATHS paths on: the smallest of the measured sizes from which it is
+// not slower than k_gbm_paths (DESIGN.md section 5 has the times); mcg_debug_gbm_route overrides.
+constexpr int64_t GBM_WIDE_MIN_PATHS = 2000000;
+static bool gbm_takes_wide(const mcg_ctx* ctx, int64_t n_paths) {
+    if (ctx->gbm_route == 1 || ctx->gbm_route == 2) return ctx->gbm_route == 2;
+    return n_paths >= GBM_WIDE_MIN_PATHS;
+}
+
 // paths per lane: 2 once every CU has several workgroups of 512 paths to work on
 static int gbm_paths_per_lane(const mcg_ctx* ctx, int64_t n_paths) {
     static const int forced = study_switch("MCG_GBM_PPL", 0);
@@ -288,10 +456,12 @@ static int gbm_paths_per_lane(const mcg_ctx* ctx, int64_t n_paths) {
 
 int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double sigma, double dt,
                bool want_payoff, double K, int is_call) {
+    const bool wide = gbm_takes_wide(ctx, P->n_paths);
     const int ppl = gbm_paths_per_lane(ctx, P->n_paths);
-    const int64_t n_blocks = (P->n_paths + 256 * ppl - 1) / (256 * ppl);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
     if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    // the units that leave partial sums and stamp the clock: workgroups of the narrow kernel, tiles of the wide one
+    const int64_t n_blocks = wide ? P->ld / WIDE_TILE : (P->n_paths + 256 * ppl - 1) / (256 * ppl);
+    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
     if (want_payoff) {
         int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
         if (rc) return rc;
@@ -311,8 +481,11 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
     a.is_call = is_call;
     a.partials = ctx->partials;
     a.log_tab = (const double2*)ctx->log_tab;
-    // shader-clock stamps (armed launches only, mcg_generator_clock_arm): one workgroup in every 2^shift, the smallest shift
-    // that needs at most GBM_CLK_SLOTS slots
+    a.sincos2 = (const double2*)ctx->sincos2_tab;
+    a.ticket = reinterpret_cast<unsigned*>(ctx->scalars + SC_GBM_TICKET);
+    a.n_tiles = wide ? (unsigned)n_blocks : 0u;
+    // shader-clock stamps (armed launches only, mcg_generator_clock_arm): one workgroup (tile) in every 2^shift, the smallest
+    // shift that needs at most GBM_CLK_SLOTS slots
     a.clk = nullptr;
     a.clk_first = 0;
     a.clk_shift = 0;
@@ -326,6 +499,8 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
         ctx->clk_slots_used = (int)(((n_blocks - 1 - a.clk_first) >> shift) + 1);
         MCG_HIP(hipMemsetAsync(ctx->clk_stamps, 0, sizeof(unsigned long long) * 2 * GBM_CLK_SLOTS, ctx->stream));
     }
+    if (wide) MCG_HIP(hipMemsetAsync(a.ticket, 0, sizeof(unsigned), ctx->stream));
+    ctx->gbm_last_route = wide ? 2 : 1;
     {
         TimedLaunch t(ctx, MCG_K_GBM);
         const bool small = std::fabs(a.drift) + std::fabs(a.vol) * fm::MAX_ABS_NORMAL <= fm::SMALL_EXP_BOUND;
@@ -333,7 +508,10 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
         // vol^2 (-2 ln u) must stay a normal positive double for modes 2 and 3
         const int mode = !small ? 0 : !(a.vol > 1e-100) ? 1 : reach <= fm::SMALL6_EXP_BOUND ? 3 : 2;
         a.ls = fm::make_log_scale(a.vol * a.vol);
-        if (want_payoff) {
+        if (wide) {
+            if (want_payoff) launch_gbm_wide_mode<true>(ctx, a, mode);
+            else launch_gbm_wide_mode<false>(ctx, a, mode);
+        } else if (want_payoff) {
             if (ppl == 2) launch_gbm_mode<true, 2>(ctx, a, mode, (unsigned)n_blocks);
             else launch_gbm_mode<true, 1>(ctx, a, mode, (unsigned)n_blocks);
         } else {

@@ -265,6 +265,12 @@ static int init_impl(mcg_ctx** out, int device, bool adopt, void* external_strea
         mcg_finalize(ctx);
         return fail(MCG_ERR_OOM, "table upload failed");
     }
+    constexpr size_t sincos2_bytes = sizeof(double) * 4 * SINCOS2_ENTRIES;
+    if (hipMalloc((void**)&ctx->sincos2_tab, sincos2_bytes) != hipSuccess ||
+        hipMemcpy(ctx->sincos2_tab, host_sincos2_tables(), sincos2_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        mcg_finalize(ctx);
+        return fail(MCG_ERR_OOM, "table upload failed");
+    }
     *out = ctx;
     return MCG_OK;
 }
@@ -304,6 +310,7 @@ int mcg_finalize(mcg_ctx* ctx) {
     if (ctx->lsm_v) (void)hipFree(ctx->lsm_v);
     if (ctx->lsm_dv) (void)hipFree(ctx->lsm_dv);
     if (ctx->log_tab) (void)hipFree(ctx->log_tab);
+    if (ctx->sincos2_tab) (void)hipFree(ctx->sincos2_tab);
     if (ctx->batch_fork) (void)hipEventDestroy(ctx->batch_fork);
     if (ctx->batch_join) (void)hipEventDestroy(ctx->batch_join);
     if (ctx->batch_aux) (void)hipStreamDestroy(ctx->batch_aux);
@@ -1140,6 +1147,14 @@ int mcg_debug_lsm_date_fault(mcg_ctx* ctx, int mode, int date, int workgroup, in
     ctx->lsm_date_hook[2] = workgroup;
     ctx->lsm_date_hook[3] = delay;
     ctx->lsm_date_spin_limit = spin_limit;
+    return MCG_OK;
+}
+
+int mcg_debug_gbm_route(mcg_ctx* ctx, int route, int* last_route) {
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    if (route < -1 || route > 2) return fail(MCG_ERR_INVALID, "route must be 0 (auto), 1 (narrow), 2 (wide) or -1 (unchanged)");
+    if (route >= 0) ctx->gbm_route = route;
+    if (last_route) *last_route = ctx->gbm_last_route;
     return MCG_OK;
 }
 

@@ -108,6 +108,9 @@ struct mcg_ctx {
     int clk_slots_used = 0;
     bool clk_armed = false;                    // mcg_generator_clock_arm: only armed launches stamp (and pay the memset ahead of them)
     double* log_tab = nullptr;   // device copy of fm::LOG_TAB_HOST + fm::SINCOS_TAB_HOST + fm::EXP2_TAB_HOST (34 KiB), staged to LDS
+    double* sincos2_tab = nullptr;  // device copy of host_sincos2_tables(): coarse, then fine (128 KiB; fm::sincos_two_level)
+    int gbm_route = 0;           // mcg_debug_gbm_route: 0 = launch_gbm chooses, 1 = k_gbm_paths, 2 = k_gbm_paths_wide
+    int gbm_last_route = 0;      //   what the last GBM launch took (1 or 2; 0: none yet)
 
     // collective
     mcg_allreduce_fn allreduce = nullptr;
@@ -145,6 +148,7 @@ struct mcg_paths {
 
 namespace mcg {
 
+constexpr int SINCOS2_ENTRIES = 4096;  // entries {cos, sin} of each of the two tables of fm::sincos_two_level
 constexpr int GBM_CLK_SLOTS = 64;     // stamping workgroups of a GBM generator launch (mcg_generator_clock)
 constexpr int SCALARS_DOUBLES = 256;
 // layout of ctx->scalars (doubles)
@@ -154,6 +158,7 @@ constexpr int SC_COEF = 40;    // [40..60) the LSM coefficient block of the curr
 constexpr int SC_FINAL = 64;   // [64..67) LSM final sums
 constexpr int SC_BARRIER = 72; // [72] 32-bit timeout flag of k_lsm_coop's hand-shake
 constexpr int SC_TICKET = 80;  // [80] 64-bit share ticket of the persistent rBergomi generator (zeroed before each launch)
+constexpr int SC_GBM_TICKET = 81;  // [81] 32-bit tile ticket of the wide GBM generator (k_gbm_paths_wide; zeroed before each launch)
 constexpr int SC_LSM_TICKET = 160; // [160..225) 129 32-bit "workgroups done" tickets of the per-date LSM kernel (k_lsm_date)
 constexpr int SC_LSM_MSG = 96;     // [96..144) per-date LSM message: the 3p+2 <= 47 moments the next launch solves (the all-reduced part)
 constexpr int SC_LSM_STATE = 144;  // [144..147) per-date LSM state: date, phase, centre (kernels_lsm.hip: LSM_ST_*)
@@ -296,6 +301,8 @@ int run_asymptotic(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
                    double sigma, double dividend, double* price);
 
 // host-side math (host/volterra.cpp, host/estimators.cpp, host/asymptotic.cpp)
+// host/sincos2.cpp: 2 * SINCOS2_ENTRIES doubles of the coarse table, then as many of the fine one (built on first use)
+const double* host_sincos2_tables();
 void host_asymptotic_tables(int n_cols, double r, double K, double maturity, double dt, int is_call, double sigma,
                             double dividend, std::vector<double>& bnd, std::vector<double>& disc);
 int host_estimate_params(const double* hist, size_t n, double out5[5]);

@@ -569,6 +569,13 @@ class PathEngine:
                                      y.ctypes.data_as(C.POINTER(C.c_double)), len(x)))
         return y
 
+    def debug_gbm_route(self, route: int = -1) -> int:
+        """Test hook (mcg_debug_gbm_route): 0 = the generators choose their kernel by size, 1 = the narrow kernel, 2 = the
+        wide one, -1 = unchanged; returns what the last GBM launch took (1 or 2; 0: none yet)."""
+        last = C.c_int()
+        check(self._L.mcg_debug_gbm_route(self._ctx, int(route), C.byref(last)))
+        return last.value
+
     # -- measurement ----------------------------------------------------------------------------
     def timing_enable(self, on: bool = True) -> None:
         check(self._L.mcg_timing_enable(self._ctx, int(on)))
@@ -900,3 +907,12 @@ def rbergomi_spectrum(H: float, eta: float, dt: float, n_steps: int):
                                   comp.ctypes.data_as(C.POINTER(C.c_double)), C.byref(mz)))
     assert mz.value == M
     return amp, comp
+
+
+def sincos2_tables():
+    """Test hook, host-only (mcg_debug_sincos2_tables): (coarse[4096][2], fine[4096][2]), the {cos, sin} tables of the wide
+    GBM generator's two-level sin/cos."""
+    L = N.load_library()
+    coarse, fine = np.empty((4096, 2)), np.empty((4096, 2))
+    check(L.mcg_debug_sincos2_tables(coarse.ctypes.data_as(C.POINTER(C.c_double)), fine.ctypes.data_as(C.POINTER(C.c_double))))
+    return coarse, fine

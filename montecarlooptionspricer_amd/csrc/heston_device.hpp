@@ -1,8 +1,8 @@
-// The Heston path generator's skeleton for gfx950, shared by its variance schemes (kernels_heston.hip: full-truncation
-// log-Euler; kernels_heston_qe.hip: Andersen's QE; kernels_bates.hip: either with compound-Poisson jumps): two adjacent
-// paths per lane with S and v in registers, fm::Tables in LDS, two Philox streams per path (price driver and volatility
-// driver, philox.hpp), step-major 16-byte nontemporal stores of the price row and -- optionally -- of the variance row, the
-// terminal payoff partials of the fused form, and the launcher.
+// The Heston path kernel for gfx950, shared by its variance schemes (kernels_heston.hip: full-truncation log-Euler;
+// kernels_heston_qe.hip: Andersen's QE; kernels_bates.hip: either with compound-Poisson jumps), on the generators' skeleton
+// of paths_device.hpp (row store, block walk, payoff partials): two adjacent paths per lane with S and v in registers, two
+// Philox streams per path (price driver and volatility driver, philox.hpp), the price row and -- optionally -- the variance
+// row stored per step, and the launcher.
 //
 // A scheme is a struct the kernel holds one object of (heston_schemes.hpp: the two variance schemes; kernels_bates.hip: either
 // of them with jumps):
@@ -16,6 +16,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "mcg_internal.hpp"
+#include "paths_device.hpp"
 
 namespace mcg {
 
@@ -51,7 +52,6 @@ __device__ __forceinline__ double sqrt_nonneg(double x) {
 template <class Scheme, bool PAYOFF, bool VAR>
 __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme::Consts> a) {
     constexpr int PPL = HESTON_PPL;
-    typedef double v2d __attribute__((ext_vector_type(2)));
     __shared__ fm::Tables tabs;
     fm::load_tables(&tabs, a.tabs);
     const fm::Tables* tab = &tabs;
@@ -66,22 +66,12 @@ __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme
         v[p] = a.v0;
     }
     if (in_row) {
-        // The generator's store pattern (kernels_gbm.hip): a wave-uniform row pointer that advances by ld on the scalar unit
-        // plus a lane offset that never changes.  The `s_nop 1` belongs to the store: a store of more than 64 bits reads its
-        // data registers after issue, and the next step's FMA overwrites them right behind it (tools/check_asm_hazards.py).
+        // a wave-uniform row pointer that advances by ld on the scalar unit, and a lane offset that never changes
         double* row = a.out + (int64_t)blockIdx.x * (256 * PPL);
         double* vrow = VAR ? a.var + (int64_t)blockIdx.x * (256 * PPL) : nullptr;
         const unsigned lane_bytes = threadIdx.x * (8u * PPL);
-        // The `s_nop 4` in front belongs to it too: these kernels hold more scalars than there are registers (eight model
-        // constants beside the polynomials'), so hipcc keeps some in spare vector lanes, and where the row pointer is one of
-        // them its v_readlane lands right before the store -- a VMEM instruction must not read an SGPR as its address within 5
-        // wait states of a VALU write (the same checker found it).  Seven idle cycles per row against ~10^3 of arithmetic.
-        auto store_pair = [&](double* r, const double (&x)[PPL]) {
-            const v2d d = {x[0], x[1]};
-            asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(d), "s"(r) : "memory");
-        };
-        store_pair(row, S);
-        if (VAR) store_pair(vrow, v);
+        store_pair16(row, lane_bytes, S[0], S[1]);
+        if (VAR) store_pair16(vrow, lane_bytes, v[0], v[1]);
         PhiloxLane rng_s[PPL], rng_v[PPL];
 #pragma unroll
         for (int p = 0; p < PPL; ++p) {
@@ -91,83 +81,44 @@ __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme
         }
         Scheme scheme;
         uint32_t block = 0;  // the Philox block of the current four steps
-        // one step of both paths, elem = step & 3, and its rows
-        auto step = [&](const double (&z1)[PPL], const double (&z2)[PPL], const int elem) {
-            scheme.step(a, i, block, elem, tab, z1, z2, S, v);
-            row += a.ld;
-            store_pair(row, S);
-            if (VAR) {
-                vrow += a.ld;
-                store_pair(vrow, v);
-            }
-        };
-        // One Philox block per stream feeds two Box-Muller pairs = four steps.  The main loop takes whole blocks; the
-        // tail runs pair by pair over the last <= 3 steps.
-        auto pairs = [&](const Philox4 (&ws)[PPL], const Philox4 (&wv)[PPL], bool second, double (&z1a)[PPL], double (&z1b)[PPL],
-                         double (&z2a)[PPL], double (&z2b)[PPL]) {
-#pragma unroll
-            for (int p = 0; p < PPL; ++p) {
-                fm::box_muller_pair(second ? ws[p].w2 : ws[p].w0, second ? ws[p].w3 : ws[p].w1, tab, z1a[p], z1b[p]);
-                fm::box_muller_pair(second ? wv[p].w2 : wv[p].w0, second ? wv[p].w3 : wv[p].w1, tab, z2a[p], z2b[p]);
-            }
-        };
-        auto draw = [&](Philox4 (&ws)[PPL], Philox4 (&wv)[PPL]) {
-#pragma unroll
-            for (int p = 0; p < PPL; ++p) {
-                ws[p] = philox4x32_10_lane(rng_s[p], block, a.k0, a.k1);
-                wv[p] = philox4x32_10_lane(rng_v[p], block, a.k0, a.k1);
-            }
-            scheme.new_block(a, i, block, tab);
-        };
-        const int n_blocks = a.n_steps >> 2;
         Philox4 ws[PPL], wv[PPL];
-        double z1a[PPL], z1b[PPL], z2a[PPL], z2b[PPL];
-#pragma unroll 1
-        for (; block < (uint32_t)n_blocks; ++block) {
-            draw(ws, wv);
-            pairs(ws, wv, false, z1a, z1b, z2a, z2b);
-            step(z1a, z2a, 0);
-            step(z1b, z2b, 1);
-            pairs(ws, wv, true, z1a, z1b, z2a, z2b);
-            step(z1a, z2a, 2);
-            step(z1b, z2b, 3);
-        }
-        const int rest = a.n_steps & 3;
-        if (rest) {  // wave-uniform
-            draw(ws, wv);
-            pairs(ws, wv, false, z1a, z1b, z2a, z2b);
-            step(z1a, z2a, 0);
-            if (rest >= 2) step(z1b, z2b, 1);
-            if (rest == 3) {
-                pairs(ws, wv, true, z1a, z1b, z2a, z2b);
-                step(z1a, z2a, 2);
-            }
-        }
-    }
-    if (PAYOFF) {
-        __shared__ double red[2 * 4];
-        double acc[2] = {0.0, 0.0};
+        double z1a[PPL], z1b[PPL], z2a[PPL], z2b[PPL];  // z1: price driver, z2: volatility driver; a, b: the steps of a pair
+        auto pairs = [&](const bool second) {
+            normal_pairs(ws, second, tab, z1a, z1b);
+            normal_pairs(wv, second, tab, z2a, z2b);
+        };
+        walk_blocks(
+            a.n_steps, block,
+            [&](auto) {
 #pragma unroll
-        for (int p = 0; p < PPL; ++p) {
-            const double pay = (in_row && i + p < a.n_paths) ? payoff_of(a.is_call != 0, S[p], a.K) : 0.0;
-            acc[0] += pay;
-            acc[1] += pay * pay;
-        }
-        block_sum<2, 4>(acc, red);
-        if (threadIdx.x == 0) {
-            a.partials[2 * (int64_t)blockIdx.x] = acc[0];
-            a.partials[2 * (int64_t)blockIdx.x + 1] = acc[1];
-        }
+                for (int p = 0; p < PPL; ++p) {
+                    ws[p] = philox4x32_10_lane(rng_s[p], block, a.k0, a.k1);
+                    wv[p] = philox4x32_10_lane(rng_v[p], block, a.k0, a.k1);
+                }
+                scheme.new_block(a, i, block, tab);
+                pairs(false);
+            },
+            [&] { pairs(true); },
+            [&](auto elem) {  // one step of both paths, and its rows
+                scheme.step(a, i, block, elem, tab, elem & 1 ? z1b : z1a, elem & 1 ? z2b : z2a, S, v);
+                row += a.ld;
+                store_pair16(row, lane_bytes, S[0], S[1]);
+                if (VAR) {
+                    vrow += a.ld;
+                    store_pair16(vrow, lane_bytes, v[0], v[1]);
+                }
+            },
+            [] {});
     }
+    if (PAYOFF) payoff_partials(in_row, i, a.n_paths, S, a.K, a.is_call, a.partials);
 }
 
 // One launch of k_heston_paths<Scheme, ...> over P (and V: the variance matrix, or null) from the scheme's constants c.
 template <class Scheme>
 int launch_heston_scheme(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed, double S0, double v0,
                          const typename Scheme::Consts& c, bool want_payoff, double K, int is_call) {
-    const int64_t n_blocks = (P->n_paths + 511) / 512;
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    const int64_t n_blocks = launch_blocks(P, HESTON_PPL);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     if (V && (V->ld != P->ld || V->n_steps != P->n_steps))
         return fail(MCG_ERR_INVALID, "the variance matrix must have the shape of the price matrix");
     if (want_payoff) {

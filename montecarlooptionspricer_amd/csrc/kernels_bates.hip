@@ -1,6 +1,6 @@
 // Bates and Merton paths for gfx950, as stated in include/mcgpu.h (mcg_paths_bates*): compound-Poisson log-normal jumps
 // composed onto either variance scheme of heston_schemes.hpp as one more step rule, and the launcher that derives its
-// constants.  The kernel around it -- draws, rows, stores, payoff partials -- is heston_device.hpp's.
+// constants.  The kernel around it -- draws and rows -- is heston_device.hpp's, on the skeleton of paths_device.hpp.
 //
 // The jump of a step is independent of its diffusion, so the rule only adds J = comp + N mu_J + sigma_J sqrt(N) z3 to the
 // exponent the base scheme hands to its one exponential; the variance never sees it.  Jumps are rare (lambda dt = 0.004 on

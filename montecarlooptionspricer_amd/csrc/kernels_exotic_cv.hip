@@ -1,8 +1,8 @@
 // Control variates for the exotics book (include/mcgpu.h: mcg_price_exotics_cv, mcg_gbm_twin_stats).
 //
 // k_gbm_twin_stats   the five statistics of a GBM path built in registers from Philox stream 0 of (seed, path id): Philox,
-//                    Box-Muller and the step X += fma(a, z, m) as the generators run them (two adjacent paths per lane,
-//                    fm::Tables in LDS, one Philox block per four steps), one exponential per monitored step for A and three
+//                    Box-Muller and the step X += fma(a, z, m) as the generators run them (paths_device.hpp: two adjacent
+//                    paths per lane, fm::Tables in LDS, the walk over Philox blocks), one exponential per monitored step for A and three
 //                    per path at the end (G, min, max; S_T is the last step's).  40 B per path written, nothing read:
 //                    issue-bound on the VALU like the GBM generator's loop.
 // k_exotic_book_cv   k_exotic_book with nine sums a contract instead of two: {Y, Y^2, d_a, d_a^2, Y d_a, d_b, d_b^2, Y d_b,
@@ -20,6 +20,7 @@
 #include "exotic_device.hpp"
 #include "fastmath.hpp"
 #include "mcg_internal.hpp"
+#include "paths_device.hpp"
 
 namespace mcg {
 
@@ -80,37 +81,17 @@ __global__ __launch_bounds__(256) void k_gbm_twin_stats(TwinArgs t) {
             }
         }
     };
-    auto pairs = [&](const Philox4 (&w)[PPL], bool second, double (&za)[PPL], double (&zb)[PPL]) {
-#pragma unroll
-        for (int p = 0; p < PPL; ++p)
-            fm::box_muller_pair(second ? w[p].w2 : w[p].w0, second ? w[p].w3 : w[p].w1, tab, za[p], zb[p]);
-    };
-    const int n_blocks = t.n_steps >> 2, rest = t.n_steps & 3;
     Philox4 w[PPL];
     double za[PPL], zb[PPL];
     uint32_t block = 0;
-#pragma unroll 1
-    for (; block < (uint32_t)n_blocks; ++block) {
+    walk_blocks(
+        t.n_steps, block,
+        [&](auto) {
 #pragma unroll
-        for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, t.k0, t.k1);
-        pairs(w, false, za, zb);
-        step(za);
-        step(zb);
-        pairs(w, true, za, zb);
-        step(za);
-        step(zb);
-    }
-    if (rest) {
-#pragma unroll
-        for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, t.k0, t.k1);
-        pairs(w, false, za, zb);
-        step(za);
-        if (rest >= 2) step(zb);
-        if (rest == 3) {
-            pairs(w, true, za, zb);
-            step(za);
-        }
-    }
+            for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, t.k0, t.k1);
+            normal_pairs(w, false, tab, za, zb);
+        },
+        [&] { normal_pairs(w, true, tab, za, zb); }, [&](auto k) { step(k & 1 ? zb : za); }, [] {});
     const double nd = (double)(t.n_steps - t.first_row + 1);
     double g[PPL], lo[PPL], hi[PPL];
     fm::exp_full2(sumX[0] / nd, sumX[1] / nd, g[0], g[1]);
@@ -210,8 +191,8 @@ __global__ __launch_bounds__(256) void k_exotic_cv_reduce(const double* partials
 }
 
 static int launch_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* tw, int n_steps, int first_row, int64_t n_paths, double* d_stats) {
-    const int64_t n_blocks = (n_paths + 256 * CV_PPL - 1) / (256 * CV_PPL);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
+    const int64_t n_blocks = launch_blocks(n_paths, CV_PPL);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     TwinArgs t;
     t.out5 = d_stats;
     t.n_paths = n_paths;

@@ -14,6 +14,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "mcg_internal.hpp"
+#include "paths_device.hpp"
 
 #ifndef MCG_GBM_TABLES
 #define MCG_GBM_TABLES 0
@@ -171,21 +172,7 @@ __global__ __launch_bounds__(256) void k_gbm_paths(GbmArgs a) {
         dst[0] = c1 - stamp0[0];
         dst[1] = r1 - stamp0[1];
     }
-    if (PAYOFF) {
-        __shared__ double red[2 * 4];
-        double v[2] = {0.0, 0.0};
-#pragma unroll
-        for (int p = 0; p < PPL; ++p) {
-            const double pay = (in_row && i + p < a.n_paths) ? payoff_of(a.is_call != 0, S[p], a.K) : 0.0;
-            v[0] += pay;
-            v[1] += pay * pay;
-        }
-        block_sum<2, 4>(v, red);
-        if (threadIdx.x == 0) {
-            a.partials[2 * (int64_t)blockIdx.x] = v[0];
-            a.partials[2 * (int64_t)blockIdx.x + 1] = v[1];
-        }
-    }
+    if (PAYOFF) payoff_partials(in_row, i, a.n_paths, S, a.K, a.is_call, a.partials);
 }
 
 // The generator for large launches: sin/cos of the Box-Muller angle from TWO 4096-entry tables and one complex product

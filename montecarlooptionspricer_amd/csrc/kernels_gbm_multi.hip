@@ -1,9 +1,11 @@
 // Correlated multi-asset GBM paths for gfx950 and the reduction of d asset matrices to one (include/mcgpu.h:
 // mcg_paths_gbm_multi, mcg_paths_combine).
 //
-// k_gbm_multi<D, STORE_ASSETS, STORE_COMBINED> follows the skeleton of heston_device.hpp: two adjacent paths per lane with
-// the D prices of each in registers, fm::Tables in LDS, one Philox stream per driver (stream 0, then 16..22), a wave-uniform
-// row pointer plus a constant lane offset, and the 16-byte nontemporal store with its `s_nop` guards.  The model's constants
+// k_gbm_multi<D, STORE_ASSETS, STORE_COMBINED> has the generators' skeleton of paths_device.hpp and takes its row store from
+// there: two adjacent paths per lane with the D prices of each in registers, fm::Tables in LDS, one Philox stream per driver
+// (stream 0, then 16..22), a wave-uniform row offset plus a constant lane offset.  It walks its blocks itself: draw() makes
+// all four steps' exponents at once, and through walk_blocks hipcc allots D = 5 with the combined row alone 168 vector
+// registers for 169.  The model's constants
 // (drifts, the lower triangle A = diag(sigma sqrt(dt)) L, the weights) sit in LDS behind the tables: 52 doubles, read with
 // one broadcast ds_read each, so that no D costs scalar registers for them.  The per-(path, driver) Philox state is not held:
 // three words per path stay in registers, and one 32x32 -> 64 product (two multiply instructions) per path, driver and block
@@ -16,6 +18,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "mcg_internal.hpp"
+#include "paths_device.hpp"
 
 namespace mcg {
 
@@ -72,16 +75,6 @@ __device__ __forceinline__ double combine_assets(const double (&S)[NMAX], const 
         }
     }
     return acc;
-}
-
-// The store of heston_device.hpp's store_pair: 16 bytes per lane at (wave-uniform row pointer) + (constant lane offset).
-// `s_nop 1` behind it: a store of more than 64 bits reads its data registers after issue, and the next step overwrites them.
-// `s_nop 4` in front: where the row pointer comes out of a spare vector lane its v_readlane lands right before the store, and
-// a VMEM instruction must not read an SGPR as its address within 5 wait states of a VALU write (tools/check_asm_hazards.py).
-__device__ __forceinline__ void store_pair16(double* r, unsigned lane_bytes, double x0, double x1) {
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    const v2d d = {x0, x1};
-    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(d), "s"(r) : "memory");
 }
 
 template <int D, bool STORE_ASSETS, bool STORE_COMBINED>
@@ -246,9 +239,8 @@ int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, in
                      double r, const double* q, const double* sigma, const double* L, double dt, int kind,
                      const double* weights) {
     const mcg_paths* P = assets ? assets[0] : comb;
-    const int64_t n_blocks = (P->n_paths + 256 * MULTI_PPL - 1) / (256 * MULTI_PPL);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    const int64_t n_blocks = launch_blocks(P, MULTI_PPL);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     MultiArgs a{};
     MultiConsts c{};
     const double sq = std::sqrt(dt);
@@ -297,9 +289,8 @@ int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, in
 // One launch of k_paths_combine: out = combination of n_assets matrices of out's shape; weights: never null here.
 int launch_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
                          mcg_paths* out) {
-    const int64_t n_blocks = (out->n_paths + 256 * MULTI_PPL - 1) / (256 * MULTI_PPL);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    if ((out->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    const int64_t n_blocks = launch_blocks(out, MULTI_PPL);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     CombineArgs a{};
     for (int d = 0; d < n_assets; ++d) {
         if (assets[d]->ld != out->ld) return fail(MCG_ERR_INVALID, "the matrices must have one row stride");

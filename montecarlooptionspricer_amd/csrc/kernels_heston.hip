@@ -1,7 +1,7 @@
 // Heston path generation for gfx950 by the full-truncation log-Euler scheme stated in include/mcgpu.h: the launcher of the step
 // rule HestonEuler (heston_schemes.hpp).  The kernel around it -- two adjacent paths per lane with S and v in registers,
-// two Philox streams per path, step-major 16-byte nontemporal stores of the price row and, optionally, of the variance row,
-// the terminal payoff partials of the fused form -- is heston_device.hpp's, shared with the QE generator.
+// two Philox streams per path, the price row and, optionally, the variance row stored per step -- is heston_device.hpp's,
+// shared with the QE generator; its row store, block walk and payoff partials are those of every generator (paths_device.hpp).
 //
 // Roofline: HBM write, 8*(n_steps+1) bytes per path and matrix, reads ~0.  Per path-step the kernel pays half a Philox
 // block and one Box-Muller pair more than the GBM generator, a square root, and an exponential whose argument the host

@@ -1,6 +1,7 @@
 // Heston path generation by Andersen's quadratic-exponential (QE) scheme for gfx950, as stated in include/mcgpu.h
-// (mcg_paths_heston_qe*): the launcher of the step rule HestonQe (heston_schemes.hpp).  The kernel around it -- draws,
-// rows, stores, payoff partials -- is heston_device.hpp's, shared with the Euler generator (kernels_heston.hip).
+// (mcg_paths_heston_qe*): the launcher of the step rule HestonQe (heston_schemes.hpp).  The kernel around it -- draws and
+// rows -- is heston_device.hpp's, shared with the Euler generator (kernels_heston.hip); stores, block walk and payoff
+// partials are those of every generator (paths_device.hpp).
 //
 // What the scheme adds per path-step: two divisions (2/psi and m/(1 + b^2): v_rcp_f64 and two Newton steps each), two more
 // square roots, and -- only in a wave where some lane has psi > psi_c -- the uniform of Philox stream 3, one more

@@ -1,9 +1,8 @@
 // Local-volatility paths for gfx950 (include/mcgpu.h: mcg_paths_localvol, mcg_paths_localvol_payoff).
 //
-// k_localvol_paths<PAYOFF, ONE_SLICE> follows the skeleton of heston_device.hpp and k_gbm_multi: two adjacent paths per lane
-// with S and the running log-moneyness X in registers, fm::Tables in LDS, one Philox block of the price stream per four steps,
-// a wave-uniform row pointer plus a constant lane offset, the 16-byte nontemporal store with its `s_nop` guards,
-// fm::scaled_exp for the price and the payoff partials of heston_device.hpp.
+// k_localvol_paths<PAYOFF, ONE_SLICE> stands on the generators' skeleton of paths_device.hpp (row store, block walk, normals,
+// payoff partials): two adjacent paths per lane with S and the running log-moneyness X in registers, one Philox block of the
+// price stream per four steps, fm::scaled_exp for the price.
 //
 // What is new is the surface lookup: one 16-byte gather {a_j, d_j} per path-step at a per-lane index, from LDS.
 //   ONE_SLICE  (a surface without a time axis) the slice, <= 127 entries, is staged once behind the tables.
@@ -18,6 +17,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "mcg_internal.hpp"
+#include "paths_device.hpp"
 
 namespace mcg {
 
@@ -67,7 +67,6 @@ template <bool PAYOFF, bool ONE_SLICE>
 __global__ __launch_bounds__(256) void k_localvol_paths(LocalVolArgs a) {
     constexpr int PPL = LV_PPL;
     constexpr bool STAGED = LV_STAGED;
-    typedef double v2d __attribute__((ext_vector_type(2)));
     __shared__ fm::Tables tabs;
     __shared__ double2 slices[ONE_SLICE ? LV_SLICE_MAX : STAGED ? 2 * LV_STAGE : 1];
     fm::load_tables(&tabs, a.tabs);
@@ -98,31 +97,15 @@ __global__ __launch_bounds__(256) void k_localvol_paths(LocalVolArgs a) {
     if (in_row || !ONE_SLICE) {
         double* row = a.out + (int64_t)blockIdx.x * (256 * PPL);
         const unsigned lane_bytes = threadIdx.x * (8u * PPL);
-        // (the store of heston_device.hpp, with both of its guards)
-        auto store_pair = [&](double* r, const double (&x)[PPL]) {
-            if (in_row) {
-                const v2d d = {x[0], x[1]};
-                asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 nt\n\ts_nop 1" : : "v"(lane_bytes), "v"(d), "s"(r) : "memory");
-            }
+        auto store_row = [&]() {
+            if (in_row) store_pair16(row, lane_bytes, S[0], S[1]);
         };
-        store_pair(row, S);
+        store_row();
         PhiloxLane rng[PPL];
 #pragma unroll
         for (int p = 0; p < PPL; ++p) rng[p] = philox_lane_setup(a.path_begin + (uint64_t)(i + p), STREAM_PRICE, a.k1);
         uint32_t block = 0;  // the Philox block of the current four steps
         const double2* cur = slices;
-        auto step = [&](const double (&z)[PPL], const int elem) {
-            const double2* sl = ONE_SLICE ? cur : cur + elem * nx1;
-#pragma unroll
-            for (int p = 0; p < PPL; ++p) localvol_step(a, sl, z[p], S[p], X[p]);
-            row += a.ld;
-            store_pair(row, S);
-        };
-        auto pairs = [&](const Philox4 (&w)[PPL], bool second, double (&za)[PPL], double (&zb)[PPL]) {
-#pragma unroll
-            for (int p = 0; p < PPL; ++p)
-                fm::box_muller_pair(second ? w[p].w2 : w[p].w0, second ? w[p].w3 : w[p].w1, tab, za[p], zb[p]);
-        };
         // Staging of the slices of block + 1 (multi-slice kernels): fetch() issues the global loads, land() writes them into the
         // buffer the workgroup is not stepping through.  The barrier at the top of the next block orders land() against
         // that block's reads, and this block's reads against the land() of the block after.
@@ -155,67 +138,41 @@ __global__ __launch_bounds__(256) void k_localvol_paths(LocalVolArgs a) {
                 __syncthreads();
             }
         };
-        const int n_blocks = a.n_steps >> 2;
-        const int rest = a.n_steps & 3;
         Philox4 w[PPL];
         double za[PPL], zb[PPL];
-#pragma unroll 1
-        for (; block < (uint32_t)n_blocks; ++block) {
-            if (!ONE_SLICE) {
-                if (block) stage_barrier();
-                cur = STAGED ? slices + (block & 1u) * LV_STAGE : a.surf + (size_t)block * 4 * nx1;
-                if (STAGED) fetch();
-            }
+        walk_blocks(
+            a.n_steps, block,
+            [&](auto whole) {  // the tail fetches nothing: no block follows it
+                if (!ONE_SLICE) {
+                    if (block) stage_barrier();
+                    cur = STAGED ? slices + (block & 1u) * LV_STAGE : a.surf + (size_t)block * 4 * nx1;
+                    if (STAGED && whole) fetch();
+                }
 #pragma unroll
-            for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, a.k0, a.k1);
-            pairs(w, false, za, zb);
-            step(za, 0);
-            step(zb, 1);
-            pairs(w, true, za, zb);
-            step(za, 2);
-            step(zb, 3);
-            if (!ONE_SLICE && STAGED) land();
-        }
-        if (rest) {  // wave-uniform
-            if (!ONE_SLICE) {
-                if (block) stage_barrier();
-                cur = STAGED ? slices + (block & 1u) * LV_STAGE : a.surf + (size_t)block * 4 * nx1;
-            }
+                for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, a.k0, a.k1);
+                normal_pairs(w, false, tab, za, zb);
+            },
+            [&] { normal_pairs(w, true, tab, za, zb); },
+            [&](auto elem) {
+                const double2* sl = ONE_SLICE ? cur : cur + elem * nx1;
 #pragma unroll
-            for (int p = 0; p < PPL; ++p) w[p] = philox4x32_10_lane(rng[p], block, a.k0, a.k1);
-            pairs(w, false, za, zb);
-            step(za, 0);
-            if (rest >= 2) step(zb, 1);
-            if (rest == 3) {
-                pairs(w, true, za, zb);
-                step(za, 2);
-            }
-        }
+                for (int p = 0; p < PPL; ++p) localvol_step(a, sl, (elem & 1 ? zb : za)[p], S[p], X[p]);
+                row += a.ld;
+                store_row();
+            },
+            [&] {
+                if (!ONE_SLICE && STAGED) land();
+            });
     }
-    if (PAYOFF) {
-        __shared__ double red[2 * 4];
-        double acc[2] = {0.0, 0.0};
-#pragma unroll
-        for (int p = 0; p < PPL; ++p) {
-            const double pay = (in_row && i + p < a.n_paths) ? payoff_of(a.is_call != 0, S[p], a.K) : 0.0;
-            acc[0] += pay;
-            acc[1] += pay * pay;
-        }
-        block_sum<2, 4>(acc, red);
-        if (threadIdx.x == 0) {
-            a.partials[2 * (int64_t)blockIdx.x] = acc[0];
-            a.partials[2 * (int64_t)blockIdx.x + 1] = acc[1];
-        }
-    }
+    if (PAYOFF) payoff_partials(in_row, i, a.n_paths, S, a.K, a.is_call, a.partials);
 }
 
 // One launch of k_localvol_paths over P.  table: n_slices * (n_x - 1) entries {a, d} on the host (mcg_localvol_table), n_slices
 // = 1 or P->n_steps; it goes into the ctx's cached buffer on the ctx's stream ahead of the launch.
 int launch_localvol(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, const LocalVolScalars& c, int n_x, const double* table,
                     int n_slices, bool want_payoff, double K, int is_call) {
-    const int64_t n_blocks = (P->n_paths + 256 * LV_PPL - 1) / (256 * LV_PPL);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
+    const int64_t n_blocks = launch_blocks(P, LV_PPL);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     if (n_x < 2 || n_x > LOCALVOL_MAX_NX || (n_slices != 1 && n_slices != P->n_steps))
         return fail(MCG_ERR_INVALID, "local vol: a table of %d slices x %d nodes does not fit %d steps", n_slices, n_x, P->n_steps);
     const size_t table_doubles = (size_t)n_slices * (size_t)(n_x - 1) * 2;

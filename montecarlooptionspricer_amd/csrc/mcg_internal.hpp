@@ -166,6 +166,18 @@ constexpr int SC_LSM_STATE = 144;  // [144..147) per-date LSM state: date, phase
 int pool_alloc(mcg_ctx* ctx, size_t bytes, void** out);
 void pool_release(mcg_ctx* ctx, void* ptr, size_t bytes);
 int ensure_cap(mcg_ctx* ctx, double** buf, size_t* cap, size_t need_doubles);
+// The grid of a step-major path generator (paths_device.hpp): workgroups of 256 lanes with ppl paths each over n_paths, or
+// over the padded rows of P; -1 after fail(MCG_ERR_INVALID, ...) where one launch cannot cover them
+inline int64_t launch_blocks(int64_t n_paths, int ppl) {
+    const int64_t n_blocks = (n_paths + 256 * ppl - 1) / (256 * ppl);
+    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch"), -1;
+    return n_blocks;
+}
+inline int64_t launch_blocks(const mcg_paths* P, int ppl) {
+    const int64_t n_blocks = launch_blocks(P->n_paths, ppl);
+    if (n_blocks >= 0 && (P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns"), -1;
+    return n_blocks;
+}
 
 // timing scope: records events around a launch when ctx->timing is on
 struct TimedLaunch {
@@ -198,7 +210,7 @@ int peer_arm(mcg_ctx* ctx, double* mbox, int rounds, int n, uint64_t sentinel); 
 int paths_new(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, mcg_paths** out);
 
 // generator launchers, each in the .hip file of its name; the Heston and Bates ones derive their scheme's constants and share
-// heston_device.hpp's launch_heston_scheme
+// heston_device.hpp's launch_heston_scheme.  All but launch_gbm and launch_rbergomi size their grid with launch_blocks.
 int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double sigma, double dt,
                bool want_payoff, double K, int is_call);
 int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double xi, double H,

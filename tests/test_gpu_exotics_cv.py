@@ -170,9 +170,9 @@ def twin_numpy(seed, S0, r, q, sigma, dt, n_steps, n_paths, path_begin, first_ro
                      S0 * np.exp(M.max(axis=0))])
 
 
-@pytest.mark.parametrize("n_steps", [1, 3, 4, 5, 50, 253])
+@pytest.mark.parametrize("n_steps", [1, 2, 3, 4, 5, 7, 50, 253])
 def test_twin_statistics_against_numpy(eng, n_steps):
-    begins = {1: 0, 2: 1, 63: 2 ** 32 + 12345, 65: 2 ** 33 + 1, 257: 777, 1001: 2 ** 32 + 1}
+    begins = {1: 0, 2: 1, 63: 2 ** 32 + 12345, 65: 2 ** 33 + 1, 257: 777, 513: 3, 1001: 2 ** 32 + 1}
     for n_paths, begin in begins.items():
         seed = SEED64 if n_paths in (65, 1001) else 7
         for first_row in sorted({0, 1, n_steps}):

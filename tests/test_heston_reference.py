@@ -154,8 +154,11 @@ LARGE_VOL = dict(kappa=1.0, theta=4.0, sigma_v=1.0, rho=-0.3, v0=4.0)
 # 5.2e-15 at 40).  A yardstick that is itself good to 1e-8 cannot carry a bound below 1e-9, so that set's long shape has 40
 # steps (v < 0 on a twentieth of its paths already); test_parity_cases_are_well_conditioned holds every case to 1e-11.
 SEED64 = 0x9E3779B97F4A7C15
+# The last four complete n_steps in {1, 2, 3, 4, 5, 7} -- every tail of the block walk (csrc/paths_device.hpp) with and without a
+# whole block before it -- each with a path count out of {1, 257, 513}: a last workgroup whose upper waves lie beyond the row,
+# on either side of a 256-column pad.
 PARITY_SHAPES = ((8, 1000, 0, 7), (9, 257, 1, 7), (10, 700, 12345, SEED64), (11, 1, 2 ** 33 + 12345, 7), (3, 513, 2 ** 33 + 1, SEED64),
-                 (1, 300, 0, 7))
+                 (1, 300, 0, 7), (2, 513, 0, 7), (4, 257, 2 ** 33 + 3, SEED64), (5, 1, 77, 7), (7, 513, 1, SEED64))
 PARITY_SETS = {"feller": (PARAMS["feller"], 1.0 / 252.0, PARITY_SHAPES + ((252, 1300, 777, SEED64),)),
                "feller-violating": (FELLER_VIOLATING, 1.0 / 252.0, PARITY_SHAPES + ((40, 1300, 777, SEED64),)),
                "large-vol": (LARGE_VOL, 1.0 / 12.0, PARITY_SHAPES + ((252, 1300, 777, SEED64),))}

@@ -59,7 +59,8 @@ enum mcg_kernel {
     MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
     MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
     MCG_K_LSM_APPLY = 14, /* mcg_lsm_apply: the forward pass of an exercise policy over a stored matrix */
-    MCG_K_COUNT = 15
+    MCG_K_LSM_DUAL = 15,  /* mcg_lsm_dual_upper: the nested simulation and the martingale recursion (two launches a batch) */
+    MCG_K_COUNT = 16
 };
 
 const char* mcg_last_error(void);
@@ -451,8 +452,9 @@ int mcg_price_lsm2(mcg_ctx* ctx, const mcg_paths* paths, const mcg_paths* state,
  * a kind outside {0, 1, 2}; row n_steps not TERMINAL, or another row TERMINAL; a non-finite coefficient or centre in an
  * EXERCISE_RULE row; (continuation) a date outside [0, n_steps], n < 0, a NULL S or cont_out with n > 0; a ctx that holds a
  * collective, for fit and apply alike.  An empty matrix is MCG_ERR_EMPTY_PATHS.
- * Out of scope: two-regressor policies (mcg_price_lsm2); upper bounds; collectives; the one-launch sweeps; the batch rows, the
- * coalescing layer and the drop-in classes; Greeks under a fixed policy. */
+ * Out of scope: two-regressor policies (mcg_price_lsm2); upper bounds other than mcg_lsm_dual_upper's (below: the one-regressor
+ * policy under a GBM inner model); collectives; the one-launch sweeps; the batch rows, the coalescing layer and the drop-in
+ * classes; Greeks under a fixed policy. */
 #define MCG_LSM_POLICY_STRIDE 20
 enum mcg_lsm_policy_kind { MCG_POL_CONTINUE = 0, MCG_POL_EXERCISE_RULE = 1, MCG_POL_TERMINAL = 2 };
 typedef struct mcg_lsm_policy_hdr {
@@ -466,6 +468,65 @@ int mcg_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coe
                   double* std_err, double* sums3, int64_t* tau_hist);
 int mcg_lsm_policy_continuation(const mcg_lsm_policy_hdr* hdr, const double* coef, int date, const double* S, int64_t n,
                                 double* cont_out);
+
+/* ---- Dual upper bounds for LSM exercise policies by nested simulation ------------------------- */
+/* mcg_lsm_apply prices a stopping time: a lower bound.  mcg_lsm_dual_upper is the other side, the Andersen-Broadie (2004)
+ * dual: along each outer path it builds the martingale part of the policy's own value process, with every conditional
+ * expectation estimated by n_inner inner paths started from the outer path's price, and takes the pathwise maximum of the
+ * discounted payoff less that martingale.
+ *
+ * Inputs: a checked policy (hdr, coef), n = hdr.n_steps; the outer matrix `paths` of n + 1 rows; the inner model: GBM with
+ * model.sigma >= 0, dividend yield model.q and the header's r and dt; model.n_inner in [1, 65536]; the inner seed and
+ * path_begin.  Per outer path i, global id g = path_begin + i, prices S_0 .. S_n:
+ *   h_j = payoff(S_j) disc_j, disc_j = exp(-r dt j) formed on the host in binary64 (mcg_lsm_apply's table).
+ *   e_j = mcg_lsm_apply's stop decision at (j, S_j), bit for the same rule: row j is EXERCISE_RULE, payoff(S_j) > 1e-14 and
+ *         !(continuation_j(S_j) > payoff(S_j)), Horner fused in y = fma(S, 1/K, -1) - centre; e_n is true.
+ *   C_j (j < n) = (sum over k < n_inner of v_{j,k}) / n_inner, the sum in ascending k within a slice of consecutive k and
+ *         the slices in ascending order (the slices depend on n_inner and n only).  v_{j,k} is what mcg_lsm_apply returns for
+ *         inner path k: it starts at S_j on date j, visits the dates j+1 .. n and stops at the first date l >= j+1 at which
+ *         the rule stops (row n always), with v = payoff(S_l) disc_l.  An inner step is the in-register twin's
+ *         (mcg_gbm_twin_stats): X = 0 at date j, X += fma(a, z, m), a = sigma sqrt(dt), m = (r - q - sigma^2/2) dt,
+ *         S_l = S_j exp(X).
+ *   L_j = e_j ? h_j : C_j (j < n), L_n = h_n;  Mt_0 = 0, Mt_{j+1} = Mt_j + L_{j+1} - C_j.
+ *   D_i = max over the exercisable dates of (h_j - Mt_j): every j < n with !((double)j * dt > hdr.maturity), the expression
+ *         the fit uses, and j = n.
+ * upper = mean(D); std_err from {sum D, sum D^2, n} as mcg_lsm_apply forms its own.
+ * Inner draws (the RNG contract of csrc/philox.hpp, extended): key = model.seed; counter = (g_lo, g_hi, (j << 12) | b,
+ * 0x10000 + k); the step from date l - 1 to l, relative step s = l - j - 1, uses block b = s >> 2, element s & 3.  Hence
+ * n_steps <= 16384.  Stream numbers >= 0x10000 are no generator's, so the inner seed may equal the outer one.
+ *
+ * For ANY policy E[D] is an upper bound on the value of the option exercisable on those dates, and the noise of the inner means
+ * biases it upwards, never downwards (D is a maximum of terms linear in them: Jensen).  It is the caller's bound only if
+ * the outer paths follow the same GBM (r, q, sigma, dt) as the inner ones: the library cannot check that.
+ *
+ * Outputs: sums3 (may be NULL) = {sum D, sum D^2, n}; cont_out (may be NULL; host, [n_steps][n_paths]) = C_j of every outer
+ * path; d_out (may be NULL; host, n_paths) = D_i; inner_steps (may be NULL) = the sum over every inner path of the steps it
+ * took, an integer count.  No floating-point atomics: repeated calls are bit-identical, and D_i and the C_j of outer path i
+ * depend on that path alone, so any split of the outer paths into shards gives the same d_out and cont_out, bit for bit.
+ * Sharded sets are combined by hand: give each shard its path_begin and add the shards' sums3 and inner_steps.  inner_steps
+ * then equals the whole set's exactly; the added sums3 equal the whole set's to the rounding of the partial sums (floating-point
+ * sums of other groupings), not bit for bit.  Booked under MCG_K_LSM_DUAL.
+ * MCG_ERR_INVALID with a message: a NULL hdr, coef, model, ctx, paths or upper; n_inner outside [1, 65536]; a negative or
+ * non-finite sigma; a non-finite q; hdr.n_steps above 16384; anything mcg_lsm_policy_continuation's validator rejects (these
+ * are answered before the ctx is looked at); paths of another ctx; hdr.n_steps different from the matrix's; a ctx that holds a
+ * collective.  An empty matrix is MCG_ERR_EMPTY_PATHS.
+ * Out of scope: two-regressor policies; inner models other than GBM; collectives; compaction of stopped lanes and variance
+ * reduction of the inner means; the drop-in classes. */
+#define MCG_LSM_DUAL_MAX_INNER 65536
+#define MCG_LSM_DUAL_MAX_STEPS 16384
+typedef struct mcg_lsm_dual_model {
+    uint64_t seed;
+    double sigma, q;
+    uint64_t path_begin;
+    int n_inner;
+    int reserved;
+} mcg_lsm_dual_model;
+int mcg_lsm_dual_upper(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coef, const mcg_paths* paths,
+                       const mcg_lsm_dual_model* model, double* upper, double* std_err,
+                       double* sums3 /* may be NULL: {sum D, sum D^2, n} */,
+                       double* cont_out /* may be NULL: host, [n_steps][n_paths], C_j of every outer path */,
+                       double* d_out /* may be NULL: host, n_paths, D_i */,
+                       int64_t* inner_steps /* may be NULL: sum over every inner path of the steps it took */);
 
 /* ---- Greeks ----------------------------------------------------------------------------- */
 /* Price sensitivities with Monte Carlo standard errors.  Every field an entry point does not fill is NaN, and so is its

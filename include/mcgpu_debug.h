@@ -26,6 +26,15 @@ int mcg_debug_sincos2_tables(double* coarse, double* fine);
  * narrow kernel (k_gbm_paths), 2 = the wide one (k_gbm_paths_wide), -1 = leave it as it is; *last_route (may be NULL) = what
  * the last GBM launch took (1 or 2; 0 before the first). */
 int mcg_debug_gbm_route(mcg_ctx* ctx, int route, int* last_route);
+/* Measurement hook: the path-steps the wavefronts of this context's last mcg_lsm_dual_upper ran through -- for every step a
+ * wavefront executed, the outer paths it holds, whether the inner path of each was still alive or not.  inner_steps over this
+ * is the share of live lane-steps (1 where no inner path stops before the last date). */
+int mcg_debug_lsm_dual_executed(mcg_ctx* ctx, int64_t* executed);
+/* Test hook: mcg_lsm_dual_upper works through its outer paths in batches whose workspace (slices x dates x outer paths of the
+ * batch, in doubles) stays under a bound, 2^24 by default; `doubles` sets that bound for this context (0: the default).  A batch
+ * is a multiple of 512 outer paths and never fewer, so a small bound makes a few hundred outer paths take several batches.
+ * No result depends on the bound. */
+int mcg_debug_lsm_dual_workspace(mcg_ctx* ctx, size_t doubles);
 /* Test hooks of the one-launch LSM sweeps' hand-shake: spin_limit = polling rounds before a wait gives up (0: every
  * wait gives up at once, which drives the time-out -> per-date fall-back on a healthy device; < 0: the default);
  * poll_delay = units of ~4 us by which workgroups other than the reducing one reach their coefficient poll late. */

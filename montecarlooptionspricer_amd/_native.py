@@ -14,6 +14,8 @@ KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_
                 K_LSM_SOLVE: "lsm_solve", K_TRANSPOSE: "transpose", K_ASYM: "asymptotic", K_MARTINGALE: "martingale", K_BRANCHING: "branching", K_BATCH: "batch_rows",
                 K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi", K_LOCALVOL: "localvol"}
 K_LSM_APPLY = 14  # mcg_lsm_apply's forward pass (KERNEL_NAMES stays the table of the fourteen spans the bench tools tabulate)
+K_LSM_DUAL = 15   # mcg_lsm_dual_upper's nested simulation and martingale recursion
+LSM_DUAL_MAX_INNER, LSM_DUAL_MAX_STEPS = 65536, 16384
 
 # LSM exercise policies (include/mcgpu.h): a row is LSM_POLICY_STRIDE doubles, slot 18 its kind
 LSM_POLICY_STRIDE = 20
@@ -70,6 +72,12 @@ class LsmPolicyHdr(C.Structure):
     """mcg_lsm_policy_hdr (include/mcgpu.h): what an LSM exercise policy was fitted with."""
     _fields_ = [("n_steps", C.c_int), ("poly_order", C.c_int), ("is_call", C.c_int), ("reserved", C.c_int),
                 ("r", C.c_double), ("K", C.c_double), ("maturity", C.c_double), ("dt", C.c_double)]
+
+
+class LsmDualModel(C.Structure):
+    """mcg_lsm_dual_model (include/mcgpu.h): the inner GBM of mcg_lsm_dual_upper (r and dt are the policy header's)."""
+    _fields_ = [("seed", C.c_uint64), ("sigma", C.c_double), ("q", C.c_double), ("path_begin", C.c_uint64), ("n_inner", C.c_int),
+                ("reserved", C.c_int)]
 
 
 class Exotic(C.Structure):
@@ -209,6 +217,9 @@ def load_library():
     newer("mcg_lsm_fit", [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp, C.POINTER(LsmPolicyHdr), dp])
     newer("mcg_lsm_apply", [vp, C.POINTER(LsmPolicyHdr), dp, vp, dp, dp, dp, C.POINTER(C.c_int64)])
     newer("mcg_lsm_policy_continuation", [C.POINTER(LsmPolicyHdr), dp, C.c_int, dp, C.c_int64, dp])
+    newer("mcg_lsm_dual_upper", [vp, C.POINTER(LsmPolicyHdr), dp, vp, C.POINTER(LsmDualModel), dp, dp, dp, dp, dp, C.POINTER(C.c_int64)])
+    newer("mcg_debug_lsm_dual_executed", [vp, C.POINTER(C.c_int64)])
+    newer("mcg_debug_lsm_dual_workspace", [vp, C.c_size_t])
     newer("mcg_path_stats", [vp, vp, C.c_int, dp])
     newer("mcg_price_exotics", [vp, vp, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
     newer("mcg_price_exotics_cv", [vp, vp, vp, C.POINTER(GbmTwin), C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,

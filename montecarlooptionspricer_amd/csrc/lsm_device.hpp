@@ -391,6 +391,41 @@ __device__ __forceinline__ double lsm_continuation(const double (&c)[NB], double
     return cont;
 }
 
+// ---- a policy's rows (mcg_lsm_apply, mcg_lsm_dual_upper) ----
+typedef double la_d2 __attribute__((ext_vector_type(2)));
+// The policy table and the discounts are written before the launch and only read in it: read through the constant address
+// space, a wave-uniform index gives scalar loads although the kernel also stores (partials, counters).
+typedef const double __attribute__((address_space(4))) * la_table;
+
+// Horner from the policy's order down, for the two paths of a unit at once; c: the date's sixteen coefficients (uniform)
+__device__ __forceinline__ void la_continuation(const double (&c)[16], int order, double y0, double y1, double& cont0, double& cont1) {
+    double a = 0.0, b = 0.0;
+#define LA_STEP(T)              \
+    a = fma(a, y0, c[T]);       \
+    b = fma(b, y1, c[T]);
+    switch (order) {
+        default: LA_STEP(15) [[fallthrough]];
+        case 14: LA_STEP(14) [[fallthrough]];
+        case 13: LA_STEP(13) [[fallthrough]];
+        case 12: LA_STEP(12) [[fallthrough]];
+        case 11: LA_STEP(11) [[fallthrough]];
+        case 10: LA_STEP(10) [[fallthrough]];
+        case 9: LA_STEP(9) [[fallthrough]];
+        case 8: LA_STEP(8) [[fallthrough]];
+        case 7: LA_STEP(7) [[fallthrough]];
+        case 6: LA_STEP(6) [[fallthrough]];
+        case 5: LA_STEP(5) [[fallthrough]];
+        case 4: LA_STEP(4) [[fallthrough]];
+        case 3: LA_STEP(3) [[fallthrough]];
+        case 2: LA_STEP(2) [[fallthrough]];
+        case 1: LA_STEP(1) [[fallthrough]];
+        case 0: LA_STEP(0)
+    }
+#undef LA_STEP
+    cont0 = a;
+    cont1 = b;
+}
+
 // run-time order -> the unrolled instance
 __device__ inline void lsm_solve_one(const double* moments, int nb, double min_count, double K, double* coef) {
     switch (nb) {

@@ -111,6 +111,8 @@ struct mcg_ctx {
     double* sincos2_tab = nullptr;  // device copy of host_sincos2_tables(): coarse, then fine (128 KiB; fm::sincos_two_level)
     int gbm_route = 0;           // mcg_debug_gbm_route: 0 = launch_gbm chooses, 1 = k_gbm_paths, 2 = k_gbm_paths_wide
     int gbm_last_route = 0;      //   what the last GBM launch took (1 or 2; 0: none yet)
+    int64_t lsm_dual_executed = 0;  // mcg_debug_lsm_dual_executed: path-steps the waves of the last mcg_lsm_dual_upper ran through
+    size_t lsm_dual_ws_doubles = 0;  // mcg_debug_lsm_dual_workspace: the workspace bound of one batch of mcg_lsm_dual_upper (0: default)
 
     // collective
     mcg_allreduce_fn allreduce = nullptr;

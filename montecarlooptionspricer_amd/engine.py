@@ -389,6 +389,45 @@ class PathEngine:
             out += (sums,)
         return out
 
+    def dual_upper_lsm(self, policy: "LsmPolicy", paths: PathMatrix, sigma: float, n_inner: int, seed: int, q: float = 0.0,
+                       path_begin: int = 0, return_cont: bool = False, return_d: bool = False) -> "DualResult":
+        """The Andersen-Broadie dual upper bound of the policy by nested simulation (mcg_lsm_dual_upper): along every outer
+        path of `paths`, n_inner GBM paths (sigma, q, the policy's r and dt; Philox key `seed`) from every date estimate the
+        policy's continuation value, and the bound is the mean of the pathwise maximum of the discounted payoff less the
+        martingale they build.  An upper bound for any policy, biased upwards by the inner noise -- the caller's bound only if
+        the outer paths follow the same GBM.  path_begin: the global id of the first outer path (shards: add sums3 and
+        inner_steps).  Returns a DualResult (upper, std_err, sums3, inner_steps), then cont [n_steps][n_paths] when return_cont,
+        then d [n_paths] when return_d."""
+        paths._alive()
+        if not 1 <= int(n_inner) <= N.LSM_DUAL_MAX_INNER:
+            raise McgError(f"dual_upper_lsm: n_inner must be in [1, {N.LSM_DUAL_MAX_INNER}] (got {n_inner})", 1)
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(path_begin) < 2 ** 64:
+            raise McgError("dual_upper_lsm: seed and path_begin must be in [0, 2^64)", 1)
+        up, se, steps = C.c_double(), C.c_double(), C.c_int64()
+        dp = C.POINTER(C.c_double)
+        sums = np.zeros(3)
+        cont = np.empty((policy.n_steps, paths.n_paths)) if return_cont else None
+        d = np.empty(paths.n_paths) if return_d else None
+        hdr = policy._hdr()
+        model = N.LsmDualModel(int(seed), float(sigma), float(q), int(path_begin), int(n_inner), 0)
+        check(self._L.mcg_lsm_dual_upper(self._ctx, C.byref(hdr), policy.coef.ctypes.data_as(dp), paths._h, C.byref(model), C.byref(up),
+                                         C.byref(se), sums.ctypes.data_as(dp), cont.ctypes.data_as(dp) if return_cont else None,
+                                         d.ctypes.data_as(dp) if return_d else None, C.byref(steps)))
+        return DualResult(up.value, se.value, sums, steps.value, cont, d)
+
+    def debug_lsm_dual_executed(self) -> int:
+        """Measurement hook (mcg_debug_lsm_dual_executed, include/mcgpu_debug.h; not part of the product surface): path-steps
+        the wavefronts of the last dual_upper_lsm ran through, stopped inner paths included -- inner_steps over this is the
+        share of live lane-steps that tools/bench_lsm_dual.py reports."""
+        n = C.c_int64()
+        check(self._L.mcg_debug_lsm_dual_executed(self._ctx, C.byref(n)))
+        return n.value
+
+    def debug_lsm_dual_workspace(self, doubles: int = 0) -> None:
+        """Test hook (mcg_debug_lsm_dual_workspace): the workspace, in doubles, one batch of outer paths of dual_upper_lsm may
+        use; 0: the default (2^24).  A batch is never smaller than 512 outer paths."""
+        check(self._L.mcg_debug_lsm_dual_workspace(self._ctx, int(doubles)))
+
     def greeks_european(self, paths: PathMatrix, K: float, r: float, T: float, is_call: bool,
                         sigma: Optional[float] = None) -> dict:
         """European price, delta, gamma, vega, rho, dual delta and their std errors (mcg_greeks_european); NaN where a
@@ -765,6 +804,18 @@ class CvResult(tuple):
         """(plain_se / std_err)^2: the factor in path count the controls are worth (inf where std_err is 0)."""
         with np.errstate(divide="ignore", invalid="ignore"):
             return (self.plain_se / self.std_err) ** 2
+
+
+class DualResult(tuple):
+    """What dual_upper_lsm returns: (upper, std_err, sums3, inner_steps), then cont and d where they were asked for, with the
+    same by name (.cont and .d are None unless asked for)."""
+
+    def __new__(cls, upper, std_err, sums3, inner_steps, cont=None, d=None):
+        self = super().__new__(cls, (upper, std_err, sums3, inner_steps) + tuple(x for x in (cont, d) if x is not None))
+        self.cont, self.d = cont, d
+        return self
+
+    upper, std_err, sums3, inner_steps = (property(lambda self, i=i: self[i]) for i in range(4))
 
 
 def control(form, mean: Optional[float] = None, on_twin: bool = False, **exotic_fields) -> tuple:

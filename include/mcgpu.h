@@ -184,7 +184,7 @@ int mcg_paths_heston_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, do
  *   z1 = draw n of Philox stream 0,  z2 = draw n of Philox stream 1    (as above: block n >> 2, element n & 3)
  *   u  = (word (n & 3) of block (n >> 2) of Philox stream 3 + 0.5) * 2^-32      in (0, 1)
  *        (stream 2 belongs to the branching-process kernels)
- *   m  = theta + (v_n - theta) E
+ *   m  = theta + (v_n - theta) E                      kappa == 0: m = v_n
  *   s2 = v_n c1 + c2
  *   psi = s2 / m^2
  *   m == 0          : v' = 0

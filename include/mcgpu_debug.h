@@ -17,8 +17,30 @@ extern "C" {
  * fn 4: x holds a path id as a double; y[0..3] = the four normals of block 0, stream 0, seed 1
  * fn 5: as 4 through the reference-grade (device library) implementation.
  * fn 6: y[0] = e^x for |x| <= 0.125 (the branch-free step exponential)   fn 7: the same for |x| <= 0.1.
- * fn 10: as 3 by the two 4096-entry tables (fm::sincos_two_level), read from device memory. */
+ * fn 8: y[0], y[1] = 2^(x/256), 2^((x+96)/256): both chains of fm::exp2_pair, x already in units of (ln 2)/256.
+ * fn 9: as 4 with the four table entries of the block requested together (normal_quad_fast<true>).
+ * fn 10: as 3 by the two 4096-entry tables (fm::sincos_two_level), read from device memory.
+ * fn 11: y[0] = e^x with the range reduction always on (fm::exp_full).
+ * fn 12: y[0], y[1] = e^x, e^(x + 0.375): both chains of fm::exp_full2.
+ * fn 13: y[0], y[1] = e^x - 1, e^-x - 1 for |x| <= 0.1: both chains of fm::expm1_small6_2.   fn 14: the same for |x| <= 0.34
+ *        (fm::expm1_small9_2).
+ * fn 15: y[0] = sqrt_nonneg(x) of the Heston steps: 0 for x <= 0, the root of max(x, 2^-1000) otherwise. */
 int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n);
+/* Test hook: the same for routines with several inputs per element or with wave-uniform parameters.  x holds n_in doubles per
+ * element, params n_params doubles for the whole launch (both must be what the fn takes); y has 4n doubles as above.  32-bit
+ * Philox words and path ids travel as doubles.
+ * fn 0: x = {d}: y[0] = qe_rcp(d)             fn 1: x = {n, d}: y[0] = qe_div(n, d)      (csrc/heston_schemes.hpp)
+ * fn 2: x = {wa, wb}: y[0] = the radius uniform ((wb & 0xFF) 2^32 + wa + 1/2) 2^-40      (radius_u01)
+ * fn 3: x = {u}, params = {vol2}: y[0] = vol2 (-2 ln u) by fm::neg2log_scaled, its table staged by fm::load_tables_scaled(vol2)
+ *       and its constants built by fm::make_log_scale(vol2), as the GBM kernels do.
+ * fn 4..7: x = {wa, wb}, params = {vol, drift}: y[0], y[1] = drift + vol z_even, drift + vol z_odd of the pair (the GBM step's
+ *       exponents) by fm::box_muller_pair_affine (4), _affine_scaled (5; staging and constants of fn 3 with vol2 = vol vol),
+ *       _affine2 (6) and _affine_scaled2 (7), the last two with the context's two-level sin/cos tables in device memory.
+ * fn 8: one HestonQe::step.  x = {v, z1, z2, S, path id}; params = the scheme's constants {theta, E, c1, c2, drift, K1, K2, K3}
+ *       as they stand (not the model's parameters), then {k0, k1, block, elem}: the Philox key and the place of the step's
+ *       stream-3 uniform.  A lane takes elements 2j and 2j + 1 as its two paths (the lanes of the last wave beyond n repeat
+ *       the last element); y = {v', S', 1 if s2 > 1.5 m^2 (the exponential branch) else 0}. */
+int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in, const double* params, int n_params, double* y, int64_t n);
 /* Test hook, host-only: the two tables of fm::sincos_two_level as the contexts upload them, 4096 {cos, sin} pairs each:
  * coarse[i] = (cos, sin)(2 pi i / 4096), fine[j] = (cos, sin)(2 pi (j + 1/2) / 2^24). */
 int mcg_debug_sincos2_tables(double* coarse, double* fine);

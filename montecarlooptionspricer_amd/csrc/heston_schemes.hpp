@@ -99,7 +99,9 @@ struct HestonQe {
         const double E = std::exp(-kappa * dt);
         const double g = kappa * rho / sigma_v - 0.5;
         Consts c;
-        c.theta = theta;
+        // kappa = 0: m = v exactly.  theta + (v - theta) rounds at the size of theta, and a step from v << theta then carries
+        // that into ln(1 / m^2) of the exponential branch (2e-12 of S' at v = 1e-8, theta = 0.04); theta enters nothing else here.
+        c.theta = kappa > 0.0 ? theta : 0.0;
         c.E = E;
         c.c1 = kappa > 0.0 ? sigma_v * sigma_v * E * (1.0 - E) / kappa : sigma_v * sigma_v * dt;
         c.c2 = kappa > 0.0 ? theta * sigma_v * sigma_v * (1.0 - E) * (1.0 - E) / (2.0 * kappa) : 0.0;

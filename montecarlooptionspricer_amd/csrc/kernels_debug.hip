@@ -1,7 +1,9 @@
-// Test hook behind mcg_debug_eval: runs one routine of fastmath.hpp elementwise so that tests can
-// measure its error against mpmath / libm.  Not on any product path.
+// Test hooks behind mcg_debug_eval and mcg_debug_eval_v: run one routine of fastmath.hpp, philox.hpp or the Heston
+// steps (heston_device.hpp, heston_schemes.hpp) elementwise so that tests can measure its error against mpmath / libm.
+// Not on any product path.
 #include "devmath.hpp"
 #include "fastmath.hpp"
+#include "heston_schemes.hpp"
 #include "mcg_internal.hpp"
 
 namespace mcg {
@@ -28,6 +30,11 @@ __global__ __launch_bounds__(256) void k_debug_eval(int fn, const double* x, dou
         case 8: fm::exp2_pair(v, v + 96.0, tab, a, b); break;  // 2^(v/256), 2^((v+96)/256)
         case 9: fm::normal_quad_fast<true>(1u, 0u, (uint64_t)v, 0u, STREAM_PRICE, tab, z); break;
         case 10: fm::sincos_two_level((uint32_t)v, sincos2, sincos2 + fm::SINCOS2_ENTRIES, a, b); break;  // (tables in device memory)
+        case 11: a = fm::exp_full(v); break;
+        case 12: fm::exp_full2(v, v + 0.375, a, b); break;
+        case 13: fm::expm1_small6_2(v, -v, a, b); break;
+        case 14: fm::expm1_small9_2(v, -v, a, b); break;
+        case 15: a = sqrt_nonneg(v); break;
         default: normal_quad_ref(1u, 0u, (uint64_t)v, 0u, STREAM_PRICE, z); break;
     }
     if (fn < 4 || (fn > 5 && fn != 9)) {
@@ -38,11 +45,167 @@ __global__ __launch_bounds__(256) void k_debug_eval(int fn, const double* x, dou
     for (int e = 0; e < 4; ++e) y[4 * i + e] = z[e];
 }
 
+// ---- mcg_debug_eval_v: routines with several inputs per element or wave-uniform parameters ----------------------------------
+enum : int {
+    V_QE_RCP = 0, V_QE_DIV, V_RADIUS, V_NEG2LOG_SCALED, V_BM_AFFINE, V_BM_AFFINE_SCALED, V_BM_AFFINE2, V_BM_AFFINE_SCALED2,
+    V_QE_STEP, V_COUNT
+};
+constexpr int V_MAX_PARAMS = 12;
+// {doubles per element, parameters} of each fn
+constexpr int V_SHAPE[V_COUNT][2] = {{1, 0}, {2, 0}, {2, 0}, {1, 1}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {5, 12}};
+
+struct DebugVArgs {
+    int fn, n_in;
+    const double* x;
+    double* y;
+    int64_t n;
+    double p[V_MAX_PARAMS];
+    double scale;      // the scaled forms: vol^2, what the GBM kernels stage their logarithm table with
+    fm::LogScale ls;   // ... and fm::make_log_scale of it, built on the host as launch_gbm does
+    const double2* gtab;
+    const double2* sincos2;
+};
+
+__global__ __launch_bounds__(256) void k_debug_eval_v(DebugVArgs a) {
+    __shared__ fm::Tables tabs;
+    const bool scaled = a.fn == V_NEG2LOG_SCALED || a.fn == V_BM_AFFINE_SCALED || a.fn == V_BM_AFFINE_SCALED2;  // (uniform)
+    if (scaled) fm::load_tables_scaled(&tabs, a.gtab, a.scale);
+    else fm::load_tables(&tabs, a.gtab);
+    const fm::Tables* tab = &tabs;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const double* xi = a.x + i * a.n_in;
+    const double2 *coarse = a.sincos2, *fine = a.sincos2 + fm::SINCOS2_ENTRIES;  // (in device memory)
+    double z[4] = {0.0, 0.0, 0.0, 0.0};
+    switch (a.fn) {
+        case V_QE_RCP: z[0] = qe_rcp(xi[0]); break;
+        case V_QE_DIV: z[0] = qe_div(xi[0], xi[1]); break;
+        case V_RADIUS: z[0] = radius_u01((uint32_t)xi[0], (uint32_t)xi[1]); break;
+        case V_NEG2LOG_SCALED: z[0] = fm::neg2log_scaled(xi[0], tab->log, a.ls); break;
+        case V_BM_AFFINE: fm::box_muller_pair_affine((uint32_t)xi[0], (uint32_t)xi[1], tab, a.p[0], a.p[1], z[0], z[1]); break;
+        case V_BM_AFFINE_SCALED:
+            fm::box_muller_pair_affine_scaled((uint32_t)xi[0], (uint32_t)xi[1], tab, a.ls, a.p[1], z[0], z[1]);
+            break;
+        case V_BM_AFFINE2:
+            fm::box_muller_pair_affine2((uint32_t)xi[0], (uint32_t)xi[1], tab->log, coarse, fine, a.p[0], a.p[1], z[0], z[1]);
+            break;
+        default:
+            fm::box_muller_pair_affine_scaled2((uint32_t)xi[0], (uint32_t)xi[1], tab->log, coarse, fine, a.ls, a.p[1], z[0], z[1]);
+            break;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a.y[4 * i + e] = z[e];
+}
+
+// One HestonQe::step.  The step asks for the path of its p-th path as `a.path_begin + (i + p)`; here every element names its own
+// path, so path_begin is a pair of ids whose `+ p` picks one (i = 0).  Everything else of the argument block is what the
+// step reads of HestonArgs.
+struct DebugQePaths {
+    uint64_t id[HESTON_PPL];
+    __device__ __forceinline__ uint64_t operator+(uint64_t p) const { return id[p]; }
+};
+struct DebugQeArgs {
+    HestonQe::Consts c;
+    DebugQePaths path_begin;
+    uint32_t k0, k1;
+};
+
+__global__ __launch_bounds__(256) void k_debug_qe_step(DebugVArgs a) {
+    constexpr int PPL = HESTON_PPL;
+    __shared__ fm::Tables tabs;
+    fm::load_tables(&tabs, a.gtab);
+    __syncthreads();
+    // a lane takes two consecutive elements as its two paths.  Every lane of a launched wave runs the step -- the wave's
+    // ballot decides whether the exponential branch is entered -- so a lane past the end repeats the last element and
+    // stores nothing.
+    const int64_t first = ((int64_t)blockIdx.x * 256 + threadIdx.x) * PPL;
+    DebugQeArgs q;
+    q.c = HestonQe::Consts{a.p[0], a.p[1], a.p[2], a.p[3], a.p[4], a.p[5], a.p[6], a.p[7]};
+    q.k0 = (uint32_t)a.p[8];
+    q.k1 = (uint32_t)a.p[9];
+    const uint32_t block = (uint32_t)a.p[10];
+    const int elem = (int)a.p[11];
+    double S[PPL], v[PPL], z1[PPL], z2[PPL], flag[PPL];
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        const int64_t e = first + p < a.n ? first + p : a.n - 1;
+        const double* xi = a.x + e * 5;
+        v[p] = xi[0];
+        z1[p] = xi[1];
+        z2[p] = xi[2];
+        S[p] = xi[3];
+        q.path_begin.id[p] = (uint64_t)xi[4];
+        // the step's decision, from the step's own expressions
+        const double m = __builtin_fma(v[p] - q.c.theta, q.c.E, q.c.theta);
+        flag[p] = __builtin_fma(v[p], q.c.c1, q.c.c2) <= QE_PSI_C * (m * m) ? 0.0 : 1.0;
+    }
+    HestonQe scheme;
+    scheme.new_block(q, (int64_t)0, block, &tabs);
+    scheme.step(q, (int64_t)0, block, elem, &tabs, z1, z2, S, v);
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        if (first + p >= a.n) continue;
+        double* yi = a.y + 4 * (first + p);
+        yi[0] = v[p];
+        yi[1] = S[p];
+        yi[2] = flag[p];
+        yi[3] = 0.0;
+    }
+}
+
 }  // namespace mcg
+
+extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in, const double* params, int n_params, double* y,
+                                int64_t n) {
+    using namespace mcg;
+    if (!ctx || !x || !y || n < 0 || fn < 0 || fn >= V_COUNT) return fail(MCG_ERR_INVALID, "bad arguments");
+    if (n_in != V_SHAPE[fn][0] || n_params != V_SHAPE[fn][1] || (n_params > 0 && !params))
+        return fail(MCG_ERR_INVALID, "fn %d takes %d doubles per element and %d parameters", fn, V_SHAPE[fn][0], V_SHAPE[fn][1]);
+    if (n > (int64_t)1 << 24) return fail(MCG_ERR_INVALID, "at most 2^24 elements");
+    DebugVArgs a;
+    a.fn = fn;
+    a.n_in = n_in;
+    a.n = n;
+    for (int k = 0; k < V_MAX_PARAMS; ++k) a.p[k] = k < n_params ? params[k] : 0.0;
+    a.scale = fn == V_NEG2LOG_SCALED ? a.p[0] : a.p[0] * a.p[0];
+    a.ls = fm::make_log_scale(a.scale);
+    if (fn == V_QE_STEP) {
+        const double k0 = a.p[8], k1 = a.p[9], block = a.p[10], elem = a.p[11];
+        if (!(k0 >= 0.0 && k0 < 0x1p32 && k1 >= 0.0 && k1 < 0x1p32 && block >= 0.0 && block < 0x1p32 && elem >= 0.0 && elem <= 3.0))
+            return fail(MCG_ERR_INVALID, "k0, k1, block must be 32-bit words and elem 0..3");
+    }
+    if (n == 0) return MCG_OK;
+    MCG_HIP(hipSetDevice(ctx->device));
+    double *dx = nullptr, *dy = nullptr;
+    MCG_HIP(hipMalloc((void**)&dx, (size_t)n * n_in * sizeof(double)));
+    if (hipMalloc((void**)&dy, (size_t)n * 4 * sizeof(double)) != hipSuccess) {
+        (void)hipFree(dx);
+        return fail(MCG_ERR_OOM, "hipMalloc failed");
+    }
+    a.x = dx;
+    a.y = dy;
+    a.gtab = (const double2*)ctx->log_tab;
+    a.sincos2 = (const double2*)ctx->sincos2_tab;
+    int rc = MCG_OK;
+    if (hipMemcpyAsync(dx, x, (size_t)n * n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = fail(MCG_ERR_HIP, "H2D failed");
+    if (rc == MCG_OK) {
+        if (fn == V_QE_STEP)
+            hipLaunchKernelGGL(k_debug_qe_step, dim3((unsigned)((n + 511) / 512)), dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL(k_debug_eval_v, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
+        if (hipMemcpyAsync(y, dy, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            rc = fail(MCG_ERR_HIP, "debug eval failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    (void)hipFree(dx);
+    (void)hipFree(dy);
+    return rc;
+}
 
 extern "C" int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n) {
     using namespace mcg;
-    if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 10) return fail(MCG_ERR_INVALID, "bad arguments");
+    if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 15) return fail(MCG_ERR_INVALID, "bad arguments");
     if (n == 0) return MCG_OK;
     MCG_HIP(hipSetDevice(ctx->device));
     double *dx = nullptr, *dy = nullptr;

@@ -608,6 +608,19 @@ class PathEngine:
                                      y.ctypes.data_as(C.POINTER(C.c_double)), len(x)))
         return y
 
+    def debug_eval_v(self, fn: int, x: np.ndarray, params=()) -> np.ndarray:
+        """Test hook (mcg_debug_eval_v): one device routine with several inputs per element (x: [n][n_in]) and parameters
+        shared by the launch; returns [n][4]."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x.reshape(-1, 1)
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+        y = np.empty((x.shape[0], 4), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self._L.mcg_debug_eval_v(self._ctx, int(fn), x.ctypes.data_as(dp), x.shape[1], p.ctypes.data_as(dp), len(p),
+                                       y.ctypes.data_as(dp), x.shape[0]))
+        return y
+
     def debug_gbm_route(self, route: int = -1) -> int:
         """Test hook (mcg_debug_gbm_route): 0 = the generators choose their kernel by size, 1 = the narrow kernel, 2 = the
         wide one, -1 = unchanged; returns what the last GBM launch took (1 or 2; 0: none yet)."""

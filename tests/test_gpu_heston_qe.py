@@ -9,7 +9,23 @@ observed on an MI355X over all cases of this file (observed: S 7.88e-14, v 5.74e
 Feller-violating shape), far inside the 1e-9 they may not
 exceed.  The cases are test_heston_qe_reference.QE_PARITY_SETS, where every draw keeps a distance of 1e-9 from both branch
 decisions of the scheme and the reference's own rounding error is held to 1e-11.
-The fused payoff, the consumers and the exotics keep the bounds of the Euler file (test_gpu_heston.py)."""
+The fused payoff, the consumers and the exotics keep the bounds of the Euler file (test_gpu_heston.py).
+
+One step on its own (mcg_debug_eval_v fn 8: HestonQe::step as the kernels call it, two paths per lane) is compared with the step
+of include/mcgpu.h in mpmath, test_heston_qe_reference.qe_step_mp, on the cases of step_cases.  Its three bars are 1.5 times the
+largest error observed on an MI355X:
+  STEP_V_BAR_IN_M  v' in units of m, the step's conditional mean: observed 1.912e-10 (theta = 0, v = 1.3e-8, psi = 5e5, u next
+                   to p).  The exponential branch dominates it: v' = ln(1 / y) / beta with y = (1 - u) / (1 - p) rounded next
+                   to 1, so an ulp of y is an ulp of 1 / beta = m (psi + 1) / 2, and psi has no upper end.  In the quadratic branch
+                   and at psi of order one the cancellation in m = theta + (v - theta) E dominates (4.3e-13 at v = 5e-8,
+                   theta = 0.04, daily steps: half an ulp of theta is 2e-14 of that m, doubled by ln(1 / m^2)).
+  STEP_V_BAR       v' on the scale that takes both out (qe_step_mp: (m or 1 / beta, plus v') x max(1, theta / m)): observed
+                   4.234e-16, two ulps -- the bar that would notice a lost Newton step or a wrong coefficient.
+  STEP_S_BAR       S' relatively, in units of the size of its exponent's terms (1 + |drift| + |K1 v| + |K2 v'| + |sqrt z1|):
+                   observed 8.966e-16 -- the 2 ulp of the exponential and an ulp per term; K2 times the error of v' is below
+                   1e-16 in every case.
+(Before HestonQe::constants took m = v at kappa = 0, that corner had v' off by 6.8e-5 m and S' by 2.2e-12 at v = 1.8e-8,
+theta = 0.04.)"""
 import math
 
 import numpy as np
@@ -19,7 +35,8 @@ import montecarlooptionspricer_amd as mc
 from montecarlooptionspricer_amd import _native as N
 from test_exotics_reference import stats_numpy
 from test_gpu_exotics import check_prices, full_book
-from test_heston_qe_reference import QE_PARITY_SETS, STAT_PATHS, STAT_ROWS, heston_qe_numpy, stat_cases
+from test_heston_qe_reference import (QE_PARITY_SETS, STAT_PATHS, STAT_ROWS, STEP_BLOCK, STEP_ELEM, STEP_MARGIN, STEP_SEED,
+                                      STEP_SETS, heston_qe_numpy, stat_cases, step_constants, step_reference)
 from test_heston_reference import (FELLER_VIOLATING, PARAMS, R, S0, SEED64, STAT_SEED, STD_ERRORS, STRIKES,
                                    heston_closed_form)
 
@@ -27,6 +44,10 @@ pytestmark = pytest.mark.gpu
 
 S_BOUND = 7.9e-13
 V_BOUND = 5.8e-12
+STEP_V_BAR_IN_M = 1.5 * 1.912e-10
+STEP_V_BAR = 1.5 * 4.234e-16
+STEP_S_BAR = 1.5 * 8.966e-16
+V_QE_STEP = 8
 DT = 1.0 / 252.0
 observed = {"S": 0.0, "v": 0.0}
 
@@ -108,6 +129,85 @@ def test_parity_with_numpy(eng, name):
                                   (name, n_steps, n_paths, begin, want_variance, payoff))
         if name == "feller-violating" and n_paths >= 257 and n_steps >= 8:
             assert (gv == 0.0).any()                     # the exponential branch and its mass at zero, in the short shapes too
+
+
+def qe_step(eng, name, cases):
+    """[n][3] (v', S', exponential?) of HestonQe::step on cases [n][>= 5] (v, z1, z2, S, path id) of one parameter set."""
+    p, dt = STEP_SETS[name]
+    params = step_constants(p, dt) + (STEP_SEED & 0xFFFFFFFF, STEP_SEED >> 32, STEP_BLOCK, STEP_ELEM)
+    return eng.debug_eval_v(V_QE_STEP, np.ascontiguousarray(cases[:, :5]), params)[:, :3]
+
+
+step_observed = {"v in m": 0.0, "v": 0.0, "S": 0.0}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report_steps():
+    yield
+    print("\nlargest errors of one step against mpmath in this run: " + ", ".join(f"{k} {v:.3e}" for k, v in step_observed.items()))
+
+
+@pytest.mark.parametrize("name", list(STEP_SETS))
+def test_one_step_against_mpmath(eng, name):
+    import mpmath as mp
+    cases, ref = step_reference(name)
+    got = qe_step(eng, name, cases)
+    assert np.isfinite(got).all() and (got[:, 0] >= 0.0).all() and (got[:, 1] > 0.0).all()        # (c): every case has m >= 0
+    worst = {"v in m": 0.0, "v": 0.0, "S": 0.0}
+    at = {}
+    for row, (gv, gs, gflag), (vn, Sn, exponential, m, margin, v_scale, e_size) in zip(cases, got, ref):
+        if margin < STEP_MARGIN:                           # (at most STEP_LEFT_OUT of all cases: asserted in the reference's file)
+            continue
+        assert bool(gflag) == exponential, row                                                      # (a)
+        err = {"S": float(abs(mp.mpf(gs) / Sn - 1) / e_size)}
+        if m == 0 or vn == 0:
+            assert gv == 0.0, row
+        else:
+            dv = abs(mp.mpf(gv) - vn)
+            err["v in m"], err["v"] = float(dv / m), float(dv / v_scale)
+        for k, e in err.items():
+            if e > worst[k]:
+                worst[k], at[k] = e, (row[0], float(m), exponential)
+    print(f"{name}: " + ", ".join(f"{k} {worst[k]:.3e} at (v, m, exponential) = {at.get(k)}" for k in worst))
+    for k in worst:
+        step_observed[k] = max(step_observed[k], worst[k])
+    assert worst["v in m"] <= STEP_V_BAR_IN_M and worst["v"] <= STEP_V_BAR and worst["S"] <= STEP_S_BAR, (name, worst)   # (b)
+
+
+def test_one_step_does_not_depend_on_the_wave(eng):
+    """A wave enters the exponential branch when one of its lanes needs it.  Whole waves (128 elements: 64 lanes of two paths) of
+    quadratic elements, of exponential elements, and the quadratic wave with a single exponential element: every element keeps
+    its bits, the quadratic lane-mate of the exponential element included."""
+    name = "violating-eighth"
+    cases, ref = step_reference(name)
+    clear = np.array([r[4] >= STEP_MARGIN for r in ref])
+    expo = np.array([r[2] for r in ref])
+    Q, X = cases[clear & ~expo][:128], cases[clear & expo][:128]
+    assert len(Q) == len(X) == 128
+    q, x = qe_step(eng, name, Q), qe_step(eng, name, X)
+    assert (q[:, 2] == 0.0).all() and (x[:, 2] == 1.0).all()
+    mixed = Q.copy()
+    mixed[37] = X[0]
+    want = q.copy()
+    want[37] = x[0]
+    assert bits(qe_step(eng, name, mixed)) == bits(want)
+    assert bits(qe_step(eng, name, np.concatenate([Q, X, Q[:5]]))) == bits(np.concatenate([q, x, q[:5]]))
+    everything = qe_step(eng, name, cases)
+    assert bits(everything[clear & ~expo][:128]) == bits(q) and bits(everything[clear & expo][:128]) == bits(x)
+
+
+def test_with_kappa_zero_the_level_does_not_enter(eng):
+    """kappa = 0: no constant of the scheme depends on theta, and m = v exactly (HestonQe::constants) -- formed as theta + (v - theta)
+    it would round at the size of theta and move S by 1e-12 a step where v << theta.  (v0 = 0.01: psi = 0.7 at the first step, so
+    every path has a positive variance for that rounding to act on.)"""
+    a = dict(S0=S0, r=R, dt=1.0 / 52.0, n_steps=9, scheme="qe", v0=0.01, kappa=0.0, sigma_v=0.6, rho=-0.7)
+    out = []
+    for theta in (0.0, 0.04, 4.0):
+        P, V = eng.heston(SEED64, n_paths=1000, want_variance=True, theta=theta, **a)
+        out.append((bits(P.to_host_step_major()), bits(V.to_host_step_major())))
+        P.free()
+        V.free()
+    assert out[0] == out[1] == out[2]
 
 
 def test_sharding_and_determinism(eng):

@@ -2,6 +2,7 @@
 mpmath (50 digits).  Bar: <= 2 ulp for exp / sqrt, <= 3.5e-16 absolute for sin/cos, <= 4 ulp for -2 ln u
 (table + cancellation next to u = 1), and the fast normal pair within 1e-14 absolute of the RNG contract evaluated in
 high precision."""
+import math
 import struct
 
 import mpmath as mp
@@ -127,3 +128,263 @@ def test_normal_quad_fast_matches_contract(eng):
             r = mp.sqrt(-2 * mp.log(u))
             assert abs(mp.mpf(fast[i, 2 * h]) - r * mp.cos(2 * mp.pi * f)) < mp.mpf("4e-15")
             assert abs(mp.mpf(fast[i, 2 * h + 1]) - r * mp.sin(2 * mp.pi * f)) < mp.mpf("4e-15")
+
+
+# ---- the routines of the later kernels (mcg_debug_eval fn 11..15 and mcg_debug_eval_v) ---------------------------------------
+# A bar that the code does not state is 1.5 times the worst error observed on an MI355X, written beside it.
+V_QE_RCP, V_QE_DIV, V_RADIUS, V_NEG2LOG_SCALED, V_BM_AFFINE, V_BM_AFFINE_SCALED, V_BM_AFFINE2, V_BM_AFFINE_SCALED2 = range(8)
+EXP_INPUTS_SEED = 0
+
+
+def exp_inputs():
+    """The inputs of test_scaled_exp; the last two overflow and underflow."""
+    rs = np.random.RandomState(EXP_INPUTS_SEED)
+    return np.concatenate([rs.uniform(-0.7, 0.7, 3000), rs.uniform(-40, 40, 1000), rs.normal(0, 0.02, 2000),
+                           [0.0, 1e-300, -1e-300, 0.34657359, -0.34657359, 709.0, -740.0, 1000.0, -1000.0]])
+
+
+def bits_equal(a, b):
+    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
+
+
+def test_exp_full(eng):
+    """fm::exp_full (the reduction always on): the polynomial and reduction of scaled_exp, so its bar, <= 2 ulp."""
+    x = exp_inputs()
+    y = eng.debug_eval(11, x)[:, 0]
+    worst = max(ulp_err(yi, mp.e ** mp.mpf(xi)) for xi, yi in zip(x[:-2], y[:-2]))
+    print("exp_full: worst", worst, "ulp")
+    assert worst <= 2.0, worst
+    assert y[-2] == np.inf and y[-1] == 0.0
+
+
+def test_exp_full2_is_exp_full_twice(eng):
+    """Both chains of fm::exp_full2 run exp_full's instruction sequence: the same bits for the same argument."""
+    x = exp_inputs()
+    pair = eng.debug_eval(12, x)
+    assert bits_equal(pair[:, 0], eng.debug_eval(11, x)[:, 0])
+    assert bits_equal(pair[:, 1], eng.debug_eval(11, x + 0.375)[:, 0])      # (the hook forms x + 0.375 in binary64 as well)
+    assert pair[-2, 0] == np.inf and pair[-2, 1] == np.inf and pair[-1, 0] == 0.0 and pair[-1, 1] == 0.0
+
+
+EXPM1_REL_OBSERVED = {13: 4.41, 14: 1.37}       # worst relative error against mpmath expm1, in units of 2^-53
+
+
+def small_exp_inputs(bound, seed):
+    rs = np.random.RandomState(seed)
+    return np.concatenate([rs.uniform(-bound, bound, 2500), rs.normal(0, 0.0126, 2500).clip(-bound, bound),
+                           [0.0, bound, -bound, 5e-324, -5e-324, 1e-300]])
+
+
+@pytest.mark.parametrize("fn, bound", [(13, 0.1), (14, 0.34)])
+def test_expm1_small_pairs(eng, fn, bound):
+    """fm::expm1_small6_2 on |a| <= 0.1 and fm::expm1_small9_2 on |a| <= 0.34 (the rBergomi tiles' price step).  Absolutely, on
+    the scale of what they stand for: <= 2 ulp of e^a, the bar of the exponentials.  Relatively, against mpmath's expm1:
+    observed on an MI355X 4.41 x 2^-53 for expm1_small6_2 (its polynomial is fitted to e^a, and 2^-54.2 of e^a is a larger share
+    of e^a - 1) and 1.37 x 2^-53 for expm1_small9_2; the bar is 1.5 times that.  (Absolutely: 0.42 and 0.39 ulp of e^a.)
+    Both chains give the same bits for the same argument."""
+    x = small_exp_inputs(bound, fn)
+    y = eng.debug_eval(fn, x)
+    back = eng.debug_eval(fn, -x)
+    assert bits_equal(y[:, 0], back[:, 1]) and bits_equal(y[:, 1], back[:, 0])
+    worst_abs, worst_rel = 0.0, 0.0
+    for a, got in zip(np.concatenate([x, -x]), np.concatenate([y[:, 0], y[:, 1]])):
+        want = mp.expm1(mp.mpf(a))
+        err = abs(mp.mpf(got) - want)
+        worst_abs = max(worst_abs, float(err / mp.mpf(np.spacing(float(mp.e ** mp.mpf(a))))))
+        if a != 0.0:
+            worst_rel = max(worst_rel, float(err / abs(want) * 2 ** 53))
+        else:
+            assert got == 0.0
+    print(f"fn {fn}: worst absolute {worst_abs} ulp of e^a, worst relative {worst_rel} x 2^-53")
+    assert worst_abs <= 2.0, worst_abs
+    assert worst_rel <= 1.5 * EXPM1_REL_OBSERVED[fn], worst_rel
+
+
+def test_rbergomi_exponentials_agree_on_their_common_range(eng):
+    """A wave of the rBergomi tiles takes expm1_small6_2, expm1_small9_2 or exp_full2 - 1 by its largest exponent, so on
+    |a| <= 0.1 a path's value depends on its wave neighbours by the difference of the three.  Each is within 2 ulp of e^a of
+    the truth, so any two are within 4 ulp of e^a of each other (observed on an MI355X: 0.875 ulp of e^a, 1.39e-16 absolute --
+    DESIGN.md records it)."""
+    x = small_exp_inputs(0.1, 21)
+    e6, e9, ef = eng.debug_eval(13, x)[:, 0], eng.debug_eval(14, x)[:, 0], eng.debug_eval(12, x)[:, 0] - 1.0
+    ulp = np.spacing(np.exp(x))
+    worst_ulp, worst_abs = 0.0, 0.0
+    for a, b in ((e6, e9), (e6, ef), (e9, ef)):
+        worst_ulp = max(worst_ulp, float(np.max(np.abs(a - b) / ulp)))
+        worst_abs = max(worst_abs, float(np.max(np.abs(a - b))))
+    print(f"the three exponentials on |a| <= 0.1: largest pairwise difference {worst_ulp} ulp of e^a, {worst_abs} absolute")
+    assert worst_ulp <= 4.0, worst_ulp
+
+
+def test_scaled_exp_shortcut_is_bit_identical(eng):
+    """scaled_exp skips its range reduction for a wave whose lanes all have |a| <= 0.34.  The same small arguments in waves
+    that take the shortcut and in waves that one lane of 5.0 sends through the reduction: the same bits."""
+    rs = np.random.RandomState(5)
+    x = np.concatenate([rs.uniform(-0.34, 0.34, 2048), rs.normal(0, 0.02, 2040), [0.34, -0.34, 0.0, 1e-300, -5e-324, 0.1, -0.1, 0.339]])
+    assert len(x) % 64 == 0 and np.max(np.abs(x)) <= 0.34
+    lanes = np.arange(len(x) // 64) * 64 + (np.arange(len(x) // 64) * 7) % 64         # one lane of every wave
+    mixed = x.copy()
+    mixed[lanes] = 5.0
+    small, general = eng.debug_eval(0, x)[:, 0], eng.debug_eval(0, mixed)[:, 0]
+    keep = np.ones(len(x), dtype=bool)
+    keep[lanes] = False
+    assert bits_equal(small[keep], general[keep])
+    assert ulp_err(general[lanes[0]], mp.e ** 5) <= 2.0 and bits_equal(general[lanes], np.full(len(lanes), general[lanes[0]]))
+
+
+def neg2log_inputs():
+    """The u of test_neg2log and the two ends of the 40-bit radius uniform."""
+    rs = np.random.RandomState(1)
+    u = np.concatenate([rs.uniform(0, 1, 4000), 1 - rs.uniform(0, 1, 1500) ** 8, rs.uniform(0, 1, 1500) ** 12,
+                        [2.0 ** -53, 1 - 2.0 ** -53, 0.5, 0.6875, 0.99609375, 0.25, 1.0, 2.0 ** -52 * 1.5, 2.0 ** -41, 1 - 2.0 ** -41]])
+    return u[(u > 0) & (u <= 1)]
+
+
+BENCH_VOL2 = (0.015 * np.sqrt(252.0) * np.sqrt(1.0 / 252.0)) ** 2       # vol^2 of the benchmark's generator, as launch_gbm forms it
+NEG2LOG_SCALED_OBSERVED = 1.73       # worst over the six vol2, in ulp
+
+
+def test_neg2log_scaled(eng):
+    """vol2 (-2 ln u) with vol2 folded into the table and the constants (fm::load_tables_scaled, fm::make_log_scale), against
+    mpmath with vol2 the exact binary64 value.  Observed on an MI355X: worst 1.73 ulp over the six vol2 (the unscaled
+    routine on the same u: 1.39 ulp, so the rounding of the folded constants costs a third of an ulp); the bar is 1.5 times
+    the observed worst.  At vol2 = 1 the constants are those of neg2log and the bits must be too."""
+    u = neg2log_inputs()
+    plain = eng.debug_eval(1, u)[:, 0]
+    exact = [-2 * mp.log(mp.mpf(ui)) for ui in u]
+    plain_worst = max(ulp_err(yi, e) for yi, e in zip(plain, exact))
+    worst = 0.0
+    for vol2 in (1e-10, BENCH_VOL2, 1.6e-4, 0.0833, 1.0, 2.25):
+        y = eng.debug_eval_v(V_NEG2LOG_SCALED, u, [vol2])[:, 0]
+        w = max(ulp_err(yi, mp.mpf(vol2) * e) for yi, e in zip(y, exact))
+        print(f"neg2log_scaled, vol2 = {vol2!r}: worst {w} ulp")
+        worst = max(worst, w)
+        if vol2 == 1.0:
+            assert bits_equal(y, plain)
+    print(f"neg2log_scaled: worst {worst} ulp; neg2log on the same u: {plain_worst} ulp")
+    assert plain_worst <= 4.0
+    assert worst <= 1.5 * NEG2LOG_SCALED_OBSERVED, worst
+
+
+def test_radius_u01_is_exact(eng):
+    """The radius uniform of a pair, ((wb & 0xFF) 2^32 + wa + 1/2) 2^-40, pasted together from the words: exact."""
+    rs = np.random.RandomState(9)
+    wa = np.concatenate([rs.randint(0, 2 ** 32, size=5000, dtype=np.uint64), np.repeat([0, 2 ** 32 - 1, 1 << 20, (1 << 20) - 1, 1 << 31], 6)])
+    wb = np.concatenate([rs.randint(0, 2 ** 32, size=5000, dtype=np.uint64), np.tile([0, 255, 256, 2 ** 32 - 1, 0xFFFFFF00, 0x80], 5)])
+    y = eng.debug_eval_v(V_RADIUS, np.stack([wa, wb], axis=1).astype(np.float64))[:, 0]
+    want = [(2 * (((int(b) & 0xFF) << 32) | int(a)) + 1) / 2.0 ** 41 for a, b in zip(wa, wb)]     # a 41-bit integer: exact
+    assert np.array_equal(y, np.array(want))
+    assert y.min() == 2.0 ** -41 and y.max() == 1 - 2.0 ** -41
+
+
+GBM_MODES = [(3, 0.2, 1.0 / 252.0), (2, 0.015 * math.sqrt(252.0), 1.0 / 252.0), (1, 0.0, 1.0 / 252.0), (0, 1.0, 1.0 / 12.0)]
+
+
+@pytest.fixture(scope="module")
+def pair_words():
+    """[n][2] (wa, wb): both pairs of block 0, stream 0, seed 1 of 5000 paths (as fn 4), and the edge words of
+    test_sincos_table as wb with wa = 0 and 2^32 - 1; and their unit normals (z_even, z_odd) from the RNG contract in mpmath."""
+    from test_heston_reference import philox_words
+    w = philox_words(1, np.arange(5000, dtype=np.uint64), 0, 0)
+    edge = [0, 2 ** 32 - 1, 1 << 29, (1 << 29) - 1, 3 << 29, (5 << 29) + 255, 7 << 29, 1 << 8, 255, 1 << 30, (1 << 30) - 1,
+            1 << 31, (1 << 31) - 1, 3 << 30, (3 << 30) - 1, 1 << 23, (1 << 23) - 1]
+    wa = np.concatenate([w[0], w[2], np.zeros(len(edge), dtype=np.uint64), np.full(len(edge), 2 ** 32 - 1, dtype=np.uint64)])
+    wb = np.concatenate([w[1], w[3], np.array(edge + edge, dtype=np.uint64)])
+    z = []
+    for a, b in zip(wa, wb):
+        u = (mp.mpf(((int(b) & 0xFF) << 32) | int(a)) + mp.mpf(1) / 2) / mp.mpf(2) ** 40
+        c, s = mp.cos_sin(2 * mp.pi * (mp.mpf(int(b) >> 8) + mp.mpf(1) / 2) / mp.mpf(2) ** 24)
+        r = mp.sqrt(-2 * mp.log(u))
+        z.append((r * c, r * s))
+    return np.stack([wa, wb], axis=1).astype(np.float64), z
+
+
+@pytest.mark.parametrize("mode, sigma, dt", GBM_MODES)
+def test_affine_box_muller(eng, pair_words, mode, sigma, dt):
+    """The exponent of a GBM step, drift + vol z, by the four forms of the generators (narrow / wide, vol as a factor / folded
+    into the logarithm) at the (vol, drift) of test_gpu_gbm_wide.py::test_the_four_modes, against the RNG contract in mpmath.
+    Bar: 4e-15 vol (this file's bar for a unit normal in high precision) plus one ulp of the result; observed on an MI355X beyond
+    the ulp: 1.10e-15 vol for the plain forms (narrow and wide alike), 5.3e-16 vol for the folded ones.  The folded forms need
+    vol > 0 (launch_gbm takes them above 1e-100 only) and must stay within two bars of the plain form."""
+    words, z = pair_words
+    drift, vol = (0.04 - 0.5 * sigma * sigma) * dt, sigma * math.sqrt(dt)
+    want = [(mp.mpf(drift) + mp.mpf(vol) * ze, mp.mpf(drift) + mp.mpf(vol) * zo) for ze, zo in z]
+    got = {}
+    for fn in (V_BM_AFFINE, V_BM_AFFINE2) + ((V_BM_AFFINE_SCALED, V_BM_AFFINE_SCALED2) if vol > 0.0 else ()):
+        y = eng.debug_eval_v(fn, words, [vol, drift])[:, :2]
+        got[fn] = y
+        worst, worst_ulp_part = 0.0, 0.0
+        for (ye, yo), (we, wo) in zip(y, want):
+            for g, w in ((ye, we), (yo, wo)):
+                err = float(abs(mp.mpf(g) - w))
+                if vol > 0.0:
+                    over = (err - np.spacing(abs(float(w)))) / vol
+                    if over > worst:
+                        worst, worst_ulp_part = over, np.spacing(abs(float(w))) / vol
+                else:
+                    assert g == drift
+        print(f"mode {mode} form {fn}: worst (error - ulp) / vol = {worst} (the ulp there: {worst_ulp_part} vol)")
+        assert worst <= 4e-15, (fn, worst)
+    if vol > 0.0:
+        bar = 4e-15 * vol + np.spacing(np.abs(got[V_BM_AFFINE]))
+        assert (np.abs(got[V_BM_AFFINE_SCALED] - got[V_BM_AFFINE]) <= 2 * bar).all()
+        assert (np.abs(got[V_BM_AFFINE_SCALED2] - got[V_BM_AFFINE2]) <= 2 * bar).all()
+
+
+QE_RCP_OBSERVED = 0.50               # worst error of qe_rcp in ulp
+
+
+def qe_operands():
+    """[n][2] (numerator, divisor): 10^U(-150, 150) pairs, and what HestonQe::step divides -- 2 m^2 / s2 and m / (1 + b2) -- on
+    the parameter sets of QE_PARITY_SETS with v spread around its level."""
+    from test_heston_qe_reference import QE_PARITY_SETS, qe_constants
+    rs = np.random.RandomState(13)
+    pairs = [np.stack([10.0 ** rs.uniform(-150, 150, 4000), 10.0 ** rs.uniform(-150, 150, 4000)], axis=1)]
+    for p, dt, _ in QE_PARITY_SETS.values():
+        E, c1, c2 = qe_constants(p["kappa"], p["theta"], p["sigma_v"], p["rho"], dt)[:3]
+        v = p["theta"] * np.exp(rs.normal(0, 1.5, 700))
+        m = p["theta"] + (v - p["theta"]) * E
+        s2 = v * c1 + c2
+        pairs.append(np.stack([2 * m * m, s2], axis=1))
+        q = 2 * m * m / s2
+        quad = q >= 4.0 / 3.0
+        b2 = q[quad] - 1 + np.sqrt(q[quad] * (q[quad] - 1))
+        pairs.append(np.stack([m[quad], 1 + b2], axis=1))
+    return np.concatenate(pairs)
+
+
+def test_qe_rcp_and_qe_div(eng):
+    """The reciprocal and the quotient of HestonQe::step on positive normal operands.  qe_div: <= 1 ulp, the code's claim.
+    qe_rcp: observed on an MI355X 0.49995 ulp (two Newton steps from v_rcp_f64 leave the rounding of the last FMA), bar 1.5 times
+    that.  It is below 1 ulp, but qe_div's claim does not rest on that: the correction of the quotient squares the reciprocal's
+    error (with one Newton step taken out qe_rcp is off by 10 ulp and qe_div stays at 0.49997 ulp), so a lost Newton step
+    shows in qe_rcp's bar alone.
+    For a zero or a subnormal divisor both return NaN (v_rcp_f64 gives infinity and the Newton step forms 0 x infinity):
+    observed, not asserted.  HestonQe::step does not get there with m > 0: qe_rcp(m) of a subnormal m has m^2 = 0, where
+    u d <= s2 - m^2 holds and the select takes the mass at zero, never the quotient; qe_div(2 m^2, s2) with s2 below the
+    normal range in the quadratic branch needs sigma_v^2 dt < 1e-150."""
+    nd = qe_operands()
+    assert (nd > 2.3e-308).all() and np.isfinite(nd).all()
+    rcp = eng.debug_eval_v(V_QE_RCP, nd[:, 1])[:, 0]
+    div = eng.debug_eval_v(V_QE_DIV, nd)[:, 0]
+    worst_rcp = max(ulp_err(y, 1 / mp.mpf(d)) for y, d in zip(rcp, nd[:, 1]))
+    worst_div = max(ulp_err(y, mp.mpf(n) / mp.mpf(d)) for y, (n, d) in zip(div, nd))
+    print(f"qe_rcp: worst {worst_rcp} ulp; qe_div: worst {worst_div} ulp")
+    edge = np.array([[1.0, 0.0], [1.0, 5e-324], [1.0, 1e-310]])
+    print("zero and subnormal divisors: qe_rcp", eng.debug_eval_v(V_QE_RCP, edge[:, 1])[:, 0], "qe_div", eng.debug_eval_v(V_QE_DIV, edge)[:, 0])
+    assert worst_div <= 1.0, worst_div
+    assert worst_rcp <= 1.5 * QE_RCP_OBSERVED, worst_rcp
+
+
+def test_sqrt_nonneg(eng):
+    """sqrt_nonneg of the Heston steps: 0 at and below zero, the root of 2^-1000 for a positive x below 2^-1000 (as
+    documented), <= 1 ulp elsewhere."""
+    rs = np.random.RandomState(2)
+    low = np.array([0.0, -0.0, -1e-300, -1.0, 5e-324, 2.0 ** -1001, 2.0 ** -1000, 2.0 ** -999])
+    x = np.concatenate([low, rs.uniform(0, 80, 4000), 10.0 ** rs.uniform(-16, 2, 2000), [2.2e-16, 73.5, 1.0, 4.0]])
+    y = eng.debug_eval(15, x)[:, 0]
+    assert (y[:4] == 0.0).all() and not np.signbit(y[:4]).any()
+    assert y[4] == y[5] == y[6] and ulp_err(y[6], mp.mpf(2) ** -500) <= 1.0
+    worst = max(ulp_err(yi, mp.sqrt(mp.mpf(xi))) for xi, yi in zip(x[6:], y[6:]))
+    print("sqrt_nonneg: worst", worst, "ulp")
+    assert worst <= 1.0, worst

@@ -62,7 +62,7 @@ def heston_qe_numpy(seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, n_steps, n_
             q1, q2 = normal_quad(seed, path, n >> 2, STREAM_PRICE), normal_quad(seed, path, n >> 2, STREAM_VOL)
             uq = uniforms(seed, path, n >> 2)
         z1, z2, u = q1[n & 3].astype(dtype), q2[n & 3].astype(dtype), uq[n & 3].astype(dtype)
-        m = theta + (v - theta) * E
+        m = theta + (v - theta) * E if kappa > 0.0 else v
         s2 = v * c1 + c2
         with np.errstate(all="ignore"):          # each branch is evaluated for every path and selected below
             psi = s2 / (m * m)
@@ -210,3 +210,162 @@ def test_library_exports_and_rejects_without_a_gpu():
     eng = object.__new__(mc.PathEngine)
     with pytest.raises(ValueError):
         eng.heston(7, 100.0, 0.04, 0.04, 2.0, 0.04, 0.3, -0.7, 1.0 / 252.0, 8, 16, scheme="nonsense")
+
+
+# ---- one QE step in high precision (the yardstick of test_gpu_heston_qe.py::test_one_step_*) --------------------------------
+# The step of include/mcgpu.h evaluated by mpmath at 50 digits from binary64 constants and inputs, on cases built to reach every
+# corner of it.  The scheme has two discontinuities (psi against psi_c, u against p): a case within STEP_MARGIN of one, in the
+# reference's own arithmetic, carries no bound, and at most STEP_LEFT_OUT of the cases may be such.
+STEP_MARGIN = 1e-12
+STEP_LEFT_OUT = 1e-3
+STEP_SEED, STEP_BLOCK, STEP_ELEM = SEED64, 5, 2
+STEP_POOL = 1 << 18             # path ids whose stream-3 uniform the cases choose from
+STEP_SETS = {                   # name -> (model parameters, dt)
+    "feller": (PARAMS["feller"], 1.0 / 252.0),
+    "violating-daily": (FELLER_VIOLATING, 1.0 / 252.0),
+    "violating-eighth": (FELLER_VIOLATING, 1.0 / 8.0),
+    "large-vol": (LARGE_VOL, 1.0 / 12.0),
+    "theta-zero": (dict(FELLER_VIOLATING, theta=0.0), 1.0 / 52.0),
+    "kappa-zero": (dict(FELLER_VIOLATING, kappa=0.0), 1.0 / 52.0),
+    "rho-plus-one": (dict(FELLER_VIOLATING, rho=1.0), 1.0 / 8.0),
+    "rho-minus-one": (dict(PARAMS["mild"], rho=-1.0), 1.0 / 252.0),
+}
+
+
+def step_constants(p, dt, r=R):
+    """The eight HestonQe::Consts {theta, E, c1, c2, drift, K1, K2, K3} in binary64 (theta: 0 where kappa = 0, so that m = v)."""
+    E, c1, c2, K0, K1, K2, K3 = qe_constants(p["kappa"], p["theta"], p["sigma_v"], p["rho"], dt)
+    return (p["theta"] if p["kappa"] > 0.0 else 0.0, E, c1, c2, r * dt + K0, K1, K2, K3)
+
+
+def qe_step_mp(consts, v, z1, z2, S, u):
+    """One step in mpmath.  Returns (v', S', exponential?, m, margin, scale of v', size of the exponent): margin = the smaller
+    relative distance from the decisions the case meets, |s2 - 1.5 m^2| and (exponential branch) |u d - (s2 - m^2)|."""
+    import mpmath as mp
+    theta, E, c1, c2, drift, K1, K2, K3 = (mp.mpf(x) for x in consts)
+    v, z1, z2, S, u = (mp.mpf(x) for x in (v, z1, z2, S, u))
+    with mp.workdps(400):           # (exactly: at v = 1e-300 the sum cancels 300 digits)
+        m = theta + (v - theta) * E
+    m = +m
+    s2, m2 = v * c1 + c2, m * m
+    exponential = m != 0 and s2 > PSI_C * m2
+    margin = abs(s2 - PSI_C * m2) / max(s2, PSI_C * m2) if m != 0 else mp.inf
+    if m == 0:
+        vn = mp.mpf(0)
+    elif exponential:
+        d = s2 + m2
+        margin = min(margin, abs(u * d - (s2 - m2)) / max(u * d, abs(s2 - m2)))
+        vn = mp.mpf(0) if u * d <= s2 - m2 else mp.log(2 * m2 / (d * (1 - u))) * d / (2 * m)     # ln((1 - p) / (1 - u)) / beta
+    else:
+        q = 2 * m2 / s2
+        b2 = q - 1 + mp.sqrt(q * (q - 1))
+        vn = m / (1 + b2) * (mp.sqrt(b2) + z2) ** 2
+    root = mp.sqrt(K3 * (v + vn)) * z1
+    Sn = S * mp.exp(drift + K1 * v + K2 * vn + root)
+    # the scales errors are measured on.  v': the branch's own scale -- m, or 1 / beta = m (psi + 1) / 2, the mean of the
+    # exponential part (its inversion turns a rounding of y next to 1 into that much times the rounding) -- plus v' itself (the
+    # last product rounds at its size: ln(1 / y) reaches 15 where u is next to 1), times the roundings m itself carries: it is
+    # formed as theta + (v - theta) E from terms of size theta, an ulp of theta is theta / m ulps of m, and v' follows m with
+    # a condition number of order one (through m and through psi = s2 / m^2).
+    # S': the terms of the exponent, each rounded at its own size, and 1 for the exponential.
+    v_scale = 0 if m == 0 else (s2 + m2) / (2 * m) if exponential else m
+    m_roundings = 1 if m == 0 else max(1, theta / m)
+    e_size = 1 + abs(drift) + abs(K1 * v) + abs(K2 * vn) + abs(root)
+    return vn, Sn, bool(exponential), m, margin, (v_scale + vn) * m_roundings, e_size
+
+
+_step_pool = {}
+
+
+def step_pool():
+    """(ids sorted by their uniform, the uniforms): stream-3 uniform of element STEP_ELEM of block STEP_BLOCK, seed STEP_SEED."""
+    if not _step_pool:
+        ids = np.arange(STEP_POOL, dtype=np.uint64)
+        u = uniform_of_words(philox_words(STEP_SEED, ids, STEP_BLOCK, STREAM_QE_UNIFORM)[STEP_ELEM])
+        order = np.argsort(u)
+        _step_pool["v"] = (ids[order], u[order])
+    return _step_pool["v"]
+
+
+def path_with_uniform_near(target):
+    ids, u = step_pool()
+    k = min(int(np.searchsorted(u, target)), len(u) - 1)
+    return int(ids[k]), float(u[k])
+
+
+def step_cases(name):
+    """[n][6] (v, z1, z2, S, path id, u) for one parameter set: the listed variances and random ones against random uniforms and
+    against uniforms far below p, near 1 and next to p; for the sets whose psi is monotone in v (theta = 0, kappa = 0: c2 = 0),
+    variances tuned to put p at relative distances 1e-6 .. 1e-16 on either side of u and psi next to psi_c."""
+    p, dt = STEP_SETS[name]
+    theta, E, c1, c2 = step_constants(p, dt)[:4]
+    rs = np.random.RandomState(sum(name.encode()))
+    ids, us = step_pool()
+    rows = []
+
+    def add(v, target_u=None):
+        k = rs.randint(len(ids)) if target_u is None else min(int(np.searchsorted(us, target_u)), len(us) - 1)
+        rows.append((v, rs.normal(), rs.normal(), 100.0 * math.exp(rs.normal(0, 0.3)), float(ids[k]), us[k]))
+
+    listed = [0.0, 1e-300, 1e-200, 1e-12]
+    random_v = np.concatenate([rs.uniform(0, 1, 320), 10.0 ** rs.uniform(-8, 0, 320), max(theta, 0.04) * np.exp(rs.normal(0, 1, 320))])
+    for v in listed * 8 + list(random_v):
+        add(v)
+    for v in listed + list(random_v[::5]):
+        m = theta + (v - theta) * E
+        s2 = v * c1 + c2
+        if m > 0 and s2 > PSI_C * m * m:                    # exponential: uniforms placed relative to p
+            pr = (s2 - m * m) / (s2 + m * m)
+            for t in (1e-9, 0.001 * pr, pr * (1 - 1e-4), pr + (1 - pr) * 1e-4, pr + (1 - pr) * 0.5, 1 - 1e-9):
+                add(v, t)
+    if c2 == 0.0 and name in ("theta-zero", "kappa-zero"):
+        # psi = c1 / (v E'^2) with m = E' v (E' = E for theta = 0, 1 for kappa = 0): p = (psi - 1) / (psi + 1)
+        Em = E if p["theta"] == 0.0 else 1.0
+        for _ in range(12):
+            k = rs.randint(len(ids) // 4, len(ids))        # u in (1/4, 1): p there means psi in (5/3, inf): exponential
+            u = us[k]
+            for delta in (1e-6, -1e-6, 1e-9, -1e-9, 1e-11, -1e-11):
+                pt = u * (1 + delta)
+                if pt < 1:
+                    rows.append((c1 / (Em * Em * (1 + pt) / (1 - pt)), rs.normal(), rs.normal(), 100.0, float(ids[k]), u))
+        k = len(ids) // 2
+        v_at = c1 / (Em * Em * (1 + us[k]) / (1 - us[k]))   # p = u up to rounding: y within an ulp or two of 1
+        for v in (v_at, np.nextafter(v_at, 0), np.nextafter(v_at, 1)):
+            rows.append((v, rs.normal(), rs.normal(), 100.0, float(ids[k]), us[k]))
+        for delta in (1e-6, -1e-6, 1e-9, -1e-9, 1e-11, -1e-11):
+            rows.append((c1 / (Em * Em * PSI_C) * (1 + delta), rs.normal(), rs.normal(), 100.0, float(ids[0]), us[0]))
+        rows.append((c1 / (Em * Em * PSI_C), rs.normal(), rs.normal(), 100.0, float(ids[0]), us[0]))
+    return np.array(rows)
+
+
+_step_reference = {}
+
+
+def step_reference(name):
+    """(cases, mpmath results) of one parameter set, computed once and never written to."""
+    if name not in _step_reference:
+        p, dt = STEP_SETS[name]
+        cases = step_cases(name)
+        consts = step_constants(p, dt)
+        _step_reference[name] = (cases, [qe_step_mp(consts, *row[:4], row[5]) for row in cases])
+    return _step_reference[name]
+
+
+def test_step_cases_reach_every_corner_and_keep_their_margins():
+    total = left_out = 0
+    seen = dict(quadratic=0, exponential=0, zero=0, m_zero=0, K3_zero=0)
+    for name, (p, dt) in STEP_SETS.items():
+        cases, ref = step_reference(name)
+        ids = cases[:, 4].astype(np.uint64)
+        assert np.array_equal(cases[:, 5], uniform_of_words(philox_words(STEP_SEED, ids, STEP_BLOCK, STREAM_QE_UNIFORM)[STEP_ELEM]))
+        for row, (vn, Sn, exponential, m, margin, _, _) in zip(cases, ref):
+            total += 1
+            left_out += margin < STEP_MARGIN
+            assert vn >= 0 and Sn > 0
+            seen["exponential" if exponential else "quadratic"] += 1
+            seen["zero"] += exponential and vn == 0
+            seen["m_zero"] += m == 0
+        seen["K3_zero"] += len(cases) * (step_constants(p, dt)[7] == 0.0)
+    print(f"{total} cases, {left_out} within {STEP_MARGIN:g} of a decision; {seen}")
+    assert all(seen.values()), seen
+    assert 0 < left_out <= STEP_LEFT_OUT * total, (left_out, total)

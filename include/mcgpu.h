@@ -128,7 +128,15 @@ int mcg_paths_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma
 
 /* rBergomi as the reference simulates it (RoughVolatility.cpp:342-364) with explicit parameters.
  * rho is accepted for interface parity; it does not change the law.
- * Paths are generated in pairs: path_begin must be even. */
+ * Paths are generated in pairs: path_begin must be even.
+ * A path's draws depend on (seed, global path id) only, and repeated calls are bit-identical.  Shards: from 17 to 2048 steps a
+ * wavefront picks the exponential of a tile of price steps by the largest exponent |ln(S_{n+1}/S_n)| among ITS paths (up to 0.1,
+ * up to 0.34, beyond), so a shard is promised to reproduce the one-call matrix bit for bit only if it begins at a multiple of
+ * 2 * rb_pairs_per_block(Mz) = 8192 / Mz columns (8 at 2048; Mz = n_steps rounded up to a power of two): the wavefronts are then
+ * the same sets of paths.  A shard that begins at another even column agrees to rounding (1e-15 relative); it has the same bits
+ * as long as every wavefront takes the same exponential in both runs, which is the rule while the exponents stay below 0.1, but no
+ * promise: the unused steps of an unfinished last tile vote too.  Up to 16 and beyond 2048 steps a path is computed on its own and
+ * every split at an even column is bit-identical. */
 int mcg_paths_rbergomi(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, double H,
                        double eta, double rho, double dt, int n_steps, uint64_t path_begin,
                        int64_t n_paths, mcg_paths** out);

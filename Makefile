@@ -16,7 +16,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -ffp-contract=off -Iinclude -Wall -D__HIP_PLAT
 HIP_SRCS  := $(wildcard $(PKG)/csrc/*.hip)
 HOST_SRCS := $(wildcard $(PKG)/host/*.cpp) $(wildcard $(PKG)/csrc/*.cpp)
 OBJS := $(patsubst %,$(OBJDIR)/%.o,$(notdir $(HIP_SRCS) $(HOST_SRCS)))
-HDRS := $(wildcard $(PKG)/csrc/*.hpp) $(wildcard include/*.h) $(wildcard include/mcgpu/*.hpp)
+HDRS := $(wildcard $(PKG)/csrc/*.hpp) $(wildcard $(PKG)/host/*.hpp) $(wildcard include/*.h) $(wildcard include/mcgpu/*.hpp)
 
 all: lib oracle
 

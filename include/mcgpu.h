@@ -60,7 +60,8 @@ enum mcg_kernel {
     MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
     MCG_K_LSM_APPLY = 14, /* mcg_lsm_apply: the forward pass of an exercise policy over a stored matrix */
     MCG_K_LSM_DUAL = 15,  /* mcg_lsm_dual_upper: the nested simulation and the martingale recursion (two launches a batch) */
-    MCG_K_COUNT = 16
+    MCG_K_SOBOL = 16,     /* Sobol' path generation, GBM and local volatility (+ fused payoff partials) */
+    MCG_K_COUNT = 17
 };
 
 const char* mcg_last_error(void);
@@ -367,6 +368,80 @@ int mcg_paths_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double 
 int mcg_paths_localvol_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t,
                               double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
                               uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out);
+
+/* Randomised quasi-Monte Carlo: Sobol' paths with a Brownian bridge, for GBM and local volatility.
+ *
+ * Path `i` (its global id, path_begin + column) is point i of a Sobol' sequence, step by step a pure function of
+ * (table, i) as a Philox draw is one of (seed, i): repeated calls are bit-identical, any split into shards (odd path_begin
+ * included) reproduces the one-call matrix bit for bit, and the matrix is the plain step-major one every pricer takes.
+ * mcg_price_european's std_err on such a matrix is the iid formula and is NOT an error bar of a Sobol' estimate: generate a
+ * few replicates (same seed, replicate = 0, 1, ...), price each, and hand the prices to mcg_rqmc_combine.
+ *
+ * The point set (mcg_sobol_table; host only, no ctx).  Direction numbers: Joe and Kuo's new-joe-kuo-6, the first
+ * MCG_SOBOL_MAX_DIMS dimensions, 32 bits, V[d][b] with its leading digit in bit 31 (b = 0 .. 31).  Point i, dimension d:
+ *     g = i ^ (i >> 1);   x = shift[d] ^ XOR over the set bits b of g of V'[d][b]
+ * With MCG_SOBOL_PLAIN (V' = V, shift = 0) x is scipy's Sobol(d, scramble=False, bits=32) point i times 2^32.
+ * Random words of a scramble: the high 32 bits of successive outputs of ONE SplitMix64 stream per (seed, replicate),
+ *     next(s):  s += 0x9E3779B97F4A7C15;  z = s;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)                  (all mod 2^64)
+ *     h(x) = the output of next() on the state x;      the stream starts from the state  s = h(h(seed) ^ (uint64_t)replicate)
+ * For d = 0 .. n_dims-1 in turn the stream yields 33 words (under MCG_SOBOL_SHIFT too, which uses the first only, so that
+ * both scrambles of a (seed, replicate) share their shifts): shift[d] first, then w_0 .. w_31.
+ *   MCG_SOBOL_SHIFT      V' = V, the digital shift shift[d].
+ *   MCG_SOBOL_LMS_SHIFT  Matousek's linear matrix scramble ahead of the shift: M_j = ((w_j >> (31 - j)) | 1) << (31 - j), i.e.
+ *                        bit 31-j set, random bits above it, zeros below;  bit (31 - j) of V'[d][b] = parity(M_j & V[d][b]).
+ * v_out: n_dims * 32 words, V'[d][b] at v_out[d * 32 + b];  shift_out: n_dims words.
+ *
+ * The normal: u = (x + 0.5) * 2^-32 in (0, 1) and z = Phi^-1(u) by Wichura's AS241 (PPND16) in binary64: with q = u - 0.5,
+ * |q| <= 0.425 takes its central rational in r = 0.180625 - q q times q; otherwise r = sqrt(-log(min(u, 1 - u))) (<= 4.8, so
+ * only the branch r <= 5 exists) takes its rational in r - 1.6, negated for q < 0.  Each polynomial by Horner's rule.
+ *
+ * The bridge (mcg_sobol_bridge; host only): the schedule in dimension order, entry d = {t, l, r, wl, wr, sd} meaning
+ *     B(t) = wl * B(l) + (wr * B(r) + sd * z_d)          B in units of sqrt(dt), B(0) = 0
+ *   bridge = 1: entry 0 is the endpoint {n, 0, 0, 0, 0, sqrt(n)}; then the tree bridge(0, n), where bridge(l, r) stops if
+ *     r - l < 2 and otherwise has the node m = (l + r) / 2 (integer) with parents l and r, wl = (r - m) / (r - l),
+ *     wr = (m - l) / (r - l), sd = sqrt((m - l) (r - m) / (r - l)), and the children bridge(l, m), bridge(m, r).  The nodes
+ *     take the dimensions 1, 2, ... breadth first: level by level, left to right.
+ *   bridge = 0: the identity, entry d = {d + 1, d, d, 1, 0, 1}.
+ * The increment of step t is z_t = B(t + 1) - B(t) under bridge = 1 and z_t itself (dimension t) under bridge = 0.  In units of
+ * sqrt(dt) the map from the n normals to the n increments is orthogonal, so the law of the paths is that of the Philox
+ * generators: only the assignment of the dimensions changes.
+ *
+ * mcg_paths_gbm_sobol: S_{t+1} = S_t * exp(m + s z_t), m = (r - sigma^2 / 2) dt, s = sigma sqrt(dt), the exponent as one fma.
+ * mcg_paths_localvol_sobol: the step of mcg_paths_localvol with z = z_t.  Marks, sums of the _payoff forms and rejections are
+ * those of the Philox namesakes; one launch per call, booked under MCG_K_SOBOL.
+ * Limits (MCG_ERR_INVALID with a message, no launch, *out untouched): a NULL sobol; n_steps outside [1, 1024]; path_begin +
+ * n_paths > 2^32; scramble outside {0, 1, 2}; bridge outside {0, 1}.
+ * Out of scope: the Heston family (how two or three driver streams per step interleave under a bridge is a decision of its
+ * own), the rBergomi, multi-asset and in-register twin generators.
+ *
+ * mcg_rqmc_combine: the mean of n replicate estimates and std(ddof = 1) / sqrt(n); n < 2 (or a NULL argument) is
+ * MCG_ERR_INVALID. */
+#define MCG_SOBOL_MAX_DIMS 1024
+enum mcg_sobol_scramble { MCG_SOBOL_PLAIN = 0, MCG_SOBOL_SHIFT = 1, MCG_SOBOL_LMS_SHIFT = 2 };
+typedef struct {
+    uint64_t seed;
+    uint32_t replicate;
+    int scramble; /* enum mcg_sobol_scramble */
+    int bridge;   /* 0: dimensions in time order, 1: Brownian bridge */
+} mcg_sobol;
+typedef struct {
+    int t, l, r;       /* time index of the node and of its parents */
+    double wl, wr, sd; /* B(t) = wl B(l) + (wr B(r) + sd z) */
+} mcg_bridge_node;
+int mcg_sobol_table(const mcg_sobol* sobol, int n_dims, uint32_t* v_out, uint32_t* shift_out);
+int mcg_sobol_bridge(int n_steps, int bridge, mcg_bridge_node* out /* [n_steps] */);
+int mcg_rqmc_combine(const double* estimates, int n, double* mean, double* std_err);
+int mcg_paths_gbm_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
+                        uint64_t path_begin, int64_t n_paths, mcg_paths** out);
+int mcg_paths_gbm_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
+                               uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out);
+int mcg_paths_localvol_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double q, const double* times, int n_t,
+                             double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin,
+                             int64_t n_paths, mcg_paths** out);
+int mcg_paths_localvol_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double q, const double* times,
+                                    int n_t, double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
+                                    uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out);
 
 /* Upload a host matrix in the reference's layout: row_major[p*n_cols + j], n_cols = n_steps+1. */
 int mcg_paths_from_host(mcg_ctx* ctx, const double* row_major, int64_t n_paths, int n_cols,

@@ -24,7 +24,9 @@ extern "C" {
  * fn 12: y[0], y[1] = e^x, e^(x + 0.375): both chains of fm::exp_full2.
  * fn 13: y[0], y[1] = e^x - 1, e^-x - 1 for |x| <= 0.1: both chains of fm::expm1_small6_2.   fn 14: the same for |x| <= 0.34
  *        (fm::expm1_small9_2).
- * fn 15: y[0] = sqrt_nonneg(x) of the Heston steps: 0 for x <= 0, the root of max(x, 2^-1000) otherwise. */
+ * fn 15: y[0] = sqrt_nonneg(x) of the Heston steps: 0 for x <= 0, the root of max(x, 2^-1000) otherwise.
+ * fn 16: x holds a 32-bit Sobol' coordinate as a double; y[0] = Phi^-1((x + 1/2) 2^-32), the normal of the Sobol' generators
+ *        (sobol_normal: AS241 as include/mcgpu.h states it). */
 int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n);
 /* Test hook: the same for routines with several inputs per element or with wave-uniform parameters.  x holds n_in doubles per
  * element, params n_params doubles for the whole launch (both must be what the fn takes); y has 4n doubles as above.  32-bit

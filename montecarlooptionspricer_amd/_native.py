@@ -15,7 +15,13 @@ KERNEL_NAMES = {K_GBM: "gbm", K_RBERGOMI: "rbergomi", K_PAYOFF: "payoff", K_LSM_
                 K_EXOTIC: "exotic", K_HESTON: "heston", K_MULTI: "multi", K_LOCALVOL: "localvol"}
 K_LSM_APPLY = 14  # mcg_lsm_apply's forward pass (KERNEL_NAMES stays the table of the fourteen spans the bench tools tabulate)
 K_LSM_DUAL = 15   # mcg_lsm_dual_upper's nested simulation and martingale recursion
+K_SOBOL = 16      # the Sobol' generators (mcg_paths_gbm_sobol*, mcg_paths_localvol_sobol*)
 LSM_DUAL_MAX_INNER, LSM_DUAL_MAX_STEPS = 65536, 16384
+
+# Sobol' point sets (include/mcgpu.h): enum mcg_sobol_scramble and the limits
+SOBOL_PLAIN, SOBOL_SHIFT, SOBOL_LMS_SHIFT = range(3)
+SOBOL_SCRAMBLES = {"plain": SOBOL_PLAIN, "shift": SOBOL_SHIFT, "lms": SOBOL_LMS_SHIFT}
+SOBOL_MAX_DIMS = 1024
 
 # LSM exercise policies (include/mcgpu.h): a row is LSM_POLICY_STRIDE doubles, slot 18 its kind
 LSM_POLICY_STRIDE = 20
@@ -39,6 +45,16 @@ C_NONE, C_BASKET, C_BEST_OF, C_WORST_OF = -1, 0, 1, 2
 COMBINE_KINDS = {"basket": C_BASKET, "best_of": C_BEST_OF, "worst_of": C_WORST_OF}
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
+
+
+class SobolSpec(C.Structure):
+    """mcg_sobol (include/mcgpu.h): which scramble of the Sobol' sequence, and whether the dimensions go through a bridge."""
+    _fields_ = [("seed", C.c_uint64), ("replicate", C.c_uint32), ("scramble", C.c_int), ("bridge", C.c_int)]
+
+
+class BridgeNode(C.Structure):
+    """mcg_bridge_node (include/mcgpu.h): one entry of the bridge schedule."""
+    _fields_ = [("t", C.c_int), ("l", C.c_int), ("r", C.c_int), ("wl", C.c_double), ("wr", C.c_double), ("sd", C.c_double)]
 
 
 class Row(C.Structure):
@@ -203,6 +219,15 @@ def load_library():
     L.mcg_localvol_table.argtypes = [dp, C.c_int, C.c_int, dp, C.c_double, C.c_int, dp]
     L.mcg_paths_localvol.argtypes = lv + [C.POINTER(vp)]
     L.mcg_paths_localvol_payoff.argtypes = lv + [C.c_double, C.c_int, C.POINTER(vp)]
+    up = C.POINTER(C.c_uint32)
+    sb = C.POINTER(SobolSpec)
+    L.mcg_sobol_table.argtypes = [sb, C.c_int, up, up]
+    L.mcg_sobol_bridge.argtypes = [C.c_int, C.c_int, C.POINTER(BridgeNode)]
+    L.mcg_rqmc_combine.argtypes = [dp, C.c_int, dp, dp]
+    L.mcg_paths_gbm_sobol.argtypes = [vp, sb, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_int64, C.POINTER(vp)]
+    L.mcg_paths_gbm_sobol_payoff.argtypes = L.mcg_paths_gbm_sobol.argtypes[:-1] + [C.c_double, C.c_int, C.POINTER(vp)]
+    L.mcg_paths_localvol_sobol.argtypes = [vp, sb] + lv[2:] + [C.POINTER(vp)]
+    L.mcg_paths_localvol_sobol_payoff.argtypes = [vp, sb] + lv[2:] + [C.c_double, C.c_int, C.POINTER(vp)]
     L.mcg_paths_from_host.argtypes = [vp, dp, C.c_int64, C.c_int, C.POINTER(vp)]
     L.mcg_paths_to_host.argtypes = [vp, dp]
     L.mcg_paths_to_host_step_major.argtypes = [vp, dp]

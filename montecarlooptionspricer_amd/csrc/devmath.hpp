@@ -30,6 +30,55 @@ __device__ __forceinline__ void normal_quad_ref(uint32_t k0, uint32_t k1, uint64
     }
 }
 
+// z = Phi^-1((x + 1/2) 2^-32) of a 32-bit Sobol' coordinate x, by Wichura's AS241 (PPND16) as include/mcgpu.h states it: the
+// argument lies in [2^-33, 1 - 2^-33], so r = sqrt(-log(min(u, 1 - u))) <= 4.8 and the algorithm's third branch (r > 5) does
+// not exist here.  Horner by fma; log, sqrt and the division are the device library's.
+__device__ __forceinline__ double sobol_normal(uint32_t x) {
+    const double u = ((double)x + 0.5) * 0x1p-32;
+    const double q = u - 0.5;
+    double n, d;  // z = n / d: one division behind both branches (a wave nearly always holds lanes of either)
+    if (__builtin_fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        n = 2.5090809287301226727e+3;
+        d = 5.2264952788528545610e+3;
+        n = __builtin_fma(n, r, 3.3430575583588128105e+4);
+        n = __builtin_fma(n, r, 6.7265770927008700853e+4);
+        n = __builtin_fma(n, r, 4.5921953931549871457e+4);
+        n = __builtin_fma(n, r, 1.3731693765509461125e+4);
+        n = __builtin_fma(n, r, 1.9715909503065514427e+3);
+        n = __builtin_fma(n, r, 1.3314166789178437745e+2);
+        n = __builtin_fma(n, r, 3.3871328727963666080e+0);
+        d = __builtin_fma(d, r, 2.8729085735721942674e+4);
+        d = __builtin_fma(d, r, 3.9307895800092710610e+4);
+        d = __builtin_fma(d, r, 2.1213794301586595867e+4);
+        d = __builtin_fma(d, r, 5.3941960214247511077e+3);
+        d = __builtin_fma(d, r, 6.8718700749205790830e+2);
+        d = __builtin_fma(d, r, 4.2313330701600911252e+1);
+        d = __builtin_fma(d, r, 1.0);
+        n = q * n;
+    } else {
+        const double r = sqrt(-log(q < 0.0 ? u : 1.0 - u)) - 1.6;
+        n = 7.74545014278341407640e-4;
+        d = 1.05075007164441684324e-9;
+        n = __builtin_fma(n, r, 2.27238449892691845833e-2);
+        n = __builtin_fma(n, r, 2.41780725177450611770e-1);
+        n = __builtin_fma(n, r, 1.27045825245236838258e+0);
+        n = __builtin_fma(n, r, 3.64784832476320460504e+0);
+        n = __builtin_fma(n, r, 5.76949722146069140550e+0);
+        n = __builtin_fma(n, r, 4.63033784615654529590e+0);
+        n = __builtin_fma(n, r, 1.42343711074968357734e+0);
+        d = __builtin_fma(d, r, 5.47593808499534494600e-4);
+        d = __builtin_fma(d, r, 1.51986665636164571966e-2);
+        d = __builtin_fma(d, r, 1.48103976427480074590e-1);
+        d = __builtin_fma(d, r, 6.89767334985100004550e-1);
+        d = __builtin_fma(d, r, 1.67638483018380384940e+0);
+        d = __builtin_fma(d, r, 2.05319162663775882187e+0);
+        d = __builtin_fma(d, r, 1.0);
+        n = q < 0.0 ? -n : n;
+    }
+    return n / d;
+}
+
 // include/core/common.h:8-14
 __device__ __forceinline__ double payoff_of(bool is_call, double s, double k) {
     return is_call ? fmax(0.0, s - k) : fmax(0.0, k - s);

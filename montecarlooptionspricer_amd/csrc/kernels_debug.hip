@@ -45,6 +45,15 @@ __global__ __launch_bounds__(256) void k_debug_eval(int fn, const double* x, dou
     for (int e = 0; e < 4; ++e) y[4 * i + e] = z[e];
 }
 
+// fn 16 of mcg_debug_eval, in a kernel of its own (k_debug_eval stays as it is): the normal of the Sobol' generators
+__global__ __launch_bounds__(256) void k_debug_sobol_normal(const double* x, double* y, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    y[4 * i] = sobol_normal((uint32_t)x[i]);
+#pragma unroll
+    for (int e = 1; e < 4; ++e) y[4 * i + e] = 0.0;
+}
+
 // ---- mcg_debug_eval_v: routines with several inputs per element or wave-uniform parameters ----------------------------------
 enum : int {
     V_QE_RCP = 0, V_QE_DIV, V_RADIUS, V_NEG2LOG_SCALED, V_BM_AFFINE, V_BM_AFFINE_SCALED, V_BM_AFFINE2, V_BM_AFFINE_SCALED2,
@@ -205,7 +214,7 @@ extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in,
 
 extern "C" int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n) {
     using namespace mcg;
-    if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 15) return fail(MCG_ERR_INVALID, "bad arguments");
+    if (!ctx || !x || !y || n < 0 || fn < 0 || fn > 16) return fail(MCG_ERR_INVALID, "bad arguments");
     if (n == 0) return MCG_OK;
     MCG_HIP(hipSetDevice(ctx->device));
     double *dx = nullptr, *dy = nullptr;
@@ -218,8 +227,10 @@ extern "C" int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, 
     if (hipMemcpyAsync(dx, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         rc = fail(MCG_ERR_HIP, "H2D failed");
     if (rc == MCG_OK) {
-        hipLaunchKernelGGL(k_debug_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, fn, dx, dy, n,
-                           (const double2*)ctx->log_tab, (const double2*)ctx->sincos2_tab);
+        if (fn == 16) hipLaunchKernelGGL(k_debug_sobol_normal, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, dx, dy, n);
+        else
+            hipLaunchKernelGGL(k_debug_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, fn, dx, dy, n,
+                               (const double2*)ctx->log_tab, (const double2*)ctx->sincos2_tab);
         if (hipMemcpyAsync(y, dy, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess)
             rc = fail(MCG_ERR_HIP, "debug eval failed: %s", hipGetErrorString(hipGetLastError()));

@@ -16,6 +16,7 @@
 // workgroup and stays in L2.
 #include "devmath.hpp"
 #include "fastmath.hpp"
+#include "localvol_device.hpp"
 #include "mcg_internal.hpp"
 #include "paths_device.hpp"
 
@@ -32,36 +33,6 @@ constexpr bool LV_STAGED = false;
 #else
 constexpr bool LV_STAGED = true;
 #endif
-
-struct LocalVolArgs {
-    double* out;            // [n_steps+1][ld] prices
-    int64_t ld;
-    int64_t n_paths;
-    int n_steps;
-    int nx1;                // n_x - 1: entries of a slice
-    uint64_t path_begin;
-    uint32_t k0, k1;        // Philox key = seed
-    double S0;
-    double inv_dx, u0, m;   // LocalVolScalars
-    double u_max;           // (double)(n_x - 1)
-    const double2* surf;    // [n_slices][nx1] {a_j, d_j}
-    double K;
-    int is_call;
-    double* partials;       // [gridDim.x][2]
-    const double2* tabs;    // fm::Tables on the device
-};
-
-// One step of the contract from the slice `sl` (LDS) and the draw z.
-__device__ __forceinline__ void localvol_step(const LocalVolArgs& a, const double2* sl, double z, double& S, double& X) {
-    const double u = __builtin_fmin(__builtin_fmax(__builtin_fma(X, a.inv_dx, a.u0), 0.0), a.u_max);
-    const int j = min((int)u, a.nx1 - 1);
-    const double f = u - (double)j;
-    const double2 ad = sl[j];
-    const double s = __builtin_fma(f, ad.y, ad.x);
-    const double e = __builtin_fma(s, z, __builtin_fma(-0.5 * s, s, a.m));
-    X = X + e;
-    S = fm::scaled_exp(S, e);
-}
 
 template <bool PAYOFF, bool ONE_SLICE>
 __global__ __launch_bounds__(256) void k_localvol_paths(LocalVolArgs a) {

@@ -353,16 +353,22 @@ static int check_gen_args(mcg_ctx* ctx, double S0, double dt, int n_steps, int64
     return MCG_OK;
 }
 
+// sobol: null for the Philox stream `seed`, otherwise the Sobol' point set (kernels_sobol.hip) and `seed` is unused
 static int gen_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma, double dt, int n_steps,
-                   uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call, mcg_paths** out) {
-    int rc = check_gen_args(ctx, S0, dt, n_steps, n_paths, out);
+                   uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call, mcg_paths** out,
+                   const mcg_sobol* sobol = nullptr, bool is_sobol = false) {
+    int rc = is_sobol ? sobol_check_shape(sobol, n_steps, path_begin, n_paths) : MCG_OK;
+    if (rc) return rc;
+    rc = check_gen_args(ctx, S0, dt, n_steps, n_paths, out);
     if (rc) return rc;
     if (!(sigma >= 0.0)) return fail(MCG_ERR_INVALID, "sigma must be >= 0");
     mcg_paths* P = nullptr;
     rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
     if (rc) return rc;
     if (n_paths > 0) {
-        rc = launch_gbm(ctx, P, seed, S0, r, sigma, dt, payoff, K, is_call);
+        rc = is_sobol ? launch_sobol(ctx, P, sobol, S0, (r - 0.5 * sigma * sigma) * dt, sigma * std::sqrt(dt), nullptr, 0, nullptr, 0,
+                                     payoff, K, is_call)
+                      : launch_gbm(ctx, P, seed, S0, r, sigma, dt, payoff, K, is_call);
         if (rc) {
             mcg_paths_free(P);
             return rc;
@@ -381,6 +387,16 @@ int mcg_paths_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma
 int mcg_paths_gbm_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma, double dt, int n_steps,
                          uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
     return gen_gbm(ctx, seed, S0, r, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call, out);
+}
+
+int mcg_paths_gbm_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
+                        uint64_t path_begin, int64_t n_paths, mcg_paths** out) {
+    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out, sobol, true);
+}
+
+int mcg_paths_gbm_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
+                               uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
+    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call, out, sobol, true);
 }
 
 static int gen_rb(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, double H, double eta, double rho,
@@ -645,11 +661,13 @@ int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets
 // ---- local volatility ------------------------------------------------------------------------------
 static int gen_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
                         double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
-                        bool payoff, double K, int is_call, mcg_paths** out) {
+                        bool payoff, double K, int is_call, mcg_paths** out, const mcg_sobol* sobol = nullptr, bool is_sobol = false) {
     // (the model is checked before the ctx: what is wrong with a surface is reported on a machine without a GPU too)
     if (!out) return fail(MCG_ERR_INVALID, "local vol: out is NULL");
+    int rc = is_sobol ? sobol_check_shape(sobol, n_steps, path_begin, n_paths) : MCG_OK;
+    if (rc) return rc;
     *out = nullptr;
-    int rc = localvol_check_surface(times, n_t, n_x, sigma, dt, n_steps);
+    rc = localvol_check_surface(times, n_t, n_x, sigma, dt, n_steps);
     if (rc) return rc;
     rc = localvol_check_model(S0, r, q, x_min, x_max, payoff, K);
     if (rc) return rc;
@@ -663,8 +681,9 @@ static int gen_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double
         const int n_slices = n_t == 1 ? 1 : n_steps;
         std::vector<double> table((size_t)n_slices * (size_t)(n_x - 1) * 2);
         localvol_fill_table(times, n_t, n_x, sigma, dt, n_steps, table.data());
-        rc = launch_localvol(ctx, P, seed, S0, localvol_scalars(r, q, x_min, x_max, n_x, dt), n_x, table.data(), n_slices, payoff, K,
-                             is_call);
+        const LocalVolScalars c = localvol_scalars(r, q, x_min, x_max, n_x, dt);
+        rc = is_sobol ? launch_sobol(ctx, P, sobol, S0, 0.0, 0.0, &c, n_x, table.data(), n_slices, payoff, K, is_call)
+                      : launch_localvol(ctx, P, seed, S0, c, n_x, table.data(), n_slices, payoff, K, is_call);
         if (rc) {
             mcg_paths_free(P);
             return rc;
@@ -686,6 +705,20 @@ int mcg_paths_localvol_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, 
                               uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
     return gen_localvol(ctx, seed, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, true, K,
                         is_call, out);
+}
+
+int mcg_paths_localvol_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double q, const double* times, int n_t,
+                             double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin,
+                             int64_t n_paths, mcg_paths** out) {
+    return gen_localvol(ctx, 0, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out,
+                        sobol, true);
+}
+
+int mcg_paths_localvol_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double q, const double* times,
+                                    int n_t, double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
+                                    uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
+    return gen_localvol(ctx, 0, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call,
+                        out, sobol, true);
 }
 
 // ---- host <-> device ---------------------------------------------------------------------------

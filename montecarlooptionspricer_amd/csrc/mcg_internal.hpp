@@ -242,6 +242,13 @@ struct LocalVolScalars {
 };
 int launch_localvol(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, const LocalVolScalars& c, int n_x, const double* table,
                     int n_slices, bool want_payoff, double K, int is_call);
+// Sobol' paths (kernels_sobol.hip): GBM with gm = (r - sigma^2 / 2) dt and gs = sigma sqrt(dt) when lv is null, otherwise local
+// volatility with launch_localvol's scalars and table.  host/sobol.cpp: what every entry point rejects of an mcg_sobol, and of
+// the shape of a Sobol' matrix (n_steps > 1024, ids beyond 2^32; n_steps < 1 and n_paths < 0 are left to the model's own checks).
+int launch_sobol(mcg_ctx* ctx, mcg_paths* P, const mcg_sobol* sobol, double S0, double gm, double gs, const LocalVolScalars* lv,
+                 int n_x, const double* table, int n_slices, bool want_payoff, double K, int is_call);
+int sobol_check(const mcg_sobol* s);
+int sobol_check_shape(const mcg_sobol* s, int n_steps, uint64_t path_begin, int64_t n_paths);
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);

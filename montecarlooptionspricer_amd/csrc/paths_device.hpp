@@ -4,6 +4,7 @@
 // once
 //   store_pair16      the 16-byte nontemporal row store with its two hazard guards
 //   walk_blocks       the walk over whole Philox blocks and the tail of <= 3 steps
+//   walk_bridge       the depth-first walk over a Brownian bridge of Sobol' dimensions (kernels_sobol.hip)
 //   normal_pairs      Box-Muller on words 0/1 or 2/3 of the lane's Philox blocks
 //   payoff_partials   the terminal-payoff sums of a fused (*_payoff) form
 // and mcg_internal.hpp's launch_blocks the host's share (grid size and shape checks).  A generator supplies its argument
@@ -62,6 +63,51 @@ __device__ __forceinline__ void walk_blocks(const int n_steps, uint32_t& block, 
         if (rest == 3) {
             second();
             step(integral_constant<int, 2>{});
+        }
+    }
+}
+
+// The Brownian bridge of the Sobol' generators (include/mcgpu.h: mcg_sobol_bridge), walked depth first so that the unit
+// intervals [t, t + 1] come out in time order.  The host flattens the walk into one BridgeOp per node, in the order of the
+// walk (kernels_sobol.hip: bridge_program): the node's dimension, its weights, and where the values live.  Only the values
+// of the current node's ancestors are live, one slot per tree level (slot 0 holds B(0) = 0, slot 1 the endpoint B(n), a node
+// of depth k slot k + 2: BRIDGE_SLOTS of them for n <= 1024), kept in LDS because the slot is an index: each lane owns the
+// double2 {path 0, path 1} at slots[slot * 256 + threadIdx.x] and no other lane reads it, so the walk holds no barrier.
+struct BridgeOp {
+    double wl, wr, sd;  // B(t) = wl B(l) + (wr B(r) + sd z)
+    uint32_t dim_t;     // dimension | t << 16
+    uint32_t slots;     // slot of l | slot of r << 4 | slot of t << 8 | emit << 12
+                        //   emit bit 0: [t - 1, t] is a unit interval (l = t - 1), bit 1: so is [t, t + 1] (r = t + 1)
+};
+constexpr int BRIDGE_SLOTS = 12;
+typedef const BridgeOp __attribute__((address_space(4))) * bridge_program;  // wave-uniform reads: scalar loads
+
+// Per op, in this order:
+//   draw(dim, z)   the two paths' normals of that dimension
+//   step(t, dz)    step t (S_t -> S_{t+1}) with the increments dz = B(t + 1) - B(t), for each unit interval the node closes
+// mine: this lane's double2 of slot 0.
+template <class Draw, class Step>
+__device__ __forceinline__ void walk_bridge(const int n_ops, bridge_program prog, double2* mine, Draw&& draw, Step&& step) {
+    mine[0] = make_double2(0.0, 0.0);
+#pragma unroll 1
+    for (int k = 0; k < n_ops; ++k) {
+        const double wl = prog[k].wl, wr = prog[k].wr, sd = prog[k].sd;
+        const uint32_t dim_t = prog[k].dim_t, slots = prog[k].slots;
+        double z[2];
+        draw((int)(dim_t & 0xFFFFu), z);
+        const double2 bl = mine[(slots & 15u) * 256u], br = mine[((slots >> 4) & 15u) * 256u];
+        double2 b;
+        b.x = __builtin_fma(wl, bl.x, __builtin_fma(wr, br.x, sd * z[0]));
+        b.y = __builtin_fma(wl, bl.y, __builtin_fma(wr, br.y, sd * z[1]));
+        mine[((slots >> 8) & 15u) * 256u] = b;
+        const int t = (int)(dim_t >> 16);
+        if (slots & (1u << 12)) {
+            const double dz[2] = {b.x - bl.x, b.y - bl.y};
+            step(t - 1, dz);
+        }
+        if (slots & (2u << 12)) {
+            const double dz[2] = {br.x - b.x, br.y - b.y};
+            step(t, dz);
         }
     }
 }

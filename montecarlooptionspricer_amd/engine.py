@@ -321,6 +321,39 @@ class PathEngine:
             check(self._L.mcg_paths_localvol_payoff(*model, K, int(bool(is_call)), C.byref(h)))
         return PathMatrix(self, h)
 
+    def gbm_sobol(self, sobol: "Sobol", S0: float, r: float, sigma: float, dt: float, n_steps: int, n_paths: int,
+                  path_begin: int = 0, payoff: Optional[Tuple[float, bool]] = None) -> PathMatrix:
+        """GBM paths from a Sobol' point set (mcg_paths_gbm_sobol*): path i is point path_begin + i of `sobol`, one dimension per
+        step (n_steps <= 1024, path_begin + n_paths <= 2^32), the law of gbm() and the same plain matrix for every pricer.
+        price_european's own std_err on it is the iid formula and is NOT an error bar of a Sobol' estimate: generate a few
+        replicates (Sobol(seed, replicate=0, 1, ...)), price each, and take rqmc_combine over the prices."""
+        spec = sobol._spec()
+        h = C.c_void_p()
+        if payoff is None:
+            check(self._L.mcg_paths_gbm_sobol(self._ctx, C.byref(spec), S0, r, sigma, dt, n_steps, path_begin, n_paths, C.byref(h)))
+        else:
+            K, is_call = payoff
+            check(self._L.mcg_paths_gbm_sobol_payoff(self._ctx, C.byref(spec), S0, r, sigma, dt, n_steps, path_begin, n_paths,
+                                                     K, int(bool(is_call)), C.byref(h)))
+        return PathMatrix(self, h)
+
+    def local_vol_sobol(self, sobol: "Sobol", S0: float, r: float, surface: "LocalVolSurface", dt: float, n_steps: int, n_paths: int,
+                        path_begin: int = 0, q: float = 0.0, payoff: Optional[Tuple[float, bool]] = None) -> PathMatrix:
+        """Local-volatility paths from a Sobol' point set (mcg_paths_localvol_sobol*): the step of local_vol() with the normals of
+        `sobol`; limits as gbm_sobol.  price_european's own std_err on it is the iid formula and is NOT an error bar of a Sobol'
+        estimate: the error bar is rqmc_combine over replicates."""
+        dp = C.POINTER(C.c_double)
+        spec = sobol._spec()
+        model = (self._ctx, C.byref(spec), S0, r, q, surface.times.ctypes.data_as(dp), surface.n_t, surface.x_min, surface.x_max,
+                 surface.n_x, surface.sigma.ctypes.data_as(dp), dt, n_steps, path_begin, n_paths)
+        h = C.c_void_p()
+        if payoff is None:
+            check(self._L.mcg_paths_localvol_sobol(*model, C.byref(h)))
+        else:
+            K, is_call = payoff
+            check(self._L.mcg_paths_localvol_sobol_payoff(*model, K, int(bool(is_call)), C.byref(h)))
+        return PathMatrix(self, h)
+
     def from_host(self, row_major: np.ndarray) -> PathMatrix:
         """Upload [n_paths][n_steps+1] (the reference's pricePaths layout)."""
         a = np.ascontiguousarray(row_major, dtype=np.float64)
@@ -767,6 +800,59 @@ def local_vol_table(surface: LocalVolSurface, dt: float, n_steps: int) -> np.nda
     check(L.mcg_localvol_table(surface.times.ctypes.data_as(dp), surface.n_t, surface.n_x, surface.sigma.ctypes.data_as(dp), dt, n_steps,
                                out.ctypes.data_as(dp)))
     return out
+
+
+class Sobol:
+    """A randomised Sobol' point set (mcg_sobol; include/mcgpu.h states every rule): Joe and Kuo's direction numbers with the
+    scramble "plain" (none), "shift" (a digital shift) or "lms" (Matousek's linear matrix scramble and a shift), drawn from
+    (seed, replicate); bridge: the dimensions go through a Brownian bridge (the first ones carry most of the variance) instead
+    of time order.  Replicates of one seed are independent scrambles: price each and combine them with rqmc_combine -- that
+    is the error bar of a Sobol' estimate, not price_european's std_err, which is the iid formula."""
+
+    def __init__(self, seed: int, replicate: int = 0, scramble="lms", bridge: bool = True):
+        self.seed, self.replicate, self.bridge = int(seed), int(replicate), bridge
+        if isinstance(scramble, str):
+            if scramble.lower() not in N.SOBOL_SCRAMBLES:
+                raise McgError(f"unknown scramble {scramble!r}: one of {sorted(N.SOBOL_SCRAMBLES)}", 1)
+            scramble = N.SOBOL_SCRAMBLES[scramble.lower()]
+        self.scramble = int(scramble)  # (an unknown number goes to the library, which rejects it)
+
+    def _spec(self) -> "N.SobolSpec":
+        if not 0 <= self.seed < 2 ** 64 or not 0 <= self.replicate < 2 ** 32:
+            raise McgError("Sobol: seed must fit 64 bits and replicate 32", 1)
+        return N.SobolSpec(self.seed, self.replicate, self.scramble, int(self.bridge))
+
+
+def sobol_table(sobol: Sobol, n_dims: int):
+    """(V, shift) of a point set as the kernels read them (mcg_sobol_table; host only): V [n_dims][32] uint32 direction numbers,
+    scrambled or not, and shift [n_dims]; coordinate d of point i is shift[d] ^ XOR of V[d][b] over the set bits b of i ^ (i >> 1)."""
+    L = N.load_library()
+    v = np.empty((max(int(n_dims), 0), 32), dtype=np.uint32)
+    shift = np.empty(max(int(n_dims), 0), dtype=np.uint32)
+    up = C.POINTER(C.c_uint32)
+    spec = sobol._spec()
+    check(L.mcg_sobol_table(C.byref(spec), int(n_dims), v.ctypes.data_as(up), shift.ctypes.data_as(up)))
+    return v, shift
+
+
+def sobol_bridge(n_steps: int, bridge: bool = True) -> np.ndarray:
+    """The bridge schedule in dimension order (mcg_sobol_bridge; host only): a structured array of n_steps entries with the
+    fields t, l, r, wl, wr, sd -- B(t) = wl B(l) + (wr B(r) + sd z_d), in units of sqrt(dt)."""
+    L = N.load_library()
+    out = (N.BridgeNode * max(int(n_steps), 1))()
+    check(L.mcg_sobol_bridge(int(n_steps), int(bridge), out))
+    dtype = np.dtype([("t", np.int32), ("l", np.int32), ("r", np.int32), ("wl", np.float64), ("wr", np.float64), ("sd", np.float64)])
+    return np.array([(e.t, e.l, e.r, e.wl, e.wr, e.sd) for e in out[:int(n_steps)]], dtype=dtype)
+
+
+def rqmc_combine(estimates) -> Tuple[float, float]:
+    """(mean, standard error) of independent replicate estimates (mcg_rqmc_combine): std(ddof=1) / sqrt(n), n >= 2.  This is
+    the error bar of a Sobol' estimate; price_european's own std_err is the iid formula and does not apply to a Sobol' matrix."""
+    L = N.load_library()
+    e = _vec(estimates)
+    mean, se = C.c_double(), C.c_double()
+    check(L.mcg_rqmc_combine(e.ctypes.data_as(C.POINTER(C.c_double)), e.size, C.byref(mean), C.byref(se)))
+    return mean.value, se.value
 
 
 def make_rows(rows):

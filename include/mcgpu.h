@@ -233,7 +233,10 @@ int mcg_paths_heston_qe_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r,
  * z3 is used only where N > 0; a path's result never depends on whether its neighbours jumped.  Streams 0, 1 and 3 are used
  * exactly as by the base scheme; stream 2 stays the branching-process kernels'.  With L <= 1, 1 - c_15 < 2^-33: no uniform
  * lies above c_15 and the count never reaches a cap.  (The device decides uN > c_k as word > floor(c_k 2^32 - 1/2), which is
- * the same statement: c_k 2^32 - 1/2 is exact in binary64.)
+ * the same statement: c_k 2^32 - 1/2 is exact in binary64.)  Both are tested: the equivalence on the words next to every
+ * threshold and the last threshold at L = 1 in tests/test_bates_reference.py; on the device, words exactly on a threshold
+ * through mcg_paths_bates and every threshold, every count up to the largest (12 at L = 1) and the word 2^32 - 1 through the
+ * hook of include/mcgpu_debug.h (fn 9), in tests/test_gpu_bates.py.
  * scheme: MCG_HESTON_EULER, the step of mcg_paths_heston*, or MCG_HESTON_QE, that of mcg_paths_heston_qe*.
  * Everything else is the contract of mcg_paths_heston*: row n of *out is S_n; var_out may be NULL, otherwise row n of *var_out
  * is v_n; ownership, an odd path_begin, shard and repeat bit-identity, the sums the _payoff form leaves (all-reduced on a ctx

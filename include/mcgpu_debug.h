@@ -41,8 +41,21 @@ int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n);
  * fn 8: one HestonQe::step.  x = {v, z1, z2, S, path id}; params = the scheme's constants {theta, E, c1, c2, drift, K1, K2, K3}
  *       as they stand (not the model's parameters), then {k0, k1, block, elem}: the Philox key and the place of the step's
  *       stream-3 uniform.  A lane takes elements 2j and 2j + 1 as its two paths (the lanes of the last wave beyond n repeat
- *       the last element); y = {v', S', 1 if s2 > 1.5 m^2 (the exponential branch) else 0}. */
+ *       the last element); y = {v', S', 1 if s2 > 1.5 m^2 (the exponential branch) else 0}.
+ * fn 9: the jump count and the jump size of the Bates generators (WithJumps::count and WithJumps::jump of csrc/bates_device.hpp,
+ *       the code the product kernels run) on words the caller chooses.  x = {w0, w1, w2, w3, z3}: the four stream-4 words of a
+ *       path's Philox block and the stream-5 normal of the step asked for; params = {L, mu_j, sigma_j, comp, T[0..15], elem}:
+ *       L = lambda dt (refused outside [0, 1], as by mcg_paths_bates; the count reads the thresholds, not L), the jump
+ *       parameters, comp and the sixteen thresholds as mcg_debug_bates_constants returns them, and the element 0..3 whose jump
+ *       size is returned.  A lane takes elements 2j and 2j + 1 as its two paths and 128 consecutive elements form a wave, as
+ *       in the product; the lanes of the last wave beyond n hold the word 0, which passes no threshold.
+ *       y = {cnt, J}: cnt = N_0 + 2^8 N_1 + 2^16 N_2 + 2^24 N_3, the counts of the four words (N_e = #{k : w_e > T[k]}), and
+ *       J = comp + N_elem mu_j + sigma_j sqrt(N_elem) z3 (comp where N_elem = 0, whatever z3 holds). */
 int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in, const double* params, int n_params, double* y, int64_t n);
+/* Test hook, host-only: the jump constants of mcg_paths_bates* as its launcher derives them (the same function) -- *comp =
+ * -lambda kbar dt and T[k] = floor(min(c_k, 1) 2^32 - 1/2), the word thresholds of the count: uN > c_k <=> word > T[k].  Nothing
+ * is validated: the product's bound lambda dt <= 1 is mcg_paths_bates's. */
+int mcg_debug_bates_constants(double lambda, double mu_j, double sigma_j, double dt, uint32_t T[16], double* comp);
 /* Test hook, host-only: the two tables of fm::sincos_two_level as the contexts upload them, 4096 {cos, sin} pairs each:
  * coarse[i] = (cos, sin)(2 pi i / 4096), fine[j] = (cos, sin)(2 pi (j + 1/2) / 2^24). */
 int mcg_debug_sincos2_tables(double* coarse, double* fine);

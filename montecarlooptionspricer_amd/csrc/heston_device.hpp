@@ -4,7 +4,7 @@
 // Philox streams per path (price driver and volatility driver, philox.hpp), the price row and -- optionally -- the variance
 // row stored per step, and the launcher.
 //
-// A scheme is a struct the kernel holds one object of (heston_schemes.hpp: the two variance schemes; kernels_bates.hip: either
+// A scheme is a struct the kernel holds one object of (heston_schemes.hpp: the two variance schemes; bates_device.hpp: either
 // of them with jumps):
 //   Consts                     what the host derives from the model's parameters (HestonArgs::c; eight doubles for a variance scheme)
 //   new_block(a, i, block, tab)  called once per Philox block, after the draws of its four steps
@@ -47,7 +47,7 @@ __device__ __forceinline__ double sqrt_nonneg(double x) {
 }
 
 // HestonArgs stays the kernel's first and only argument: a scheme may read parts of a.c straight from the kernel's argument
-// block, at offsetof(HestonArgs, c) from its start (kernels_bates.hip: WithJumps::rare); the static_assert there and this note
+// block, at offsetof(HestonArgs, c) from its start (bates_device.hpp: WithJumps::rare); the static_assert there and this note
 // are what holds the two together.
 template <class Scheme, bool PAYOFF, bool VAR>
 __global__ __launch_bounds__(256) void k_heston_paths(HestonArgs<typename Scheme::Consts> a) {

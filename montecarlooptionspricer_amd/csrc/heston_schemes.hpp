@@ -1,6 +1,6 @@
 // The step rules of the Heston path kernel (heston_device.hpp): the full-truncation log-Euler scheme and Andersen's QE
 // scheme, as stated in include/mcgpu.h.  kernels_heston.hip and kernels_heston_qe.hip instantiate the kernel with them as they
-// stand; kernels_bates.hip composes a jump rule onto either.  For that a step finds its scheme's constants through
+// stand; bates_device.hpp composes a jump rule onto either.  For that a step finds its scheme's constants through
 // consts_of (a composed scheme's HestonArgs::c holds them as its part `base`) and takes, optionally, a last argument
 // `plus(p, e)` that returns the exponent the price of path p takes, given the scheme's own e; left out, it is e.
 #pragma once

@@ -1,6 +1,7 @@
 // Test hooks behind mcg_debug_eval and mcg_debug_eval_v: run one routine of fastmath.hpp, philox.hpp or the Heston
-// steps (heston_device.hpp, heston_schemes.hpp) elementwise so that tests can measure its error against mpmath / libm.
-// Not on any product path.
+// steps (heston_device.hpp, heston_schemes.hpp, bates_device.hpp) elementwise so that tests can measure its error against
+// mpmath / libm.  Not on any product path.
+#include "bates_device.hpp"
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "heston_schemes.hpp"
@@ -57,11 +58,11 @@ __global__ __launch_bounds__(256) void k_debug_sobol_normal(const double* x, dou
 // ---- mcg_debug_eval_v: routines with several inputs per element or wave-uniform parameters ----------------------------------
 enum : int {
     V_QE_RCP = 0, V_QE_DIV, V_RADIUS, V_NEG2LOG_SCALED, V_BM_AFFINE, V_BM_AFFINE_SCALED, V_BM_AFFINE2, V_BM_AFFINE_SCALED2,
-    V_QE_STEP, V_COUNT
+    V_QE_STEP, V_BATES_COUNT, V_COUNT
 };
-constexpr int V_MAX_PARAMS = 12;
+constexpr int V_MAX_PARAMS = 12;  // of DebugVArgs (V_BATES_COUNT's travel in its own argument block)
 // {doubles per element, parameters} of each fn
-constexpr int V_SHAPE[V_COUNT][2] = {{1, 0}, {2, 0}, {2, 0}, {1, 1}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {5, 12}};
+constexpr int V_SHAPE[V_COUNT][2] = {{1, 0}, {2, 0}, {2, 0}, {1, 1}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {5, 12}, {5, 5 + JUMP_CAP}};
 
 struct DebugVArgs {
     int fn, n_in;
@@ -163,7 +164,64 @@ __global__ __launch_bounds__(256) void k_debug_qe_step(DebugVArgs a) {
     }
 }
 
+// WithJumps::count and WithJumps::jump of the Bates generators on words the caller chooses.  Both read the thresholds
+// T[2..15], mu_j and sigma_j straight from the kernel's argument block, at the place of c.rare in a HestonArgs that is the
+// kernel's first and only argument (WithJumps::rare computes that address by hand).  So this kernel's first and only argument
+// is that HestonArgs, of WithJumps<HestonEuler> (the count is the same code under either base scheme), and what else the kernel
+// needs travels in fields the jump rule does not read: var = x ([n][5]: w0, w1, w2, w3, z3), out = y ([n][4]), n_paths = n,
+// n_steps = the element 0..3 whose J is asked for.
+using DebugBatesArgs = HestonArgs<WithJumps<HestonEuler>::Consts>;
+
+__global__ __launch_bounds__(256) void k_debug_bates_count(DebugBatesArgs a) {
+    constexpr int PPL = HESTON_PPL;
+    // a lane takes two consecutive elements as its two paths, as in the product.  Every lane of a launched wave runs the count
+    // -- the wave's ballots decide how far up the thresholds it goes -- so a lane past the end holds the word 0 four times,
+    // which passes no threshold, and stores nothing.
+    const int64_t first = ((int64_t)blockIdx.x * 256 + threadIdx.x) * PPL;
+    WithJumps<HestonEuler> s;
+    Philox4 w[PPL];
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        const bool in = first + p < a.n_paths;
+        const double* xi = a.var + (in ? first + p : 0) * 5;
+        w[p].w0 = in ? (uint32_t)xi[0] : 0u;
+        w[p].w1 = in ? (uint32_t)xi[1] : 0u;
+        w[p].w2 = in ? (uint32_t)xi[2] : 0u;
+        w[p].w3 = in ? (uint32_t)xi[3] : 0u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s.z3[p][e] = xi[4];
+        s.cnt[p] = 0u;
+    }
+    s.count(w, a);
+    double J[PPL];
+    switch (a.n_steps) {  // (wave-uniform; the product's element is a constant of its unrolled step)
+        case 0: s.jump(a, 0, J); break;
+        case 1: s.jump(a, 1, J); break;
+        case 2: s.jump(a, 2, J); break;
+        default: s.jump(a, 3, J); break;
+    }
+#pragma unroll
+    for (int p = 0; p < PPL; ++p) {
+        if (first + p >= a.n_paths) continue;
+        double* yi = a.out + 4 * (first + p);
+        yi[0] = (double)s.cnt[p];
+        yi[1] = J[p];
+        yi[2] = 0.0;
+        yi[3] = 0.0;
+    }
+}
+
 }  // namespace mcg
+
+extern "C" int mcg_debug_bates_constants(double lambda, double mu_j, double sigma_j, double dt, uint32_t T[16], double* comp) {
+    using namespace mcg;
+    static_assert(JUMP_CAP == 16, "the header's T[16]");
+    if (!T || !comp) return fail(MCG_ERR_INVALID, "NULL output");
+    uint32_t t[JUMP_CAP];
+    bates_constants(lambda, mu_j, sigma_j, dt, t, *comp);
+    for (int k = 0; k < JUMP_CAP; ++k) T[k] = t[k];
+    return MCG_OK;
+}
 
 extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in, const double* params, int n_params, double* y,
                                 int64_t n) {
@@ -172,6 +230,27 @@ extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in,
     if (n_in != V_SHAPE[fn][0] || n_params != V_SHAPE[fn][1] || (n_params > 0 && !params))
         return fail(MCG_ERR_INVALID, "fn %d takes %d doubles per element and %d parameters", fn, V_SHAPE[fn][0], V_SHAPE[fn][1]);
     if (n > (int64_t)1 << 24) return fail(MCG_ERR_INVALID, "at most 2^24 elements");
+    DebugBatesArgs b = {};
+    if (fn == V_BATES_COUNT) {
+        const auto word = [](double w) { return w >= 0.0 && w < 0x1p32 && w == std::floor(w); };
+        const double L = params[0], elem = params[4 + JUMP_CAP];
+        if (!(L >= 0.0 && L <= 1.0) || !(elem == 0.0 || elem == 1.0 || elem == 2.0 || elem == 3.0))
+            return fail(MCG_ERR_INVALID, "L must lie in [0, 1] and elem be 0..3");
+        b.c.rare.mu_j = params[1];
+        b.c.rare.sigma_j = params[2];
+        b.c.comp = params[3];
+        for (int k = 0; k < JUMP_CAP; ++k) {
+            if (!word(params[4 + k])) return fail(MCG_ERR_INVALID, "threshold %d is no 32-bit word", k);
+            b.c.rare.T[k] = (uint32_t)params[4 + k];
+        }
+        b.c.T0 = b.c.rare.T[0];
+        b.c.T1 = b.c.rare.T[1];
+        b.n_paths = n;
+        b.n_steps = (int)elem;
+        for (int64_t i = 0; i < n; ++i)
+            for (int e = 0; e < 4; ++e)
+                if (!word(x[5 * i + e])) return fail(MCG_ERR_INVALID, "element %lld: word %d is no 32-bit word", (long long)i, e);
+    }
     DebugVArgs a;
     a.fn = fn;
     a.n_in = n_in;
@@ -194,6 +273,8 @@ extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in,
     }
     a.x = dx;
     a.y = dy;
+    b.var = dx;
+    b.out = dy;
     a.gtab = (const double2*)ctx->log_tab;
     a.sincos2 = (const double2*)ctx->sincos2_tab;
     int rc = MCG_OK;
@@ -202,6 +283,8 @@ extern "C" int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in,
     if (rc == MCG_OK) {
         if (fn == V_QE_STEP)
             hipLaunchKernelGGL(k_debug_qe_step, dim3((unsigned)((n + 511) / 512)), dim3(256), 0, ctx->stream, a);
+        else if (fn == V_BATES_COUNT)
+            hipLaunchKernelGGL(k_debug_bates_count, dim3((unsigned)((n + 511) / 512)), dim3(256), 0, ctx->stream, b);
         else hipLaunchKernelGGL(k_debug_eval_v, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, a);
         if (hipMemcpyAsync(y, dy, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
             hipStreamSynchronize(ctx->stream) != hipSuccess)

@@ -1059,6 +1059,15 @@ def rbergomi_spectrum(H: float, eta: float, dt: float, n_steps: int):
     return amp, comp
 
 
+def bates_constants(jump_intensity: float, jump_mean: float, jump_std: float, dt: float):
+    """Test hook, host-only (mcg_debug_bates_constants): (comp, T[16]) as the Bates generators derive them -- the compensator
+    of a step and the sixteen word thresholds of the jump count, as Python ints."""
+    T, comp = (C.c_uint32 * 16)(), C.c_double()
+    check(N.load_library().mcg_debug_bates_constants(float(jump_intensity), float(jump_mean), float(jump_std), float(dt), T,
+                                                    C.byref(comp)))
+    return comp.value, [int(t) for t in T]
+
+
 def sincos2_tables():
     """Test hook, host-only (mcg_debug_sincos2_tables): (coarse[4096][2], fine[4096][2]), the {cos, sin} tables of the wide
     GBM generator's two-level sin/cos."""

@@ -5,9 +5,11 @@ that know nothing of each other (the Heston characteristic function times the ju
 Black-Scholes series); the conditioning of the element-wise cases (a jump count is a discontinuity in uN: a case that sits
 on a threshold cannot carry a bound); the scheme against the closed form; and what the library must answer without a GPU."""
 import ctypes as C
+import functools
 import inspect
 import math
 
+import mpmath as mp
 import numpy as np
 import pytest
 
@@ -35,12 +37,19 @@ def jump_constants(lam, mu_j, sigma_j, dt):
     return -lam * kbar * dt, np.array(c, dtype=np.float64)
 
 
+def jump_thresholds(L):
+    """The sixteen words T_k = floor(min(c_k, 1) 2^32 - 1/2) of lambda dt = L, as ints: uN > c_k <=> word > T_k."""
+    _, c = jump_constants(L, 0.0, 0.0, 1.0)
+    return [int(math.floor(min(float(ck), 1.0) * 2.0 ** 32 - 0.5)) for ck in c]
+
+
 def bates_numpy(seed, S0, r, v0, kappa, theta, sigma_v, rho, lam, mu_j, sigma_j, dt, n_steps, n_paths, path_begin=0, scheme="euler",
                 terminal_only=False, dtype=np.float64, trace=None):
     """The contract of mcg_paths_bates: (S, v), step-major [n_steps + 1][n_paths]; with terminal_only the last rows alone.
     dtype: the arithmetic of the steps (constants, draws and the jump count are binary64 either way).  trace: a dict that
     receives "jumps" ([n_steps][n_paths], the count of every step), "count_margin" (the smallest |uN - c_k| met) and, for
-    the QE scheme, "psi_margin" and "u_margin" as heston_qe_numpy reports them."""
+    the QE scheme, "psi_margin" and "u_margin" as heston_qe_numpy reports them, and "count_margins" ([n_steps][n_paths]: the
+    smallest |uN - c_k| of every step)."""
     assert scheme in ("euler", "qe")
     path = np.uint64(path_begin) + np.arange(n_paths, dtype=np.uint64)
     S, v = np.full(n_paths, S0, dtype=dtype), np.full(n_paths, v0, dtype=dtype)
@@ -55,6 +64,8 @@ def bates_numpy(seed, S0, r, v0, kappa, theta, sigma_v, rho, lam, mu_j, sigma_j,
         Sm, vm = np.empty((n_steps + 1, n_paths), dtype=dtype), np.empty((n_steps + 1, n_paths), dtype=dtype)
         Sm[0], vm[0] = S, v
     t = dict(jumps=np.zeros((n_steps, n_paths), dtype=np.int64), count_margin=math.inf, psi_margin=math.inf, u_margin=math.inf)
+    if trace is not None:
+        t["count_margins"] = np.empty((n_steps, n_paths))
     for n in range(n_steps):
         if n & 3 == 0:
             q1, q2 = normal_quad(seed, path, n >> 2, STREAM_PRICE), normal_quad(seed, path, n >> 2, STREAM_VOL)
@@ -98,7 +109,8 @@ def bates_numpy(seed, S0, r, v0, kappa, theta, sigma_v, rho, lam, mu_j, sigma_j,
             Sm[n + 1], vm[n + 1] = S, v
         if trace is not None:
             t["jumps"][n] = N
-            t["count_margin"] = min(t["count_margin"], float(np.abs(uN[None, :] - cdf[:, None]).min()))
+            t["count_margins"][n] = np.abs(uN[None, :] - cdf[:, None]).min(axis=0)
+            t["count_margin"] = min(t["count_margin"], float(t["count_margins"][n].min()))
     if trace is not None:
         trace.update(t)
     return (S, v) if terminal_only else (Sm, vm)
@@ -159,6 +171,122 @@ STAT_ROWS = (("euler-feller-T0.25-63", "euler", PARAMS["feller"], RARE_JUMPS, 0.
              ("qe-mild-T0.25-8", "qe", PARAMS["mild"], dict(lam=0.5, mu_j=0.1, sigma_j=0.25), 0.25, 8))
 MERTON_ROW = dict(sigma=0.2, T=1.0, n_steps=32, **RARE_JUMPS)
 
+# The count ladder: lambda dt = 1 exactly, where a few thousand paths hold some dozens of steps with 6, 7, 8 and 9 jumps, so that the
+# thresholds of the device's second lazy load (T[6..15]) decide something.  The Euler form runs on Merton's parameters, QE
+# (which needs sigma_v > 0) on the Feller set.  The seeds were picked with this file, among 1..40, for the conditions of
+# test_parity_cases_are_well_conditioned (the margins, LADDER_MOST and LADDER_MANY): at lambda dt = 1 a step has 6 jumps or
+# more with probability 5.9e-4, 46 of the 77825 steps of the two shapes on average, and 8 or more with probability 1.0e-5.
+# Seed 11 gives the first shape 26 such steps and one of 8 jumps, seed 26 the second 35 and one of 9.
+MERTON_BASE = dict(kappa=0.0, theta=0.04, sigma_v=0.0, rho=0.0, v0=0.04)
+LADDER_BASE = {"euler": MERTON_BASE, "qe": PARAMS["feller"]}
+LADDER_JUMPS, LADDER_DT = dict(lam=4.0, mu_j=-0.1, sigma_j=0.15), 0.25
+LADDER_SHAPES = {s: ((7, 4097, 0, 11), (6, 8191, 3, 26)) for s in ("euler", "qe")}
+LADDER_MOST, LADDER_MANY = 8, (6, 50)      # some step has >= 8 jumps; at least 50 steps have >= 6
+LADDER_CASES = [("ladder", "euler"), ("ladder", "qe")]
+
+
+def parity_set(name, scheme):
+    """(Heston parameters, jump parameters, dt, shapes) of an element-wise case."""
+    if name == "ladder":
+        return LADDER_BASE[scheme], LADDER_JUMPS, LADDER_DT, LADDER_SHAPES[scheme]
+    p, j, dt, shapes = BATES_PARITY_SETS[name]
+    return p, j, dt, shapes[scheme]
+
+
+# Words exactly on a threshold.  For k = 0..7 a path whose stream-4 word w of some step lies between T_k(1) and T_k(2^-40) =
+# 2^32 - 1, and the two adjacent binary64 L with T_k(L_lo) = w (w > T_k fails: k jumps) and T_k(L_hi) = w - 1 (k + 1 jumps).
+# dt = 1 makes lambda dt = L exactly.  The launch is 5 steps x 130 paths around the crafted path, which sits once in each of
+# BOUNDARY_COLUMNS (the first column; an odd column of the wave's upper 32 lanes; the last column, an odd one in the second
+# wave), and every other (path, step) of it keeps DECISION_MARGIN.
+BOUNDARY_SEED, BOUNDARY_STEPS, BOUNDARY_PATHS, BOUNDARY_COLUMNS = 11, 5, 130, (0, 65, 129)
+BOUNDARY_JUMPS = dict(mu_j=-0.5, sigma_j=0.1)
+BOUNDARY_KS = {"euler": tuple(range(8)), "qe": (0, 2, 6)}      # QE: the first entry of each of the three threshold loads
+BOUNDARY_DT = {"euler": 1.0, "qe": 1.0}
+
+
+def threshold_pair(k, w):
+    """The adjacent binary64 pair L_lo < L_hi with T_k(L_lo) = w and T_k(L_hi) = w - 1, by bisection (T_k falls as L grows,
+    by at most one word per ulp of L: an ulp of L moves c_k 2^32 by about 1e-7)."""
+    lo, hi = 2.0 ** -40, 1.0
+    assert jump_thresholds(lo)[k] >= w > jump_thresholds(hi)[k]
+    while True:
+        mid = 0.5 * (lo + hi)
+        if mid in (lo, hi):
+            break
+        if jump_thresholds(mid)[k] >= w:
+            lo = mid
+        else:
+            hi = mid
+    assert hi == math.nextafter(lo, 2.0) and jump_thresholds(lo)[k] == w and jump_thresholds(hi)[k] == w - 1, (k, w, lo, hi)
+    return lo, hi
+
+
+def boundary_runs(case, scheme):
+    """The launches of one crafted case: (L, expected count at the crafted place, lambda, dt, path_begin, column)."""
+    dt = BOUNDARY_DT[scheme]
+    for L, count in ((case["L_lo"], case["k"]), (case["L_hi"], case["k"] + 1)):
+        assert (L / dt) * dt == L
+        for column in BOUNDARY_COLUMNS:
+            yield L, count, L / dt, dt, case["path"] - column, column
+
+
+def boundary_check(case, scheme):
+    """None if every launch of the case is as the test needs it, or what is wrong; and the smallest margins met elsewhere."""
+    worst = dict(count=math.inf, psi=math.inf, u=math.inf, own=0.0)
+    wide = np.finfo(np.longdouble).eps < np.finfo(np.float64).eps
+    p = LADDER_BASE[scheme]
+    for L, count, lam, dt, begin, column in boundary_runs(case, scheme):
+        a = dict(S0=S0, r=R, dt=dt, n_steps=BOUNDARY_STEPS, n_paths=BOUNDARY_PATHS, path_begin=begin, scheme=scheme, lam=lam, **p,
+                 **BOUNDARY_JUMPS)
+        t = {}
+        S, v = bates_numpy(BOUNDARY_SEED, trace=t, **a)
+        if t["jumps"][case["step"], column] != count:
+            return f"count {t['jumps'][case['step'], column]} at the crafted place, not {count}", worst
+        others = t["count_margins"].copy()
+        if not others[case["step"], column] < 2.0 ** -32:
+            return "the crafted word is not next to its threshold", worst
+        others[case["step"], column] = math.inf
+        worst["count"] = min(worst["count"], float(others.min()))
+        worst["psi"], worst["u"] = min(worst["psi"], t["psi_margin"]), min(worst["u"], t["u_margin"])
+        if not (np.isfinite(S).all() and (S > 0.0).all()):
+            return "S is not finite and positive", worst
+        if wide:
+            Sl, vl = bates_numpy(BOUNDARY_SEED, dtype=np.longdouble, **a)
+            worst["own"] = max(worst["own"], float(np.abs(S / Sl - 1.0).max()), float(np.abs(v - vl).max()) / max(p["v0"], p["theta"]))
+    if min(worst["count"], worst["psi"], worst["u"]) < DECISION_MARGIN:
+        return "a decision elsewhere in the launch is closer than the margin", worst
+    if worst["own"] > OWN_ERROR_BOUND:
+        return "the reference's own rounding error exceeds its bound", worst
+    return None, worst
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_cases(scheme):
+    """One crafted case per k of BOUNDARY_KS[scheme]: dict(k, path, step, word, L_lo, L_hi, margins), the first path id (from
+    129 on, so that path_begin stays >= 0 in every column; up to 2^16, then up to 2^20) that boundary_check accepts."""
+    found = {}
+    lo_id = BOUNDARY_COLUMNS[-1]
+    for hi_id in (2 ** 16, 2 ** 20):
+        ids = np.arange(lo_id, hi_id + 1, dtype=np.uint64)
+        words = np.stack(list(philox_words(BOUNDARY_SEED, ids, 0, STREAM_JUMP_COUNT)) +
+                         [philox_words(BOUNDARY_SEED, ids, 1, STREAM_JUMP_COUNT)[0]])[:BOUNDARY_STEPS].astype(np.int64)
+        T1 = jump_thresholds(1.0)
+        for k in BOUNDARY_KS[scheme]:
+            if k in found:
+                continue
+            at_id, at_step = np.nonzero(((words > T1[k]) & (words < 2 ** 32 - 1)).T)
+            for i, step in zip(at_id, at_step):
+                w = int(words[step, i])
+                L_lo, L_hi = threshold_pair(k, w)
+                case = dict(k=k, path=int(ids[i]), step=int(step), word=w, L_lo=L_lo, L_hi=L_hi)
+                wrong, case["margins"] = boundary_check(case, scheme)
+                if wrong is None:
+                    found[k] = case
+                    break
+        if len(found) == len(BOUNDARY_KS[scheme]):
+            break
+    return [found[k] for k in BOUNDARY_KS[scheme] if k in found]
+
 
 def stat_cases():
     for name, scheme, p, j, T, n_steps in STAT_ROWS:
@@ -185,6 +313,66 @@ def test_thresholds():
         near = (T[:, None] + np.arange(-3, 4)[None, :]).ravel()
         w = np.concatenate([rng.integers(0, 2 ** 32, 100_000).astype(np.float64), near[(near >= 0) & (near < 2.0 ** 32)]])
         assert np.array_equal(uniform_of_words(w.astype(np.uint64))[None, :] > c[:, None], w[None, :] > T[:, None])
+
+
+THRESHOLD_LS = (0.0, 1e-300, 2.0 ** -40, 0.004, 0.5, 1.0 - 2.0 ** -53, 1.0)
+CDF_OBSERVED = 4.47     # worst error of c_k against mpmath, in units of 2^-53 c_k (at L = 0.98498..., k = 11)
+
+
+def threshold_ls():
+    """THRESHOLD_LS and a few hundred random L, uniform and log-uniform in (0, 1)."""
+    rng = np.random.default_rng(16)
+    return THRESHOLD_LS + tuple(rng.uniform(0.0, 1.0, 200)) + tuple(10.0 ** rng.uniform(-12.0, 0.0, 200))
+
+
+def test_word_thresholds_decide_as_the_uniform_does():
+    """uN > c_k in binary64 <=> word > T_k, on the three words around every threshold: off by one word, or > against >=, at
+    any k fails here.  T rises with k, and at L = 1 the last threshold is the last word: no word gives sixteen jumps."""
+    top = 2 ** 32 - 1
+    for L in threshold_ls():
+        _, c = jump_constants(L, 0.0, 0.0, 1.0)
+        T = jump_thresholds(L)
+        assert len(T) == JUMP_CAP and all(0 <= t <= top for t in T) and all(a <= b for a, b in zip(T, T[1:])), (L, T)
+        for k in range(JUMP_CAP):
+            for w in (T[k] - 1, T[k], T[k] + 1):
+                w = min(max(w, 0), top)
+                assert ((w + 0.5) * 2.0 ** -32 > c[k]) == (w > T[k]), (L, k, w, T[k], c[k])
+    assert jump_thresholds(1.0)[15] == top and jump_thresholds(0.0) == [top] * JUMP_CAP
+    print("thresholds at L = 1:", jump_thresholds(1.0))
+
+
+def test_cdf_against_mpmath():
+    """c_k in binary64 (an exponential and at most fifteen products, quotients and sums of positive terms) against the Poisson
+    CDF of the same binary64 L at 50 digits.  Observed: CDF_OBSERVED x 2^-53 relative; the bound is 1.5 times that."""
+    mp.mp.dps = 50
+    worst, at = 0.0, None
+    for L in threshold_ls():
+        _, c = jump_constants(L, 0.0, 0.0, 1.0)
+        term = total = mp.exp(-mp.mpf(L))
+        for k in range(JUMP_CAP):
+            if k:
+                term = term * mp.mpf(L) / k
+                total += term
+            err = float(abs(mp.mpf(float(c[k])) - total) / total * 2 ** 53)
+            if err > worst:
+                worst, at = err, (L, k)
+    print(f"c_k against mpmath: worst {worst:.3f} x 2^-53 at (L, k) = {at}")
+    assert worst <= 1.5 * CDF_OBSERVED, (worst, at)
+
+
+def test_library_constants_are_the_references():
+    """mcg_debug_bates_constants -- the function the launcher calls -- gives jump_thresholds(lambda dt) and the reference's comp
+    exactly: the library's libm and Python's agree on every exponential a boundary case relies on."""
+    from montecarlooptionspricer_amd.engine import bates_constants
+    for L in threshold_ls():
+        for mu_j, sigma_j in ((-0.1, 0.15), (-0.5, 0.1), (0.05, 0.2), (0.0, 0.0)):
+            comp, T = bates_constants(L, mu_j, sigma_j, 1.0)
+            assert T == jump_thresholds(L), (L, T)
+            want = jump_constants(L, mu_j, sigma_j, 1.0)[0]
+            assert np.float64(comp).tobytes() == np.float64(want).tobytes(), (L, mu_j, sigma_j, comp, want)       # (the zero's sign too)
+    for lam, dt in ((4.0, 0.25), (6.0, 1.0 / 12.0), (1.0, 1.0 / 252.0), (252.0, 1.0 / 252.0)):
+        comp, T = bates_constants(lam, -0.1, 0.15, dt)
+        assert T == jump_thresholds(lam * dt) and comp == jump_constants(lam, -0.1, 0.15, dt)[0], (lam, dt)
 
 
 def test_jump_streams_and_shards():
@@ -243,16 +431,19 @@ def test_closed_form_against_the_merton_series():
     assert abs(call - put - (S0 - 110.0 * math.exp(-R))) <= 1e-10
 
 
-@pytest.mark.parametrize("name, scheme", PARITY_CASES)
+@pytest.mark.parametrize("name, scheme", PARITY_CASES + LADDER_CASES)
 def test_parity_cases_are_well_conditioned(name, scheme):
     """Every element-wise case of the GPU file keeps every uN 1e-9 away from every threshold (and, under QE, the two margins of
     tests/test_heston_qe_reference.py), and the reference's own rounding error on it (binary64 against 80-bit arithmetic on the
-    same draws, S relatively and v on the scale max(v0, theta)) stays below 1e-11."""
+    same draws, S relatively and v on the scale max(v0, theta)) stays below 1e-11.  The shapes of the ladder set hold a step
+    with LADDER_MOST jumps or more and, together, LADDER_MANY[1] steps with LADDER_MANY[0] or more."""
     wide = np.finfo(np.longdouble).eps < np.finfo(np.float64).eps
-    p, j, dt, shapes = BATES_PARITY_SETS[name]
-    shapes = shapes[scheme]
-    assert {s[0] & 3 for s in shapes} == {0, 1, 2, 3} and all(s[1] % 512 for s in shapes)
-    worst, most = 0.0, 0
+    p, j, dt, shapes = parity_set(name, scheme)
+    if name == "ladder":
+        assert j["lam"] * dt == 1.0 and all(s[1] % 512 for s in shapes)
+    else:
+        assert {s[0] & 3 for s in shapes} == {0, 1, 2, 3} and all(s[1] % 512 for s in shapes)
+    worst, most, tally = 0.0, 0, np.zeros(JUMP_CAP + 1, dtype=np.int64)
     for n_steps, n_paths, begin, seed in shapes:
         a = dict(S0=S0, r=R, dt=dt, n_steps=n_steps, n_paths=n_paths, path_begin=begin, scheme=scheme, **p, **j)
         t = {}
@@ -264,14 +455,36 @@ def test_parity_cases_are_well_conditioned(name, scheme):
         assert np.isfinite(S).all() and (S > 0.0).all()
         if name == "frequent" and n_steps == 8:
             assert t["jumps"].max() >= 2, "steps with two jumps and more belong to this set's 8-step shape"
+        tally += np.bincount(t["jumps"].ravel(), minlength=JUMP_CAP + 1)
         if wide:
             Sl, vl = bates_numpy(seed, dtype=np.longdouble, **a)
             es, ev = float(np.abs(S / Sl - 1.0).max()), float(np.abs(v - vl).max()) / max(p["v0"], p["theta"])
             worst = max(worst, es, ev)
             assert es <= OWN_ERROR_BOUND and ev <= OWN_ERROR_BOUND, (name, scheme, n_steps, es, ev)
     print(f"most jumps in a step {most}; the reference against itself in 80-bit arithmetic: {worst:.2e}")
+    if name == "ladder":
+        print(f"steps by count: {dict((n, int(c)) for n, c in enumerate(tally) if c)}")
+        assert most >= LADDER_MOST and tally[LADDER_MANY[0]:].sum() >= LADDER_MANY[1], tally
     if not wide:
         pytest.skip("no wider float than binary64 here: the decision margins hold, the rounding comparison was not made")
+
+
+@pytest.mark.parametrize("scheme", ["euler", "qe"])
+def test_boundary_cases_are_well_conditioned(scheme):
+    """The crafted launches of the GPU file (words exactly on a threshold): one per k, the count at the crafted place k at L_lo
+    and k + 1 at L_hi in every column, every other (path, step) -- and QE's two decisions -- DECISION_MARGIN away, and the
+    reference's own rounding error within its bound."""
+    cases = boundary_cases(scheme)
+    assert [c["k"] for c in cases] == list(BOUNDARY_KS[scheme]), [c["k"] for c in cases]
+    for c in cases:
+        m = c["margins"]
+        print(f"{scheme} k = {c['k']}: path {c['path']}, step {c['step']}, word {c['word']}, L_lo = {c['L_lo']!r}; elsewhere: count "
+              f"margin {m['count']:.2e}, psi margin {m['psi']:.2e}, u margin {m['u']:.2e}; own error {m['own']:.2e}")
+        assert jump_thresholds(1.0)[c["k"]] < c["word"] < 2 ** 32 - 1 and c["path"] <= 2 ** 20
+        assert jump_thresholds(c["L_lo"])[c["k"]] == c["word"] and jump_thresholds(c["L_hi"])[c["k"]] == c["word"] - 1
+        assert c["L_hi"] == math.nextafter(c["L_lo"], 2.0)
+        wrong, _ = boundary_check(c, scheme)
+        assert wrong is None, (c, wrong)
 
 
 @pytest.mark.parametrize("scheme, p, j, T, n_steps", stat_cases())

@@ -10,16 +10,45 @@ observed on an MI355X over all cases of this file, per base scheme (observed: Eu
 shapes; QE S 8.15e-14, v 5.74e-13, both on the 252-step Feller-violating shape), far inside the 1e-9 they may not exceed.
 The cases are test_bates_reference.BATES_PARITY_SETS, where every uniform keeps a distance of 1e-9 from every threshold of
 the jump count (and from QE's two branch decisions) and the reference's own rounding error is held to 1e-11.
-The fused payoff, the consumers and the exotics keep the bounds of the Heston files (test_gpu_heston.py, test_gpu_heston_qe.py)."""
+The fused payoff, the consumers and the exotics keep the bounds of the Heston files (test_gpu_heston.py, test_gpu_heston_qe.py).
+
+The jump count N = #{k : uN > c_k}, which the device decides as word > floor(c_k 2^32 - 1/2) on a ladder of thresholds that a
+wave climbs only as far as one of its lanes passes, is tested at every threshold and every count it can reach:
+  - the "ladder" set (lambda dt = 1; 7 x 4097 and 6 x 8191 paths with steps of 6, 7, 8 and 9 jumps) and launches in which one
+    word lies exactly on threshold k (k = 0..7; QE: 0, 2, 6) at two adjacent lambda dt, on the product path in all its
+    compiled forms.  These carry exponents the older sets never had, so their error is measured apart ("ladder ..." in the
+    report).  Observed on an MI355X: Euler S 1.11e-15, v 0 (Merton's parameters: the variance never moves); QE S 1.11e-15,
+    v 4.86e-15 -- a few steps only, below the bounds above, which therefore hold for them as they stand;
+  - the counts no seed reaches (10..12 at lambda dt = 1 need a word within 1e-9 of 2^32) and the wave-level behaviour of the
+    ladder through mcg_debug_eval_v fn 9, which runs WithJumps::count and WithJumps::jump -- the product's code -- on chosen
+    words: counts as exact integers against the contract's comparison in binary64, J against mpmath (observed: 6.66 ulp of
+    |J| where N mu_J and sigma_J sqrt(N) z3 cancel to a third of their size, inside the four roundings the code makes).
+Mutation check (each in a scratch build, one run of this file on an MI355X; every test that existed before stayed green):
+  (a) `>` becomes `>=` in the count's comparison: caught on the product path (test_words_exactly_on_a_threshold, both schemes:
+      the path on the threshold is off by 36 % at L_lo) and by the hook (test_count_of_every_word_next_to_a_threshold at every
+      L, test_quiet_wave_beside_a_jumping_wave); the ladder set does not see it, as no word of it lies on a threshold;
+  (b) the second lazy load reads T[j + 1] for T[j]: caught on the product path (test_count_ladder_parity_with_numpy, both
+      schemes, by its steps of 7 jumps and more: 15 % in S; test_words_exactly_on_a_threshold at k = 6) and by the hook (three
+      tests).  The second load filling T[6..11] only: caught by the hook alone (counts of 13..16 at the last four words, in
+      test_count_of_every_word_next_to_a_threshold[1.0], test_one_lane_drives_the_ladder and test_jump_size_against_mpmath)
+      -- no seed brings a word within 1e-9 of 2^32, which is why the hook exists;
+  (c) the host takes floor(c_k 2^32) without the half: caught on the product path (test_words_exactly_on_a_threshold, both
+      schemes, at L_hi, where the word must pass the threshold and does not: 56 %), by every hook test through the constants
+      they first compare with the reference's, and without a GPU by test_bates_reference.py::test_library_constants_are_the_references."""
 import math
 
+import mpmath as mp
 import numpy as np
 import pytest
 
 import montecarlooptionspricer_amd as mc
 from montecarlooptionspricer_amd import _native as N
-from test_bates_reference import (BATES_PARITY_SETS, MERTON_ROW, PARITY_CASES, RARE_JUMPS, bates_closed_form, bates_numpy,
-                                  merton_series, stat_cases)
+from montecarlooptionspricer_amd.engine import bates_constants
+from test_bates_reference import (BATES_PARITY_SETS, BOUNDARY_JUMPS, BOUNDARY_KS, BOUNDARY_PATHS, BOUNDARY_SEED, BOUNDARY_STEPS,
+                                  JUMP_CAP, LADDER_BASE, LADDER_CASES, MERTON_ROW, PARITY_CASES, RARE_JUMPS, bates_closed_form,
+                                  bates_numpy, boundary_cases, boundary_runs, jump_constants, jump_thresholds, merton_series,
+                                  parity_set, stat_cases)
+from test_heston_qe_reference import uniform_of_words
 from test_exotics_reference import stats_numpy
 from test_gpu_exotics import check_prices, full_book
 from test_heston_reference import PARAMS, R, S0, SEED64, STAT_SEED, STD_ERRORS, STRIKES
@@ -31,6 +60,9 @@ V_BOUND = {"euler": 7.0e-14, "qe": 5.8e-12}
 DT = 1.0 / 252.0
 STAT_PATHS = 1_000_000
 observed = {"euler S": 0.0, "euler v": 0.0, "qe S": 0.0, "qe v": 0.0}
+# the same over the cases of lambda dt up to 1 (the ladder set and the words on a threshold), which carry exponents the older
+# sets never had: measured apart, held to the same bounds
+observed.update({"ladder " + k: 0.0 for k in list(observed)})
 
 
 @pytest.fixture(scope="module")
@@ -68,7 +100,7 @@ def reference(seed, p, j, dt, n_steps, n_paths, path_begin, scheme, cache={}):
     return cache[key]
 
 
-def check_parity(eng, seed, p, j, dt, n_steps, n_paths, path_begin, scheme, want_variance, payoff, where):
+def check_parity(eng, seed, p, j, dt, n_steps, n_paths, path_begin, scheme, want_variance, payoff, where, tag=""):
     S, v, _ = reference(seed, p, j, dt, n_steps, n_paths, path_begin, scheme)
     got = eng.bates(seed, n_paths=n_paths, path_begin=path_begin, payoff=payoff, want_variance=want_variance,
                     **gen(p, j, dt, n_steps, scheme))
@@ -76,14 +108,14 @@ def check_parity(eng, seed, p, j, dt, n_steps, n_paths, path_begin, scheme, want
     assert (P.n_paths, P.n_steps) == (n_paths, n_steps)
     gs = P.to_host_step_major()
     es = float(np.abs(gs / S - 1.0).max())
-    observed[scheme + " S"] = max(observed[scheme + " S"], es)
+    observed[tag + scheme + " S"] = max(observed[tag + scheme + " S"], es)
     print(f"{where}: S {es:.2e}", end="")
     assert es <= S_BOUND[scheme], (where, "S", es)
     if V is not None:
         assert (V.n_paths, V.n_steps) == (n_paths, n_steps)
         gv = V.to_host_step_major()
         ev = float(np.abs(gv - v).max()) / max(p["v0"], p["theta"])
-        observed[scheme + " v"] = max(observed[scheme + " v"], ev)
+        observed[tag + scheme + " v"] = max(observed[tag + scheme + " v"], ev)
         print(f", v {ev:.2e}", end="")
         assert ev <= V_BOUND[scheme], (where, "v", ev)
         if scheme == "qe":
@@ -113,6 +145,196 @@ def test_parity_with_numpy(eng, name, scheme):
             for payoff in (None, (100.0, (k + want_variance) % 2 == 0)):
                 check_parity(eng, seed, p, j, dt, n_steps, n_paths, begin, scheme, want_variance, payoff,
                              (name, scheme, n_steps, n_paths, begin, want_variance, payoff))
+
+
+@pytest.mark.parametrize("name, scheme", LADDER_CASES)
+def test_count_ladder_parity_with_numpy(eng, name, scheme):
+    """lambda dt = 1: steps with 6, 7, 8 and 9 jumps, so that the thresholds of the second lazy load decide (the older sets reach
+    6 once).  Every compiled form of the kernel."""
+    p, j, dt, shapes = parity_set(name, scheme)
+    for k, (n_steps, n_paths, begin, seed) in enumerate(shapes):
+        assert reference(seed, p, j, dt, n_steps, n_paths, begin, scheme)[2].max() >= 8
+        for want_variance in (False, True):
+            for payoff in (None, (100.0, (k + want_variance) % 2 == 0)):
+                check_parity(eng, seed, p, j, dt, n_steps, n_paths, begin, scheme, want_variance, payoff,
+                             (name, scheme, n_steps, n_paths, begin, want_variance, payoff), tag="ladder ")
+
+
+@pytest.mark.parametrize("scheme", ["euler", "qe"])
+def test_words_exactly_on_a_threshold(eng, scheme):
+    """A stream-4 word w of one path and the two adjacent binary64 lambda dt with T_k = w (w > T_k fails: k jumps) and T_k = w - 1
+    (k + 1 jumps), for every k of BOUNDARY_KS: > against >=, a threshold off by one word or the half left out of the floor
+    moves that path's ln S by mu_J + sigma_J z3 = -0.5 +- 0.1 z3.  The crafted path sits in the first column, in an odd column
+    of the wave's upper lanes and in the last column (an odd one in the second wave); the four forms of the kernel take turns."""
+    p = LADDER_BASE[scheme]
+    cases = boundary_cases(scheme)
+    assert [c["k"] for c in cases] == list(BOUNDARY_KS[scheme])
+    form = 0
+    for c in cases:
+        for L, count, lam, dt, begin, column in boundary_runs(c, scheme):
+            j = dict(lam=lam, **BOUNDARY_JUMPS)
+            counts = reference(BOUNDARY_SEED, p, j, dt, BOUNDARY_STEPS, BOUNDARY_PATHS, begin, scheme)[2]
+            assert counts[c["step"], column] == count, (c, L, column)
+            want_variance, payoff = form & 1 == 1, ((100.0, form & 4 == 0) if form & 2 else None)
+            form += 1
+            check_parity(eng, BOUNDARY_SEED, p, j, dt, BOUNDARY_STEPS, BOUNDARY_PATHS, begin, scheme, want_variance, payoff,
+                         ("threshold", scheme, c["k"], L, column, want_variance, payoff), tag="ladder ")
+
+
+def test_lambda_dt_of_one_is_the_edge(eng):
+    ok = dict(seed=1, S0=100.0, r=0.04, v0=0.04, kappa=2.0, theta=0.04, sigma_v=0.3, rho=-0.7, jump_mean=-0.1, jump_std=0.15, n_steps=5,
+              n_paths=100)
+    for scheme in ("euler", "qe"):
+        for lam, dt in ((1.0, 1.0), (4.0, 0.25), (0.5, 2.0)):
+            assert lam * dt == 1.0
+            M = eng.bates(**ok, jump_intensity=lam, dt=dt, scheme=scheme)
+            assert np.isfinite(M.to_host_step_major()).all()
+            M.free()
+        with pytest.raises(mc.McgError) as e:
+            eng.bates(**ok, jump_intensity=math.nextafter(1.0, 2.0), dt=1.0, scheme=scheme)
+        assert e.value.status == 1 and "lambda * dt <= 1" in str(e.value) and "more steps" in str(e.value), str(e.value)
+
+
+# ---- the count and the jump size on chosen words (mcg_debug_eval_v fn 9: WithJumps::count and WithJumps::jump) ----------------
+V_BATES_COUNT = 9
+TOP = 2 ** 32 - 1
+J_OBSERVED = 6.66      # worst error of J against mpmath, in ulp of |J|: at mu_J = -0.5, sigma_J = 0.1, N = 2, z3 = 5
+
+
+def hook(eng, L, words, z3=None, elem=0, mu_j=-0.1, sigma_j=0.15):
+    """words: [n][4] stream-4 words -> (counts [n][4], J [n] of element elem, comp), and the constants the library derives."""
+    words = np.asarray(words, dtype=np.int64)
+    comp, T = bates_constants(L, mu_j, sigma_j, 1.0)
+    assert T == jump_thresholds(L) and comp == jump_constants(L, mu_j, sigma_j, 1.0)[0]
+    z3 = np.zeros(len(words)) if z3 is None else np.asarray(z3, dtype=np.float64)
+    y = eng.debug_eval_v(V_BATES_COUNT, np.column_stack([words.astype(np.float64), z3]), [L, mu_j, sigma_j, comp] + T + [elem])
+    cnt = y[:, 0].astype(np.int64)
+    assert (cnt == y[:, 0]).all() and (y[:, 2:] == 0.0).all()
+    return np.stack([(cnt >> (8 * e)) & 0xFF for e in range(4)], axis=1), y[:, 1], comp
+
+
+def counts_of(L, words):
+    """The contract's count of every word: #{k : uN > c_k}, uN = (word + 1/2) 2^-32, in binary64."""
+    c = jump_constants(L, 0.0, 0.0, 1.0)[1]
+    return (uniform_of_words(np.asarray(words, dtype=np.uint64))[..., None] > c).sum(axis=-1)
+
+
+@pytest.mark.parametrize("L", [0.004, 0.5, 1.0])
+def test_count_of_every_word_next_to_a_threshold(eng, L):
+    """The words 0, 1, T_k - 1, T_k, T_k + 1 (k = 0..15), 2^32 - 2 and 2^32 - 1 in each of the four element positions, alone
+    in their path and beside three others.  At L = 1 the largest count is 12 (T_12 = ... = T_15 = 2^32 - 1): never 16."""
+    T = jump_thresholds(L)
+    W = sorted({min(max(w, 0), TOP) for w in [0, 1, TOP - 1, TOP] + [t + d for t in T for d in (-1, 0, 1)]})
+    m = len(W)
+    alone = [[w if e == pos else 0 for e in range(4)] for pos in range(4) for w in W]
+    mixed = [[W[i], W[(i + 7) % m], W[(i + 19) % m], W[(i + 31) % m]] for i in range(m)]
+    words = np.array(alone + mixed + mixed[::-1], dtype=np.int64)
+    assert all(set(words[:, e]) >= set(W) for e in range(4))
+    got, _, _ = hook(eng, L, words)
+    want = counts_of(L, words)
+    assert np.array_equal(want, (words[..., None] > np.array(T)).sum(axis=-1))
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    print(f"L = {L}: {len(words)} paths, {m} words, largest count {got.max()}")
+    assert got.max() == (12 if L == 1.0 else want.max()) and got.max() < JUMP_CAP
+
+
+def test_one_lane_drives_the_ladder(eng):
+    """A wave (128 paths) in which one path has c jumps in one step and the other 127 none, c = 1..12 at lambda dt = 1: the
+    thresholds above T_0 are looked at because of that one lane.  The lane is 0, 31, 32 or 63 and the path its first or second."""
+    L = 1.0
+    T = jump_thresholds(L)
+    spots = [(c, lane, which) for c in range(1, 13) for lane in (0, 31, 32, 63) for which in (0, 1)]
+    words = np.zeros((128 * len(spots), 4), dtype=np.int64)
+    for g, (c, lane, which) in enumerate(spots):
+        words[128 * g + 2 * lane + which, (c + lane + which) % 4] = T[c - 1] + 1
+    want = counts_of(L, words)
+    per_wave = want.reshape(len(spots), -1)
+    assert ((per_wave != 0).sum(axis=1) == 1).all() and list(per_wave.max(axis=1)) == [c for c, _, _ in spots]
+    got, _, _ = hook(eng, L, words)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+
+
+def test_quiet_wave_beside_a_jumping_wave(eng):
+    """Inside one workgroup (512 paths, four waves): waves in which no path jumps, next to waves in which most do.  The quiet
+    waves' counts are zero and their J is comp bit for bit, whatever z3 holds; so it is for the paths of a jumping wave that do
+    not jump."""
+    L, elem = 0.5, 2
+    T = jump_thresholds(L)
+    rng = np.random.default_rng(5)
+    quiet = np.array([0, 1, 0, 1, 1, 0, 1, 1], dtype=bool)                 # two workgroups
+    words = np.where(np.repeat(quiet, 128)[:, None], rng.integers(0, T[0] + 1, (1024, 4)), rng.integers(0, 2 ** 32, (1024, 4)))
+    words[128:256:9, 1] = T[0]                                             # on the threshold is not above it
+    z3 = rng.standard_normal(1024)
+    z3[::5] = np.nan
+    z3[1::7] = np.inf
+    want = counts_of(L, words)
+    assert (want.reshape(8, -1).sum(axis=1) == 0).tolist() == quiet.tolist() and want.max() >= 3
+    got, J, comp = hook(eng, L, words, z3, elem)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    still = want[:, elem] == 0
+    assert still[~np.repeat(quiet, 128)].any() and bits(J[still]) == bits(np.full(still.sum(), comp))
+    fine = ~still & np.isfinite(z3)
+    ref = comp + want[:, elem] * -0.1 + 0.15 * np.sqrt(want[:, elem]) * np.where(fine, z3, 0.0)
+    assert np.abs(J[fine] - ref[fine]).max() <= 1e-14
+
+
+@pytest.fixture(scope="module")
+def jump_sizes():
+    """(mu_j, sigma_j) -> [(N, z3, J at 50 digits, its inner sum and its normal term)], N = 0..12 and seven z3."""
+    mp.mp.dps = 50
+    out = {}
+    for mu_j, sigma_j in ((-0.1, 0.15), (-0.5, 0.1), (0.05, 0.2)):
+        comp = jump_constants(1.0, mu_j, sigma_j, 1.0)[0]
+        out[mu_j, sigma_j] = [(n, z, mp.mpf(comp) + n * mp.mpf(mu_j) + mp.mpf(sigma_j) * mp.sqrt(n) * mp.mpf(z),
+                               mp.mpf(comp) + n * mp.mpf(mu_j), mp.mpf(sigma_j) * mp.sqrt(n) * mp.mpf(z))
+                              for n in range(13) for z in (0.0, 1e-3, -1e-3, 1.0, -1.0, 5.0, -5.0)]
+    return out
+
+
+def test_jump_size_against_mpmath(eng, jump_sizes):
+    """J = comp + N mu_J + sigma_J sqrt(N) z3 for N = 0..12 at lambda dt = 1, in every element position, against 50 digits.
+    The device rounds four times: fm::sqrt_pos (<= 1 ulp, test_gpu_math.py), its product with sigma_J, the fused comp + N mu_J
+    and the fused sum -- at most 2^-53 (4 |sigma_J sqrt(N) z3| + |comp + N mu_J| + |J|), asserted as it stands.  In ulp of
+    |J| that is a few, more where the two terms cancel; observed on an MI355X: J_OBSERVED = 6.66 (-1 + comp against 0.707),
+    held to 1.5 times that.
+    N = 0: J is comp bit for bit."""
+    L = 1.0
+    T = jump_thresholds(L)
+    worst, at = 0.0, None
+    for (mu_j, sigma_j), rows in jump_sizes.items():
+        for elem in range(4):
+            words = np.zeros((len(rows), 4), dtype=np.int64)
+            words[:, elem] = [T[n - 1] + 1 if n else 0 for n, _, _, _, _ in rows]
+            got, J, comp = hook(eng, L, words, [z for _, z, _, _, _ in rows], elem, mu_j, sigma_j)
+            assert list(got[:, elem]) == [n for n, _, _, _, _ in rows] and not got[:, [e for e in range(4) if e != elem]].any()
+            for (n, z, exact, inner, normal), j in zip(rows, J):
+                if n == 0:
+                    assert bits(j) == bits(comp), (n, z, j, comp)
+                    continue
+                err = abs(mp.mpf(float(j)) - exact)
+                assert err <= mp.mpf(2) ** -53 * (4 * abs(normal) + abs(inner) + abs(exact)), (mu_j, sigma_j, n, z, float(j), float(err))
+                ulps = float(err / mp.mpf(float(np.spacing(abs(float(exact))))))
+                if ulps > worst:
+                    worst, at = ulps, (mu_j, sigma_j, n, z)
+    print(f"J against mpmath: worst {worst:.3f} ulp of |J| at (mu_j, sigma_j, N, z3) = {at}")
+    assert worst <= 1.5 * J_OBSERVED, (worst, at)
+
+
+def test_hook_refuses_what_is_no_word(eng):
+    comp, T = bates_constants(1.0, -0.1, 0.15, 1.0)
+    good = [1.0, -0.1, 0.15, comp] + T + [0]
+    x = np.zeros((3, 5))
+    eng.debug_eval_v(V_BATES_COUNT, x, good)
+    for change in ({0: 1.5}, {0: -0.1}, {4: 0.5}, {19: 2.0 ** 32}, {20: 4}, {20: 0.5}):
+        with pytest.raises(mc.McgError):
+            eng.debug_eval_v(V_BATES_COUNT, x, [change.get(i, v) for i, v in enumerate(good)])
+    for w in (-1.0, 2.0 ** 32, 0.5, float("nan")):
+        bad = x.copy()
+        bad[1, 2] = w
+        with pytest.raises(mc.McgError):
+            eng.debug_eval_v(V_BATES_COUNT, bad, good)
+    with pytest.raises(mc.McgError):
+        eng.debug_eval_v(V_BATES_COUNT, x, good[:-1])
 
 
 @pytest.mark.parametrize("scheme", ["euler", "qe"])

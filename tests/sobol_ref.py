@@ -110,6 +110,24 @@ def points(V, shift, path_begin, n_paths):
     return x
 
 
+def gray_codes(path_begin, n_paths):
+    """The Gray codes g = id ^ (id >> 1) of the ids path_begin .. path_begin + n_paths - 1, as Python ints."""
+    return [i ^ (i >> 1) for i in range(path_begin, path_begin + n_paths)]
+
+
+def gray_bits(path_begin, n_paths):
+    """The bits that are set in the Gray code of some id of the window and clear in another's: the direction numbers V[d][b]
+    that tell the window's points apart."""
+    g = gray_codes(path_begin, n_paths)
+    some, every = functools.reduce(int.__or__, g, 0), functools.reduce(int.__and__, g, (1 << 32) - 1)
+    return {b for b in range(32) if ((some & ~every) >> b) & 1}
+
+
+def n_bits(path_begin, n_paths):
+    """The smallest k with every id of the window below 2^k: 0 for the single id 0, 32 from 2^31 on."""
+    return (path_begin + n_paths - 1).bit_length()
+
+
 # ---- the normal: AS241 (PPND16) -----------------------------------------------------------------------------------------------
 A = (3.3871328727963666080e+0, 1.3314166789178437745e+2, 1.9715909503065514427e+3, 1.3731693765509461125e+4,
      4.5921953931549871457e+4, 6.7265770927008700853e+4, 3.3430575583588128105e+4, 2.5090809287301226727e+3)

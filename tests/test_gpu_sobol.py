@@ -1,6 +1,7 @@
 """The Sobol' generators on the GPU (mcg_paths_gbm_sobol*, mcg_paths_localvol_sobol*; PathEngine.gbm_sobol, local_vol_sobol)
-against the numpy restatement of tests/sobol_ref.py: Phi^-1 and the matrices element-wise, the bit-identities of the contract,
-the rejections, the consumers, and the statistics of randomised quasi-Monte Carlo.
+against the numpy restatement of tests/sobol_ref.py: Phi^-1 and the matrices element-wise (at every bit of the path id, every
+edge of the launch's n_bits and every shape of bridge program), the bit-identities of the contract, the rejections, the
+consumers, and the statistics of randomised quasi-Monte Carlo.
 
 Bounds: ten times the worst relative difference measured on an MI355X (the project's rule for its generators); the measured
 values stand beside them.  They come from rounding alone: numpy has no fused multiply-add and its log and exp are not the
@@ -17,7 +18,7 @@ from montecarlooptionspricer_amd import _native as N
 import sobol_ref as ref
 from test_exotics_reference import price_numpy, stats_numpy
 from test_localvol_reference import CEV, DT, NARROW, Q, R, S0, Surface, cev_half_closed_form, nodes
-from test_sobol_reference import normal_test_points
+from test_sobol_reference import BRIDGE_PROGRAM_STEPS, BRIDGE_STEPS, normal_test_points
 
 pytestmark = pytest.mark.gpu
 
@@ -25,6 +26,12 @@ SEED = 20261020
 # on an MI355X: Phi^-1 9.99e-16 over normal_test_points(); gbm_sobol 1.55e-14 (513 x 1024 steps; 5.8e-15 at 252 steps, below 9e-16 up
 # to 17); local_vol_sobol 4.88e-15 (the one-slice surface at 63 x 252; 1.3e-15 at 17 steps); the flat surface against gbm_sobol
 # 7.55e-15 (sigma = 1.5 over 1024 steps; the same bits at sigma = 0.2 and 0)
+# The cases at every index bit, n_bits edge and bridge length, on an MI355X: gbm_sobol 1.55e-14 again (601 x 1024 around
+# 0xAAAAAAAA; every other window at 2^k 1.51e-14 or less, the 56 bridge lengths of three paths 1.27e-14, the n_bits edges 1.11e-15),
+# except 6.79e-14 in the unscrambled first window (64 x 1024 from id 0, time order), where it is the restatement's: point 0 is
+# x = 0 in every dimension, so path 0 takes the same step z = Phi^-1(2^-33) = -6.34 1024 times and numpy repeats one rounding
+# error 1024 times; against the same product in 50 digits (mpmath) the restatement's last row of that path is off by 8.0e-14.
+# local_vol_sobol at the two high windows 4.88e-15 (64 x 252 at 2^31) and 1.55e-15 (300 x 33 across 2^24).  No constant moved.
 NORMAL_OBSERVED, GBM_OBSERVED, LV_OBSERVED, FLAT_OBSERVED = 9.99e-16, 1.55e-14, 4.88e-15, 7.55e-15
 observed = {"normal": 0.0, "gbm": 0.0, "local vol": 0.0, "flat against gbm_sobol": 0.0}
 SCRAMBLES = {0: "plain", 1: "shift", 2: "lms"}
@@ -110,6 +117,116 @@ def test_gbm_sobol_against_the_restatement(eng, case):
     assert e <= bound(GBM_OBSERVED), (case, e)
 
 
+# ---- gbm_sobol at every index bit, n_bits edge and bridge length -------------------------------------------------------------------
+# The cases above sit in two corners of the sequence: Gray bits 0 .. 12 and bit 31.  These walk the rest of it, in the format
+# of GBM_CASES.
+# 64 paths either side of 2^k for k = 6 .. 31, and the first 64: the window at 2^k tells its ids apart by Gray bits 0 .. 4 and k
+# (bit k - 1 is set in all of them), the first by bits 0 .. 5; 1024 steps, so every dimension is drawn; scramble and bridge
+# alternate through their six combinations
+INDEX_KS = (0,) + tuple(range(6, 32))
+INDEX_WINDOWS = tuple((64, 1024, 2 ** k - 32 if k else 0, j % 3, j % 2 == 1) for j, k in enumerate(INDEX_KS))
+# 601 paths around the id whose Gray code has every bit set, twice: from 0xAAAAAAAA - 300, which is even, and from the odd id
+# before it, which puts the pair (0xAAAAAAA9, 0xAAAAAAAA) into one lane
+EVERY_BIT_SET = 0xAAAAAAAA
+EVERY_BIT_WINDOWS = ((601, 1024, EVERY_BIT_SET - 300, 2, True), (601, 1024, EVERY_BIT_SET - 301, 1, False))
+# launch_sobol's n_bits: the last id of a launch decides how many groups of eight direction numbers sobol_pair reads
+N_BITS_EDGES = (2 ** 8, 2 ** 16, 2 ** 24)
+SMALL_LAUNCHES = ((0, 256), (0, 257), (0, 1), (2 ** 32 - 1, 1))    # (path_begin, n_paths): n_bits 8, 9, 0 and 32
+BRIDGE_BEGIN = 2 ** 20 - 1
+PAYOFF_COUNTS, PAYOFF_BEGIN = (1, 2, 255, 256, 257, 513), 2 ** 16 - 129
+
+
+def edge_case(E, reach_E, bridge):
+    """17 steps of the ids from the odd E - 301 (from 1 where that is negative) to E - 1, or to E: one lane holds the pair (E - 1, E)."""
+    begin = max(E - 301, 1)
+    return (E - begin + (1 if reach_E else 0), 17, begin, 2, bridge)
+
+
+def bridge_case(n_steps):
+    return (3, n_steps, BRIDGE_BEGIN, 2, True)
+
+
+def assert_the_new_axes():
+    """Every Gray bit 0 .. 31 set and clear, every n_bits class and edge, the listed bridge lengths."""
+    assert [w[2] for w in INDEX_WINDOWS] == [0] + [2 ** k - 32 for k in range(6, 32)] and {w[:2] for w in INDEX_WINDOWS} == {(64, 1024)}
+    for k, w in zip(INDEX_KS, INDEX_WINDOWS):
+        assert ref.gray_bits(w[2], w[0]) == ({0, 1, 2, 3, 4, k} if k else {0, 1, 2, 3, 4, 5}), k
+        assert ref.n_bits(w[2], w[0]) == (k + 1 if k else 6), k
+    assert set().union(*(ref.gray_bits(w[2], w[0]) for w in INDEX_WINDOWS)) == set(range(32))
+    for scramble in (0, 1, 2):
+        assert sum(w[3] == scramble for w in INDEX_WINDOWS) >= 8, scramble
+    for bridge in (False, True):
+        assert sum(w[4] == bridge for w in INDEX_WINDOWS) >= 8, bridge
+    assert {(w[3], w[4]) for w in INDEX_WINDOWS} == {(s, b) for s in (0, 1, 2) for b in (False, True)}
+    # n_bits 1 .. 8, 9 .. 16, 17 .. 24 and 25 .. 32: one, two, three and four groups
+    assert {(ref.n_bits(w[2], w[0]) + 7) // 8 for w in INDEX_WINDOWS} == {1, 2, 3, 4}
+    for n_paths, n_steps, begin, scramble, bridge in EVERY_BIT_WINDOWS:
+        codes = ref.gray_codes(begin, n_paths)
+        assert 2 ** 32 - 1 in codes and ref.n_bits(begin, n_paths) == 32 and len(ref.gray_bits(begin, n_paths)) >= 10
+    assert EVERY_BIT_WINDOWS[0][2] == EVERY_BIT_SET - 300 and EVERY_BIT_WINDOWS[1][2] % 2 == 1
+    assert (EVERY_BIT_SET - 1 - EVERY_BIT_WINDOWS[1][2]) % 2 == 0      # (the lane that starts at ...A9 holds ...AA)
+    for E in N_BITS_EDGES:
+        k = E.bit_length() - 1
+        for bridge in (False, True):
+            below, reach = edge_case(E, False, bridge), edge_case(E, True, bridge)
+            assert below[2] == reach[2] and below[2] % 2 == 1 and (E - 1 - below[2]) % 2 == 0 and below[1] == reach[1] == 17
+            assert below[2] + below[0] - 1 == E - 1 and reach[2] + reach[0] - 1 == E
+            assert (ref.n_bits(below[2], below[0]), ref.n_bits(reach[2], reach[0])) == (k, k + 1) and k % 8 == 0
+    assert [ref.n_bits(b, n) for b, n in SMALL_LAUNCHES] == [8, 9, 0, 32]
+    assert set(BRIDGE_PROGRAM_STEPS) == set(range(1, 41)) | {63, 64, 65, 100, 127, 128, 129, 255, 256, 257, 511, 512, 513, 683, 1000, 1023}
+    assert set(BRIDGE_PROGRAM_STEPS) <= set(BRIDGE_STEPS) and bridge_case(5) == (3, 5, 2 ** 20 - 1, 2, True)
+    assert PAYOFF_COUNTS == (1, 2, 255, 256, 257, 513) and PAYOFF_BEGIN % 2 == 1
+    assert ref.n_bits(PAYOFF_BEGIN, 129) == 16 and ref.n_bits(PAYOFF_BEGIN, 255) == 17
+    assert {s[2:] for s in LV_SHAPES} >= {(2 ** 24 - 150, 2, True), (2 ** 31 - 32, 1, False)}
+
+
+def test_new_cases_cover_their_axes():
+    assert_the_new_axes()
+
+
+def compare_gbm(eng, case):
+    """The step-major matrix of a case, held to bound(GBM_OBSERVED) against the restatement; a miss names its worst element."""
+    n_paths, n_steps, begin, scramble, bridge = case
+    want = ref.gbm_sobol_numpy(SEED, 0, scramble, bridge, GBM["S0"], GBM["r"], GBM["sigma"], GBM["dt"], n_steps, n_paths, begin)
+    got = host(eng.gbm_sobol(sobol_of(scramble, bridge), GBM["S0"], GBM["r"], GBM["sigma"], GBM["dt"], n_steps, n_paths, path_begin=begin))
+    assert got.shape == want.shape == (n_steps + 1, n_paths)
+    rel = np.abs(got / want - 1.0)
+    t, j = np.unravel_index(int(np.argmax(rel)), rel.shape)
+    e = float(rel[t, j])
+    observed["gbm"] = max(observed["gbm"], e)
+    print(f"gbm_sobol {case}: {e:.2e}")
+    assert (got[0] == GBM["S0"]).all()
+    code = ref.gray_codes(begin + int(j), 1)[0]
+    assert e <= bound(GBM_OBSERVED), (f"{case}: {e:.2e} at row {t} of path id {begin + int(j)}, Gray code {code:#034b}, "
+                                      f"{'bridge: every dimension up to the row' if bridge else f'dimension {t - 1}'}")
+    return got
+
+
+@pytest.mark.parametrize("case", INDEX_WINDOWS + EVERY_BIT_WINDOWS, ids=lambda c: "-".join(str(v) for v in c))
+def test_gbm_sobol_at_every_index_bit(eng, case):
+    compare_gbm(eng, case)
+
+
+@pytest.mark.parametrize("bridge", [True, False])
+@pytest.mark.parametrize("E", N_BITS_EDGES)
+def test_n_bits_edges(eng, E, bridge):
+    """A launch that ends at E - 1 reads one group of direction numbers fewer than one that ends at E: both are the
+    restatement's, and the columns they share are the same bytes."""
+    below, reach = compare_gbm(eng, edge_case(E, False, bridge)), compare_gbm(eng, edge_case(E, True, bridge))
+    assert reach.shape[1] == below.shape[1] + 1 and bits(reach[:, :-1]) == bits(below), (E, bridge)
+
+
+@pytest.mark.parametrize("bridge", [True, False])
+def test_smallest_and_largest_n_bits(eng, bridge):
+    mats = {(begin, n_paths): compare_gbm(eng, (n_paths, 17, begin, 2, bridge)) for begin, n_paths in SMALL_LAUNCHES}
+    assert bits(mats[0, 257][:, :256]) == bits(mats[0, 256]) and bits(mats[0, 256][:, :1]) == bits(mats[0, 1])
+
+
+@pytest.mark.parametrize("n_steps", BRIDGE_PROGRAM_STEPS)
+def test_every_shape_of_bridge_program(eng, n_steps):
+    compare_gbm(eng, bridge_case(n_steps))
+
+
 # ---- local_vol_sobol element-wise -----------------------------------------------------------------------------------------------
 # one slice of 64 nodes; 12 knots x 64 nodes (knots off the step grid, a skew that turns with time); a grid that a step
 # leaves at once, so that most path-steps sit on either clamp
@@ -117,7 +234,9 @@ KNOTS_12 = Surface([0.4 * DT + 2.3 * DT * i for i in range(12)], -0.8, 0.8,
                    [[0.2 + 0.05 * math.sin(0.7 * i) - (0.15 - 0.02 * i) * x + 0.1 * x * x for x in nodes(-0.8, 0.8, 64)] for i in range(12)])
 LV_SURFACES = {"cev": CEV, "knots-12": KNOTS_12, "narrow": NARROW}
 # (n_paths, n_steps, path_begin, scramble, bridge)
-LV_SHAPES = ((513, 9, 777, 2, True), (1000, 17, 1, 1, True), (63, 252, END, 2, False))
+# the last two at high indices: ids that straddle 2^24 (n_bits 24 and 25 in one workgroup's launch) and 2^31
+LV_SHAPES = ((513, 9, 777, 2, True), (1000, 17, 1, 1, True), (63, 252, END, 2, False), (300, 33, 2 ** 24 - 150, 2, True),
+             (64, 252, 2 ** 31 - 32, 1, False))
 
 
 def test_local_vol_surfaces_are_what_they_are_meant_to_be():
@@ -171,6 +290,44 @@ def test_bit_identities(eng, bridge):
             plain.free()
         # another replicate is another matrix
         assert bits(host(gen(sobol_of(2, bridge, 2), 1000, 4097))) != bits(whole)
+
+
+@pytest.mark.parametrize("bridge", [True, False])
+@pytest.mark.parametrize("E", (2 ** 16, 2 ** 24))
+def test_shards_across_an_n_bits_edge(eng, E, bridge):
+    """[E - 500, E) reads one group of direction numbers fewer than [E, E + 500) and than the whole: the same bytes all the same."""
+    assert ref.n_bits(E - 500, 500) + 1 == ref.n_bits(E, 500) == ref.n_bits(E - 500, 1000) and ref.n_bits(E - 500, 500) % 8 == 0
+    for name, gen in generators(eng):
+        sobol = sobol_of(2, bridge, 1)
+        whole = host(gen(sobol, 1000, E - 500))
+        parts = [host(gen(sobol, 500, E - 500)), host(gen(sobol, 500, E))]
+        assert bits(np.concatenate(parts, axis=1)) == bits(whole), (name, E, "shards")
+
+
+@pytest.mark.parametrize("n_paths", PAYOFF_COUNTS)
+def test_payoff_form_at_small_and_ragged_counts(eng, n_paths):
+    """Up to 256 paths the workgroup's upper two waves lie beyond the padded row; 257 and 513 end a row one column into a wave."""
+    T, disc = 17 * DT, math.exp(-R * 17 * DT)
+    for name, gen in generators(eng):
+        sobol = sobol_of(2, True, 1)
+        for K, is_call in ((100.0, True), (100.0, False)):
+            plain = gen(sobol, n_paths, PAYOFF_BEGIN)
+            want, want_se = eng.price_european(plain, K, R, T, is_call)
+            fused = gen(sobol, n_paths, PAYOFF_BEGIN, (K, is_call))
+            got, got_se = eng.price_european(fused, K, R, T, is_call)
+            X = host(plain)
+            assert X.shape == (18, n_paths) and bits(host(fused)) == bits(X), (name, n_paths, "payoff form")
+            assert abs(got - want) <= 1e-12 * want and abs(got_se - want_se) <= 1e-9 * want_se, (name, n_paths, K, is_call, got, want)
+            pay = disc * (np.maximum(X[-1] - K, 0.0) if is_call else np.maximum(K - X[-1], 0.0))
+            m, se = float(pay.mean()), float(pay.std(ddof=1)) / math.sqrt(n_paths) if n_paths > 1 else 0.0
+            # the std error comes from sum and sum of squares: its bound scales as in test_path_counts of test_gpu_exotics.py
+            tol_se = 1e-9 * se * (max(1.0, 0.5 + (m / se) ** 2 / n_paths) if se > 0.0 else 1.0)
+            print(f"{name} {n_paths} paths, K {K}, call {is_call}: price {got!r} (numpy {m!r}), std error {got_se!r} (numpy {se!r})")
+            assert abs(got - m) <= 1e-12 * m and abs(got_se - se) <= tol_se, (name, n_paths, K, is_call, got, m, got_se, se)
+            if n_paths == 1:
+                assert got_se == 0.0 and want_se == 0.0
+        # a call or a put at the money pays on at least one path
+        assert float(np.abs(X[-1] - 100.0).max()) > 0.0
 
 
 # ---- the flat surface and the rejections ---------------------------------------------------------------------------------------

@@ -34,6 +34,108 @@ def test_plain_table_is_scipys_unscrambled_sequence():
     assert (ref.points(V[:64], shift[:64], 777, 300).T == (eng.random(300) * 2.0 ** 32).astype(np.uint64)).all()
 
 
+def test_plain_table_is_scipys_in_all_32_columns():
+    """Points 0 .. 1076 above use Gray bits 0 .. 10 only; this is every direction number, and points near 2^14, 2^20 and 2^26."""
+    from scipy.stats import qmc
+    V, shift = mc.sobol_table(mc.Sobol(SEED, 0, "plain"), N.SOBOL_MAX_DIMS)
+    # scipy's own matrix where it shows it (a private attribute: without it the public check below stands alone)
+    sv = getattr(qmc.Sobol(N.SOBOL_MAX_DIMS, scramble=False, bits=32), "_sv", None)
+    if sv is not None:
+        assert sv.shape == (1024, 32) and sv.dtype == np.uint32
+        assert (V == sv).all() and (ref.direction_numbers(1024) == sv).all()
+    # the public interface: 64 points either side of 2^k in the first four dimensions (forwarding costs time per dimension)
+    for k in (14, 20, 26):
+        eng = qmc.Sobol(4, scramble=False, bits=32)
+        eng.fast_forward(2 ** k - 32)
+        want = eng.random(64) * 2.0 ** 32
+        assert (want == np.floor(want)).all()
+        assert k in ref.gray_bits(2 ** k - 32, 64)
+        assert (ref.points(V[:4], shift[:4], 2 ** k - 32, 64).T == want.astype(np.uint64)).all(), k
+
+
+def test_gray_bits_and_n_bits():
+    """The helpers that the coverage assertions stand on, against the ids written out."""
+    assert ref.gray_codes(0, 4) == [0, 1, 3, 2] and ref.gray_codes(0xAAAAAAAA, 1) == [0xFFFFFFFF]
+    assert ref.gray_bits(0, 1) == set() and ref.gray_bits(0, 2) == {0} and ref.gray_bits(1, 2) == {1} and ref.gray_bits(0, 1000) == set(range(10))
+    assert ref.gray_bits(777, 1000) == set(range(11)) and ref.gray_bits(4097, 1000) == set(range(10))     # (bits 11 and 12 are set in all)
+    assert ref.gray_bits(2 ** 32 - 1000, 1000) == set(range(10))                                                   # (and so is bit 31)
+    assert ref.gray_bits(2 ** 20 - 32, 64) == {0, 1, 2, 3, 4, 20} and ref.gray_bits(2 ** 31, 2) == {0}
+    for begin, n in ((0, 1000), (777, 1000), (2 ** 20 - 32, 64), (2 ** 32 - 5, 5)):
+        i = np.arange(begin, begin + n, dtype=np.uint64)
+        on = (((i ^ (i >> np.uint64(1)))[:, None] >> np.arange(32, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        assert ref.gray_bits(begin, n) == {b for b in range(32) if on[:, b].any() and not on[:, b].all()}, (begin, n)
+    assert [ref.n_bits(b, n) for b, n in ((0, 1), (1, 1), (0, 256), (0, 257), (2 ** 16 - 3, 3), (2 ** 16 - 3, 4), (2 ** 31 - 1, 1),
+                                          (2 ** 31, 1), (2 ** 32 - 1, 1))] == [0, 1, 8, 9, 16, 17, 31, 32, 32]
+
+
+def test_gpu_cases_cover_every_gray_bit_and_n_bits_class():
+    """What tests/test_gpu_sobol.py asserts of its own cases before it runs them, here without a GPU."""
+    import test_gpu_sobol as G
+    G.assert_the_new_axes()
+
+
+def moved_by(case, d, b):
+    """The largest relative move of the restatement's matrix of a case of tests/test_gpu_sobol.py (n_paths, n_steps, path_begin,
+    scramble, bridge) when the lowest bit of V'[d][b], as the device would receive it, is flipped."""
+    import test_gpu_sobol as G
+    n_paths, n_steps, begin, scramble, bridge = case
+    gbm = lambda: ref.gbm_sobol_numpy(G.SEED, 0, scramble, bridge, G.GBM["S0"], G.GBM["r"], G.GBM["sigma"], G.GBM["dt"], n_steps, n_paths, begin)  # noqa: E731
+    right, table = gbm(), ref.table
+
+    def wrong_table(*args):
+        V, shift = table(*args)
+        V = V.copy()
+        V[d, b] ^= np.uint32(1)
+        return V, shift
+    ref.table = wrong_table
+    try:
+        wrong = gbm()
+    finally:
+        ref.table = table
+    return float(np.abs(wrong / right - 1.0).max())
+
+
+def test_a_wrong_direction_number_moves_the_new_cases():
+    """The new GPU cases can fail: one wrong last bit in one direction number of a bit that tells a window's ids apart moves the
+    matrix by at least 100 times the bound the device is held to, and a bit that no id of the window has set moves nothing.
+
+    A last bit is the smallest possible error, 2^-32 in u, so at least 2^-32 sqrt(2 pi) = 5.8e-10 in z (more away from z = 0) and
+    sigma sqrt(dt) sd times that in ln S, where sd >= sqrt(1/2) is the weight of the node that takes the dimension (1 in time
+    order): at least 1.03e-11, 66 bounds, and that only where the one path that has the bit set draws z = 0 at a leaf.  In an
+    index window 32 ids or more have the bit set, and the largest move among them is asserted to be 100 bounds, as measured:
+    the smallest is 1.9e-11 = 125 bounds (the window at 2^12, dimension 1023, bit 0).  In the n_bits edges and the three-path
+    bridge cases one or two ids have it (bit k of an edge is the id E's alone): those are held to the floor above, which the
+    edge at 2^8 meets in dimension 8 (1.03e-11 = 67 bounds)."""
+    import test_gpu_sobol as G
+    limit = G.bound(G.GBM_OBSERVED)
+    one_path_floor = 0.99 * 2.0 ** -32 * math.sqrt(2.0 * math.pi) * G.GBM["sigma"] * math.sqrt(G.GBM["dt"]) * math.sqrt(0.5)
+    assert 100.0 * limit > one_path_floor >= 60.0 * limit
+    sample = [w for w in G.INDEX_WINDOWS if w[2] in tuple(2 ** k - 32 for k in (6, 7, 12, 13, 20, 21, 28, 29, 31))]
+    # at least one window per group of eight bits, with and without the bridge: all of them held to 100 bounds
+    groups = {((ref.n_bits(c[2], c[0]) + 7) // 8, c[4]) for c in sample}
+    assert groups == {(k, bridge) for k in (1, 2, 3, 4) for bridge in (True, False)}
+    sample += [G.edge_case(E, True, bridge) for E in G.N_BITS_EDGES for bridge in (True, False)]
+    sample += [G.bridge_case(n) for n in (1, 2, 37, 683)]
+    smallest = math.inf
+    for case in sample:
+        n_paths, n_steps, begin = case[:3]
+        varying = ref.gray_bits(begin, n_paths)
+        codes = ref.gray_codes(begin, n_paths)
+        unused = [b for b in range(32) if not any((g >> b) & 1 for g in codes)]
+        assert varying and not varying & set(unused), case
+        for d in sorted({0, min(1, n_steps - 1), n_steps // 2, n_steps - 1}):
+            for b in (min(varying), max(varying)):
+                several = case in G.INDEX_WINDOWS
+                assert not several or sum((g >> b) & 1 for g in codes) >= 32
+                e = moved_by(case, d, b)
+                smallest = min(smallest, e)
+                print(f"{case}: V[{d}][{b}] moves the matrix by {e:.2e} = {e / limit:.0f} bounds")
+                assert e >= (100.0 * limit if several else one_path_floor), (case, d, b, e)
+            for b in unused[:1] + unused[-1:]:
+                assert moved_by(case, d, b) == 0.0, (case, d, b)
+    print(f"smallest move {smallest:.2e} against the bound {limit:.2e}")
+
+
 @pytest.mark.parametrize("scramble", ["shift", "lms"])
 def test_scrambled_tables_equal_the_restatement(scramble):
     code = N.SOBOL_SCRAMBLES[scramble]
@@ -67,7 +169,11 @@ def test_seed_and_replicate_select_the_table():
 
 
 # ---- the bridge -------------------------------------------------------------------------------------------------------------------
-BRIDGE_STEPS = (1, 2, 3, 4, 5, 7, 8, 9, 13, 17, 252, 1024)
+# The lengths whose bridge program tests/test_gpu_sobol.py walks on the device with three paths: every n to 40 (all shapes of
+# the first five tree levels), powers of two and their neighbours (a full tree, one node short, one node over), and lengths
+# in between; schedule, orthogonality and program are judged at the same n.
+BRIDGE_PROGRAM_STEPS = tuple(range(1, 41)) + (63, 64, 65, 100, 127, 128, 129, 255, 256, 257, 511, 512, 513, 683, 1000, 1023)
+BRIDGE_STEPS = tuple(sorted(set((1, 2, 3, 4, 5, 7, 8, 9, 13, 17, 252, 1024) + BRIDGE_PROGRAM_STEPS)))
 # max |QQ^T - I| (element-wise) of the restatement over BRIDGE_STEPS: 4.4e-16, at 252 and 1024 steps
 ORTHOGONALITY_OBSERVED = 4.4e-16
 

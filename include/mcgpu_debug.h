@@ -52,6 +52,21 @@ int mcg_debug_eval(mcg_ctx* ctx, int fn, const double* x, double* y, int64_t n);
  *       y = {cnt, J}: cnt = N_0 + 2^8 N_1 + 2^16 N_2 + 2^24 N_3, the counts of the four words (N_e = #{k : w_e > T[k]}), and
  *       J = comp + N_elem mu_j + sigma_j sqrt(N_elem) z3 (comp where N_elem = 0, whatever z3 holds). */
 int mcg_debug_eval_v(mcg_ctx* ctx, int fn, const double* x, int n_in, const double* params, int n_params, double* y, int64_t n);
+/* Test hook: the regression solves of the LSM sweeps (csrc/lsm_device.hpp) on moments the caller chooses, launched as the product
+ * runs them: one workgroup per element, thread 0 solving, moments and the centred forms' workspace in LDS.  Element i reads
+ * moments[i n_moments ..) and params[3i ..) = {min_count, K, mu} and writes out[48i ..): two coefficient blocks of
+ * LSM_COEF_STRIDE = 24 doubles (coefficients 0..15, then COUNT, CENTER, REFINE, HINT at 16..19), the second the tangent's
+ * dcoef; what a fn does not write is 0.  With p = nb - 1 the moments are the power sums m[0..2p], the cross sums m[2p+1..3p+1]
+ * and, for the tangent forms, the tangent's cross sums m[3p+2..4p+2].
+ * fn 0: lsm_solve_nb<nb>, nb 1..9, n_moments = 3 nb - 1      fn 1: lsm_solve_nb<nb, true>, n_moments = 4 nb - 1
+ * fn 2: lsm_solve_one(nb), the run-time dispatch, as fn 0
+ * fn 3: lsm_solve_centered, nb 1..16, n_moments = 3 nb - 1, the moments taken about mu       fn 4: lsm_solve_centered_tan, 4 nb - 1
+ * fn 5: n_moments = 1 (nb is not read): out[0] = lsm_rcp(x), out[1] = lsm_rsqrt(x) of x = moments[0]
+ * fn 6: lsm_continuation<nb>(c, centre, x), nb 1..9; the element is {c[0..nb), centre, x}, n_moments = nb + 2; out[0].
+ * NULL pointers, n < 0, n > 2^20, nb outside the fn's range and any other n_moments are refused with a message and nothing is
+ * launched; n = 0 does nothing. */
+int mcg_debug_lsm_solve(mcg_ctx* ctx, int fn, int nb, const double* moments, int n_moments, const double* params, double* out,
+                        int64_t n);
 /* Test hook, host-only: the jump constants of mcg_paths_bates* as its launcher derives them (the same function) -- *comp =
  * -lambda kbar dt and T[k] = floor(min(c_k, 1) 2^32 - 1/2), the word thresholds of the count: uN > c_k <=> word > T[k].  Nothing
  * is validated: the product's bound lambda dt <= 1 is mcg_paths_bates's. */

@@ -1,10 +1,11 @@
 // Test hooks behind mcg_debug_eval and mcg_debug_eval_v: run one routine of fastmath.hpp, philox.hpp or the Heston
 // steps (heston_device.hpp, heston_schemes.hpp, bates_device.hpp) elementwise so that tests can measure its error against
-// mpmath / libm.  Not on any product path.
+// mpmath / libm; behind mcg_debug_lsm_solve: the regression solves of lsm_device.hpp.  Not on any product path.
 #include "bates_device.hpp"
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "heston_schemes.hpp"
+#include "lsm_device.hpp"
 #include "mcg_internal.hpp"
 
 namespace mcg {
@@ -211,7 +212,124 @@ __global__ __launch_bounds__(256) void k_debug_bates_count(DebugBatesArgs a) {
     }
 }
 
+// ---- mcg_debug_lsm_solve: the regression solves of lsm_device.hpp on moments the caller chooses --------------------------------
+// Launched as the product runs them: one workgroup per element, the moments staged in LDS (as k_lsm_reduce_solve hands them to
+// the solve), thread 0 solving into a coefficient block in LDS, the centred forms' workspace in LDS.  Every case below calls
+// the routine of lsm_device.hpp itself.
+enum : int { L_SOLVE_NB = 0, L_SOLVE_NB_TAN, L_SOLVE_ONE, L_CENTERED, L_CENTERED_TAN, L_RCP_RSQRT, L_CONTINUATION, L_COUNT };
+constexpr int L_MAX_MOMENTS = 4 * LSM_MAX_NB - 1;  // the tangent's centred solve at sixteen basis functions
+constexpr int L_OUT = 2 * LSM_COEF_STRIDE;         // coef, dcoef
+
+struct DebugLsmArgs {
+    int fn, nb, n_moments;
+    const double* moments;  // [n][n_moments]
+    const double* params;   // [n][3]: min_count, K, mu
+    double* out;            // [n][L_OUT]
+};
+
+template <int NB>
+__device__ __forceinline__ double debug_lsm_continuation(const double* e) {
+    double c[NB];
+#pragma unroll
+    for (int t = 0; t < NB; ++t) c[t] = e[t];
+    return lsm_continuation<NB>(c, e[NB], e[NB + 1]);
+}
+
+#define MCG_DEBUG_LSM_NB(CALL) \
+    switch (nb) {              \
+        case 1: CALL(1); break; \
+        case 2: CALL(2); break; \
+        case 3: CALL(3); break; \
+        case 4: CALL(4); break; \
+        case 5: CALL(5); break; \
+        case 6: CALL(6); break; \
+        case 7: CALL(7); break; \
+        case 8: CALL(8); break; \
+        default: CALL(9); break; \
+    }
+
+__global__ __launch_bounds__(64) void k_debug_lsm_solve(DebugLsmArgs a) {
+    __shared__ double sm_mom[L_MAX_MOMENTS + 1];
+    __shared__ double sm_coef[L_OUT];
+    __shared__ double sm_ws[lsm_ws_doubles(LSM_MAX_NB)];
+    const int64_t i = blockIdx.x;
+    for (int t = threadIdx.x; t < a.n_moments; t += 64) sm_mom[t] = a.moments[i * a.n_moments + t];
+    for (int t = threadIdx.x; t < L_OUT; t += 64) sm_coef[t] = 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int nb = a.nb;  // (uniform)
+        const double min_count = a.params[3 * i], K = a.params[3 * i + 1], mu = a.params[3 * i + 2];
+        double* coef = sm_coef;
+        double* dcoef = sm_coef + LSM_COEF_STRIDE;
+        switch (a.fn) {
+            case L_SOLVE_NB:
+#define CALL(NB) lsm_solve_nb<NB>(sm_mom, min_count, K, coef)
+                MCG_DEBUG_LSM_NB(CALL)
+#undef CALL
+                break;
+            case L_SOLVE_NB_TAN:
+#define CALL(NB) lsm_solve_nb<NB, true>(sm_mom, min_count, K, coef, dcoef)
+                MCG_DEBUG_LSM_NB(CALL)
+#undef CALL
+                break;
+            case L_SOLVE_ONE: lsm_solve_one(sm_mom, nb, min_count, K, coef); break;
+            case L_CENTERED: lsm_solve_centered(sm_mom, nb, mu, K, coef, sm_ws); break;
+            case L_CENTERED_TAN: lsm_solve_centered_tan(sm_mom, nb, mu, K, coef, dcoef, sm_ws); break;
+            case L_RCP_RSQRT:
+                coef[0] = lsm_rcp(sm_mom[0]);
+                coef[1] = lsm_rsqrt(sm_mom[0]);
+                break;
+            default:
+#define CALL(NB) coef[0] = debug_lsm_continuation<NB>(sm_mom)
+                MCG_DEBUG_LSM_NB(CALL)
+#undef CALL
+                break;
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < L_OUT; t += 64) a.out[i * L_OUT + t] = sm_coef[t];
+}
+#undef MCG_DEBUG_LSM_NB
+
 }  // namespace mcg
+
+extern "C" int mcg_debug_lsm_solve(mcg_ctx* ctx, int fn, int nb, const double* moments, int n_moments, const double* params,
+                                   double* out, int64_t n) {
+    using namespace mcg;
+    static_assert(L_OUT == 48, "the header's 48 doubles per element");
+    if (!ctx || !moments || !params || !out) return fail(MCG_ERR_INVALID, "NULL argument");
+    if (n < 0 || fn < 0 || fn >= L_COUNT) return fail(MCG_ERR_INVALID, "bad arguments");
+    if (n > (int64_t)1 << 20) return fail(MCG_ERR_INVALID, "at most 2^20 elements");
+    const bool centred = fn == L_CENTERED || fn == L_CENTERED_TAN;
+    const int nb_max = centred ? LSM_MAX_NB : 9;
+    if (fn != L_RCP_RSQRT && (nb < 1 || nb > nb_max)) return fail(MCG_ERR_INVALID, "fn %d takes nb 1..%d", fn, nb_max);
+    const int want = fn == L_RCP_RSQRT ? 1 : fn == L_CONTINUATION ? nb + 2 : fn == L_SOLVE_NB_TAN || fn == L_CENTERED_TAN ? 4 * nb - 1 : 3 * nb - 1;
+    if (n_moments != want) return fail(MCG_ERR_INVALID, "fn %d at nb %d takes %d doubles per element", fn, nb, want);
+    if (n == 0) return MCG_OK;
+    MCG_HIP(hipSetDevice(ctx->device));
+    const size_t n_in = (size_t)n * n_moments, n_par = (size_t)n * 3, n_out = (size_t)n * L_OUT;
+    double* buf = nullptr;  // moments, params, out
+    MCG_HIP(hipMalloc((void**)&buf, (n_in + n_par + n_out) * sizeof(double)));
+    DebugLsmArgs a;
+    a.fn = fn;
+    a.nb = nb;
+    a.n_moments = n_moments;
+    a.moments = buf;
+    a.params = buf + n_in;
+    a.out = buf + n_in + n_par;
+    int rc = MCG_OK;
+    if (hipMemcpyAsync(buf, moments, n_in * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(buf + n_in, params, n_par * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = fail(MCG_ERR_HIP, "H2D failed");
+    if (rc == MCG_OK) {
+        hipLaunchKernelGGL(k_debug_lsm_solve, dim3((unsigned)n), dim3(64), 0, ctx->stream, a);
+        if (hipMemcpyAsync(out, a.out, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess)
+            rc = fail(MCG_ERR_HIP, "debug lsm solve failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    (void)hipFree(buf);
+    return rc;
+}
 
 extern "C" int mcg_debug_bates_constants(double lambda, double mu_j, double sigma_j, double dt, uint32_t T[16], double* comp) {
     using namespace mcg;

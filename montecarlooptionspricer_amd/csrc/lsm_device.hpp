@@ -30,7 +30,9 @@ __host__ __device__ constexpr int lsm_ws_doubles(int nb) { return 7 * nb * nb + 
 // Where that matrix has full numerical rank and the data are well spread, the fitted values are those of the unique
 // least-squares polynomial and any accurate method yields them: here LDL^T on the equilibrated normal equations of
 // the scaled regressor (cond ~1e2 instead of ~1e8; ~1 us).  The fast path is taken only when both hold:
-//   * every pivot > 1e-6 (normal equations then lose at most ~1e-10 of relative accuracy), and
+//   * every pivot > 1e-6 (normal equations then lose at most ~1e-10 of relative accuracy; the device code is held to 8 eps
+//     kappa of the exact solution of the same moments by test_fast_path_against_the_exact_solution, tests/test_gpu_lsm_solve.py,
+//     and DESIGN.md gives the errors observed), and
 //   * est = (std(S) / max(mean(S), 1)^2)^p -- the size of sigma_min / sigma_max of the raw-monomial matrix for data
 //     of that spread -- exceeds Eigen's threshold by four orders of magnitude, so Eigen sees full rank as well.
 // Otherwise (few or nearly coincident in-the-money prices, all paths equal at j = 0, high orders whose raw monomials
@@ -42,9 +44,9 @@ __host__ __device__ constexpr int lsm_ws_doubles(int nb) { return 7 * nb * nb + 
 // NB is a template parameter so that every loop unrolls and G, Q live in registers: with a run-time size the
 // arrays go to scratch memory and the (serial, one-thread) solve takes ~20 us instead of ~2.
 // 1/x and x^(-1/2) for positive normal x from the hardware seeds (v_rcp_f64, v_rsq_f64) and two Newton steps (one
-// second-order step), <= 1 ulp: the solve runs on ONE thread between two grid-wide hand-shakes of the one-launch
-// sweeps, where the ~35 dependent instructions of a correctly rounded fp64 division (a dozen of them per date) were a
-// quarter of the date's 9 us.
+// second-order step), <= 1 ulp (test_rcp_and_rsqrt_within_one_ulp, tests/test_gpu_lsm_solve.py): the solve runs on ONE
+// thread between two grid-wide hand-shakes of the one-launch sweeps, where the ~35 dependent instructions of a correctly
+// rounded fp64 division (a dozen of them per date) were a quarter of the date's 9 us.
 __device__ __forceinline__ double lsm_rcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);
@@ -188,7 +190,10 @@ __device__ __forceinline__ void lsm_solve_nb(const double* moments, double min_c
 //      so A_raw = U_y B with B = F T (at most nb x nb): the singular values of B ARE Eigen's, and its left singular
 //      vectors W give Eigen's in U_y coordinates.  B = diag(row scales) x (well-conditioned), the case in which
 //      one-sided Jacobi on the rows delivers even the smallest singular values to high relative accuracy
-//      (Demmel-Veselic); checked against 60-digit arithmetic for spreads 1e-2 .. 1e-8 in tests/.
+//      (Demmel-Veselic).  This routine itself is run on chosen moments (mcg_debug_lsm_solve) against Eigen's rule in 60-digit
+//      arithmetic for nb 1..16 and spreads 0.3 .. 1e-8 by test_centred_solve_against_eigens_rule_in_exact_arithmetic
+//      (tests/test_gpu_lsm_solve.py; cases, references and a binary64 restatement in tests/test_lsm_solve_reference.py); the
+//      oracle's own solver by test_lsm_oracle_rank_rule_on_near_degenerate_dates_vs_exact_arithmetic.
 //   3. Eigen's rule: keep sigma_i > min(rows, cols) eps sigma_max.  Fitted values = A_raw V_k S_k^-1 U_k^T b
 //      = A_y F^-1 P_k z with P_k the projector on the kept left singular vectors: the coefficients in y are
 //      F^-1 P_k z -- no raw-monomial coefficient (huge, cancelling) is ever formed.

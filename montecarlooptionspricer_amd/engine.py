@@ -654,6 +654,23 @@ class PathEngine:
                                        y.ctypes.data_as(dp), x.shape[0]))
         return y
 
+    def debug_lsm_solve(self, fn: int, nb: int, moments: np.ndarray, params=None) -> np.ndarray:
+        """Test hook (mcg_debug_lsm_solve): one regression solve of the LSM sweeps per element, on the moments given
+        (moments: [n][n_moments]; params: [n][3] = min_count, K, mu per element, default {1, 1, 0}); returns [n][48]: the
+        coefficient block (24 doubles) and the tangent's."""
+        m = np.ascontiguousarray(moments, dtype=np.float64)
+        if m.ndim == 1:
+            m = m.reshape(-1, 1)
+        p = np.tile([1.0, 1.0, 0.0], (m.shape[0], 1)) if params is None else np.ascontiguousarray(params, dtype=np.float64)
+        if p.shape != (m.shape[0], 3):
+            raise McgError("params must be [n][3]", 1)
+        p = np.ascontiguousarray(p)
+        out = np.empty((m.shape[0], 48), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self._L.mcg_debug_lsm_solve(self._ctx, int(fn), int(nb), m.ctypes.data_as(dp), m.shape[1], p.ctypes.data_as(dp),
+                                          out.ctypes.data_as(dp), m.shape[0]))
+        return out
+
     def debug_gbm_route(self, route: int = -1) -> int:
         """Test hook (mcg_debug_gbm_route): 0 = the generators choose their kernel by size, 1 = the narrow kernel, 2 = the
         wide one, -1 = unchanged; returns what the last GBM launch took (1 or 2; 0: none yet)."""

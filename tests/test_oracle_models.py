@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle.binding import Oracle, Reference, have_ref, synthetic_history
+from test_lsm_solve_reference import _exact_eigen_rule_fit
 
 DT = 1.0 / 252.0
 
@@ -252,28 +253,6 @@ def lsm_numpy(paths_pm, r, K, maturity, dt, is_call, poly):
         Vn[otm] = V[otm] * disc
         V = Vn
     return V.mean()
-
-
-def _exact_eigen_rule_fit(S, b, p):
-    """Eigen's bdcSvd().solve(b) on raw monomials of S (LSMPricer.cpp:61-76) in 60-digit arithmetic: minimum-norm least
-    squares with singular values <= min(rows, cols) eps sigma_max dropped.  Returns the fitted values at the data."""
-    import mpmath as mp
-    mp.mp.dps = 60
-    n = len(S)
-    A = mp.matrix(n, p + 1)
-    for i in range(n):
-        for k in range(p + 1):
-            A[i, k] = mp.mpf(float(S[i])) ** k
-    U, sv, V = mp.svd_r(A, full_matrices=False, compute_uv=True)
-    thr = min(n, p + 1) * mp.mpf(np.finfo(float).eps) * sv[0]
-    coef = mp.matrix(p + 1, 1)
-    for j in range(len(sv)):
-        if sv[j] > thr:
-            proj = sum(U[i, j] * mp.mpf(float(b[i])) for i in range(n)) / sv[j]
-            for t in range(p + 1):
-                coef[t] += proj * V[j, t]
-    fit = A * coef
-    return np.array([float(fit[i]) for i in range(n)])
 
 
 def test_lsm_oracle_rank_rule_on_near_degenerate_dates_vs_exact_arithmetic(orc):

@@ -292,7 +292,11 @@ int mcg_paths_bates_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, dou
  * many assets there are.  The combined matrix of the fused call equals mcg_paths_combine of the asset matrices bit for bit, and
  * the asset matrices have the same bits whether or not a combination was asked for.  A path depends on (seed, global path id)
  * only: any split into shards reproduces the one-call matrices bit for bit, repeated calls are bit-identical, path_begin may
- * be odd, n_paths = 0 gives empty matrices.  n_assets = 1 is valid: the asset matrix is then the law of mcg_paths_gbm, from the
+ * be odd, n_paths = 0 gives empty matrices.  Asset a depends on S0, q and sigma of the assets 0 .. a and on the leading
+ * (a + 1) x (a + 1) block of corr only, bit for bit, whatever n_assets is: row a of the Banachiewicz loop reads nothing beyond
+ * that block, and e_a sums the drivers b <= a in one fixed order -- the first d asset matrices of a call are the matrices of
+ * the d-asset call on the leading block (tests/test_gpu_gbm_multi.py: test_asset_prefixes_are_bit_identical, d = 1 .. 8;
+ * tests/test_gbm_multi_reference.py for the factor and for the scheme).  n_assets = 1 is valid: the asset matrix is then the law of mcg_paths_gbm, from the
  * same stream (not its bits: that kernel folds sigma into the logarithm).  Asset matrices are marked `generated`; a combined
  * matrix is `generated` iff all its inputs are, for both entry points: dS_T/dr = T S_T holds for sums, max and min
  * (mcg_greeks_european's rho).  One launch, booked under MCG_K_MULTI.

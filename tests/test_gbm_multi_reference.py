@@ -2,8 +2,9 @@
 yardstick of tests/test_gpu_gbm_multi.py: the contract of include/mcgpu.h line for line on the Philox normals of
 tests/test_heston_reference.py; the Cholesky factor as a loop in Python floats, which mcg_cholesky_corr must reproduce bit for
 bit; the reference's own rounding error on the parity cases (binary64 against 80-bit steps); the law of the scheme against
-closed forms (forwards, correlations, Margrabe's exchange option from a spread, from a best-of and from a worst-of); and what
-the library must answer without a GPU."""
+closed forms (forwards, correlations, Margrabe's exchange option from a spread, from a best-of and from a worst-of; every mean
+and covariance of the log-returns of eight assets); that the first assets of a model, factor and scheme, do not depend on how
+many follow; and what the library must answer without a GPU."""
 import ctypes as C
 import math
 
@@ -93,7 +94,8 @@ def banded(n, rho):
 
 # ---- the element-wise cases (reused by tests/test_gpu_gbm_multi.py) -----------------------------------------------------------
 # name -> model; every set runs over the shapes of test_heston_reference.PARITY_SHAPES (Philox tails 0..3, path counts that are
-# no multiples of 512, an odd path_begin, ids above 2^33, both seeds), "three" over one long shape too.  Basket weights hold a
+# no multiples of 512, an odd path_begin, ids above 2^33, both seeds), "three" and "dense-5" over one long shape too (the dense
+# sets follow below: with them every asset count from one to eight has a set).  Basket weights hold a
 # negative one (a spread) wherever there are two assets; best-of / worst-of take 1 / S0.
 MULTI_SETS = {
     "one": dict(S0=[100.0], sigma=[0.2], corr=[[1.0]], q=None, weights=[0.7]),
@@ -107,9 +109,30 @@ MULTI_SETS = {
 }
 LONG_SHAPE = (252, 1300, 777, SEED64)
 
+# A dense correlation matrix without Toeplitz structure, C_ij = s_i s_j exp(-|x_i - x_j|): the signed Ornstein-Uhlenbeck kernel
+# on uneven points, exactly symmetric with an exact unit diagonal in Python floats (smallest squared pivot 0.095, smallest
+# eigenvalue 0.047).  Below its first column the factor of banded(n, rho) depends on a - b alone, L_ab = rho^(a-b) sqrt(1 - rho^2),
+# so a triangle index that is off by one row and one column reads the same number there; this factor has entries of both signs
+# and no two alike.  Every sigma is positive (every driver moves every later asset) and the basket weights hold negative ones.
+DENSE_X = [0.0, 0.3, 0.35, 1.1, 1.5, 2.6, 2.7, 4.0]
+DENSE_SIGN = [1.0, -1.0, 1.0, 1.0, -1.0, 1.0, -1.0, -1.0]
+DENSE_CORR = [[DENSE_SIGN[i] * DENSE_SIGN[j] * math.exp(-abs(DENSE_X[i] - DENSE_X[j])) for j in range(8)] for i in range(8)]
+DENSE_WEIGHTS = [0.2, -0.1, 0.15, -0.3, 0.05, 0.2, -0.1, 0.25]
+
+
+def dense_model(d):
+    """The first d assets of the dense eight-asset model: the leading d x d block of its correlation matrix."""
+    e = MULTI_SETS["eight"]
+    return dict(S0=e["S0"][:d], sigma=e["sigma"][:d], corr=[row[:d] for row in DENSE_CORR[:d]], q=e["q"][:d], weights=DENSE_WEIGHTS[:d])
+
+
+DENSE_NAMES = {4: "dense-4", 5: "dense-5", 6: "dense-6", 7: "dense-7", 8: "dense-eight"}
+MULTI_SETS.update({name: dense_model(d) for d, name in DENSE_NAMES.items()})
+
 
 def shapes_of(name):
-    return PARITY_SHAPES + ((LONG_SHAPE,) if name == "three" else ())
+    """"dense-5" takes the long shape as well: k_gbm_multi<5, ., .> is the instantiation with the tightest register allocation."""
+    return PARITY_SHAPES + ((LONG_SHAPE,) if name in ("three", "dense-5") else ())
 
 
 def model_args(m):
@@ -175,10 +198,37 @@ def check_statistics(s, ST, spread, best, worst, where):
         assert abs(got - want) <= STD_ERRORS * se, (where, k, got, want, se)
 
 
+def check_covariances(model, ST, where):
+    """ST: [d][n] terminal prices of `model` (S0, sigma, corr, q) at STAT_T.  The log-returns are jointly normal with means
+    (r - q_a - sigma_a^2 / 2) T and covariances sigma_a sigma_b C_ab T: every mean and every entry of the sample covariance
+    matrix within STD_ERRORS closed-form standard errors, which are exact for a normal sample of size n -- sigma_a sqrt(T / n)
+    for a mean, sqrt((var_a var_b + cov_ab^2) / (n - 1)) for a covariance.  Nothing here comes from the sample but the estimates.
+    Returns the worst deviations (covariances, means) in standard errors."""
+    d, n = ST.shape
+    sigma, q, corr = model["sigma"], model["q"] or [0.0] * d, model["corr"]
+    lr = np.log(ST / np.array(model["S0"])[:, None])
+    mean, cov = lr.mean(axis=1), np.cov(lr, ddof=1).reshape(d, d)
+    means, covs = [], []            # (deviation in standard errors, what, got, want, se)
+    for a in range(d):
+        want = (R - q[a] - sigma[a] * sigma[a] / 2.0) * STAT_T
+        se = sigma[a] * math.sqrt(STAT_T / n)
+        means.append((abs(float(mean[a]) - want) / se, (a,), float(mean[a]), want, se))
+        for b in range(a + 1):
+            want = sigma[a] * sigma[b] * corr[a][b] * STAT_T
+            se = math.sqrt((sigma[a] ** 2 * sigma[b] ** 2 * STAT_T ** 2 + want * want) / (n - 1))
+            covs.append((abs(float(cov[a, b]) - want) / se, (a, b), float(cov[a, b]), want, se))
+    print(f"{where}: {d} assets, {n} paths: worst of {len(covs)} covariances {max(covs)[0]:.2f} std errors at {max(covs)[1]}, "
+          f"worst of {d} means {max(means)[0]:.2f} at {max(means)[1]}")
+    for dev, *rest in means + covs:
+        assert dev <= STD_ERRORS, (where, dev, rest)
+    return max(covs)[0], max(means)[0]
+
+
 # ---- tests ----------------------------------------------------------------------------------------------------------------
 CHOLESKY_CASES = {"n1": [[1.0]], "n2": [[1.0, -0.3], [-0.3, 1.0]], "n2-0.999": [[1.0, 0.999], [0.999, 1.0]],
                   "n3": MULTI_SETS["three"]["corr"], "n3-0.999": [[1.0, 0.999, 0.5], [0.999, 1.0, 0.52], [0.5, 0.52, 1.0]],
-                  "n8": banded(8, 0.6), "n8-0.999": banded(8, 0.999), "n8-negative": banded(8, -0.7)}
+                  "n8": banded(8, 0.6), "n8-0.999": banded(8, 0.999), "n8-negative": banded(8, -0.7),
+                  **{name: MULTI_SETS[name]["corr"] for name in DENSE_NAMES.values()}}
 
 
 @pytest.mark.parametrize("name", sorted(CHOLESKY_CASES))
@@ -191,6 +241,46 @@ def test_cholesky_is_the_python_loop_bit_for_bit(name):
     e_c = float(np.abs(got @ got.T - c).max())
     print(f"{name}: against numpy.linalg.cholesky {e_np:.2e}, L L^T against C {e_c:.2e}")
     assert e_np <= 1e-14 and e_c <= 1e-15
+
+
+def test_cholesky_of_a_leading_block_is_the_leading_block_of_the_factor():
+    """Row j of the Banachiewicz loop reads rows 0 .. j of C and of L only, so the factor of the leading d x d block is the
+    leading block of the factor, bit for bit -- what makes asset a of mcg_paths_gbm_multi independent of n_assets."""
+    c = np.array(DENSE_CORR)
+    full, full_py = mc.cholesky_corr(c), cholesky_python(c)
+    assert full.tobytes() == full_py.tobytes()
+    assert len({abs(float(full[a, b])) for a in range(8) for b in range(a + 1)}) == 36       # no two entries alike ...
+    assert (np.tril(full) < 0.0).any() and (np.tril(full, -1) > 0.0).any()                 # ... and both signs
+    for d in range(1, 8):
+        block = np.ascontiguousarray(c[:d, :d])
+        want = np.ascontiguousarray(full[:d, :d])
+        assert mc.cholesky_corr(block).tobytes() == want.tobytes(), d
+        assert cholesky_python(block).tobytes() == want.tobytes(), d
+
+
+def test_dense_model_is_what_it_says():
+    c = np.array(DENSE_CORR)
+    assert np.array_equal(c, c.T) and (np.diag(c) == 1.0).all()
+    pivots = np.diag(cholesky_python(c)) ** 2
+    eig = np.linalg.eigvalsh(c)
+    print(f"dense model: smallest squared pivot {pivots.min():.3f}, smallest eigenvalue {eig.min():.3f}")
+    assert pivots.min() > 0.09 and eig.min() > 0.04
+    for d, name in DENSE_NAMES.items():
+        m = MULTI_SETS[name]
+        assert len(m["S0"]) == d and all(s > 0.0 for s in m["sigma"]) and min(m["weights"]) < 0.0
+        assert m["corr"] == [row[:d] for row in DENSE_CORR[:d]]
+
+
+def test_first_assets_of_the_scheme_do_not_depend_on_the_asset_count():
+    """e_a sums the drivers b <= a only, with constants of the leading block of the factor: the first d assets of the
+    eight-asset run are the d-asset run, bit for bit."""
+    for shape in PARITY_SHAPES:
+        n_steps, n_paths, begin, seed = shape
+        eight = reference("dense-eight", shape)
+        for d in range(1, 8):
+            part = reference(DENSE_NAMES[d], shape) if d in DENSE_NAMES else gbm_multi_numpy(
+                seed, dt=DT, n_steps=n_steps, n_paths=n_paths, path_begin=begin, **model_args(dense_model(d)))
+            assert part.shape == (d, n_steps + 1, n_paths) and part.tobytes() == eight[:d].tobytes(), (shape, d)
 
 
 def test_cholesky_may_work_in_place():
@@ -292,3 +382,13 @@ def test_scheme_against_the_closed_forms(name):
     ST = gbm_multi_numpy(STAT_SEED, dt=STAT_T / STAT_STEPS, n_steps=STAT_STEPS, n_paths=STAT_PATHS_CPU, terminal_only=True,
                          **stat_model(s))
     check_statistics(s, ST, combine_numpy(ST, BASKET, [1.0, -1.0]), combine_numpy(ST, BEST_OF), combine_numpy(ST, WORST_OF), name)
+
+
+def test_scheme_against_the_covariance_law():
+    """All 36 covariances and 8 means of the dense model's log-returns.  (The reference on this seed: 2.20 and 1.58 standard
+    errors at 200 000 paths, 1.79 and 1.78 on the first 1M, the GPU file's sample.)"""
+    m = dense_model(8)
+    ST = gbm_multi_numpy(STAT_SEED, dt=STAT_T / STAT_STEPS, n_steps=STAT_STEPS, n_paths=STAT_PATHS_CPU, terminal_only=True,
+                         **model_args(m))
+    check_covariances(m, ST, "numpy, dense model")
+    check_covariances(dense_model(5), ST[:5], "numpy, its first five assets")

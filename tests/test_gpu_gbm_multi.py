@@ -6,11 +6,16 @@ generators, for its refusals, through the consumers of a path matrix and against
 Parity bounds: S is compared relatively.  The device draws the same normals with its own logarithm, sine / cosine and square
 root, sums an exponent with fused multiply-adds and takes its own exponential (<= ~2 ulp each), so the difference from numpy
 is rounding that accumulates over the steps.  S_BOUND is ten times the largest error observed on an MI355X over all cases of
-this file (observed: 1.60e-14, on the 252-step shape of the "three" set), far inside the 1e-9 it may not exceed; GBM_BOUND, for
+this file (observed: 1.60e-14, on the 252-step shape of the "three" set; the dense sets of four to eight assets stay within
+6.66e-15, on the 252-step shape of "dense-5"), far inside the 1e-9 it may not exceed; GBM_BOUND, for
 the one-asset matrix against mcg_paths_gbm, is ten times the 4.11e-15 observed there (252 steps, sigma = 1.5), inside the
 project's GBM bound of 1e-11.  A best-of / worst-of matrix equals combine_numpy of the downloaded asset matrices bit for bit
 (one rounded product per asset, then max / min); a basket differs from it by the fused additions only: (D + 1) 2^-52 on the
-scale sum |w_a| S^a (observed: 2.67e-16).  The order-3 American max-call of test_american_max_call_through_lsm2 came out at
+scale sum |w_a| S^a (observed: 2.69e-16 from the fused kernels; 3.51e-16 from mcg_paths_combine of up to eight uploaded
+matrices with entries of both signs).  Every k_gbm_multi<D, ., .>, D = 1 .. 8 in its three store forms, runs under an element-wise
+assertion here: the parity test on sets of every asset count, the prefix identity that ties asset a of every D to the
+eight-asset run, and every asset of every D out of the combined-only kernel alone; k_paths_combine runs at every n_assets and
+on more rows than its grid's y holds.  The order-3 American max-call of test_american_max_call_through_lsm2 came out at
 13.8977 +- 0.0156 beside the published 13.902."""
 import ctypes as C
 import math
@@ -22,10 +27,11 @@ import montecarlooptionspricer_amd as mc
 from montecarlooptionspricer_amd import _native as N
 from test_exotics_reference import stats_numpy
 from test_gbm_multi_reference import (BASKET, BEST_OF, DT, KINDS, MULTI_SETS, R, STAT_SETS, STAT_STEPS, STAT_T, WORST_OF,
-                                      check_statistics, combine_numpy, model_args, reference, shapes_of, stat_model)
+                                      check_covariances, check_statistics, combine_numpy, dense_model, model_args, reference,
+                                      shapes_of, stat_model)
 from test_gpu_exotics import check_prices, full_book
 from test_gpu_lsm2 import PRICE_BOUND as LSM2_PRICE_BOUND
-from test_heston_reference import PARAMS, STAT_SEED
+from test_heston_reference import PARAMS, SEED64, STAT_SEED
 from test_lsm2_reference import lsm2_numpy
 
 pytestmark = pytest.mark.gpu
@@ -125,9 +131,58 @@ def test_one_asset_agrees_with_the_gbm_generator(eng):
             assert e <= GBM_BOUND, (n_steps, n_paths, sigma, e)
 
 
-def test_bit_identities(eng):
-    m = MULTI_SETS["eight"]
-    gen = dict(seed=77, dt=DT, n_steps=10, n_paths=1301, path_begin=4097, **model_args(m))
+# The two shapes of the tests that tie the instantiations to each other: Philox tails 3 and 0, a last workgroup whose upper waves
+# lie beyond the row with an odd path_begin above 2^33, and two workgroups.
+TIE_SHAPES = ((7, 513, 2 ** 33 + 1, SEED64), (8, 1000, 0, 7))
+
+
+def test_asset_prefixes_are_bit_identical(eng):
+    """Asset a of the d-asset run has the bits of asset a of the eight-asset run, d = 1 .. 8: e_a sums the drivers b <= a only,
+    in increasing b with explicit fused multiply-adds on constants of the leading block of the factor, and takes the same
+    exponential, so the eight instantiations must agree -- no reference involved."""
+    for n_steps, n_paths, begin, seed in TIE_SHAPES:
+        gen = dict(seed=seed, dt=DT, n_steps=n_steps, n_paths=n_paths, path_begin=begin)
+        eight = host(eng.gbm_multi(**gen, **model_args(dense_model(8)))[0])
+        assert eight.shape == (8, n_steps + 1, n_paths) and (eight > 0.0).all() and len({bits(eight[a, 1:]) for a in range(8)}) == 8
+        differing = []
+        for d in range(1, 9):
+            S = host(eng.gbm_multi(**gen, **model_args(dense_model(d)))[0])
+            assert S.shape == (d, n_steps + 1, n_paths)
+            differing += [(d, a, int((S[a] != eight[a]).sum())) for a in range(d) if bits(S[a]) != bits(eight[a])]
+        print(f"{n_steps} x {n_paths}: 36 (d, asset) pairs against the eight-asset run, differing (d, asset, elements): {differing}")
+        assert not differing, (n_steps, n_paths, differing)
+
+
+def isolating_weights(kind, d, a):
+    """Weights under which the combination of d positive prices is the price of asset a, exactly: a basket of 0 * S = +0 and
+    fma(0, S, acc) = acc; a best-of whose other products, 1e-300 S, lie below every price; a worst-of whose others, 1e300 S, lie
+    above."""
+    other = {BASKET: 0.0, BEST_OF: 1e-300, WORST_OF: 1e300}[kind]
+    return [1.0 if b == a else other for b in range(d)]
+
+
+def test_every_asset_through_the_combined_only_kernel(eng):
+    """k_gbm_multi<d, false, true> stores no asset, and the parity test sees its prices through a sum, a max or a min only:
+    here each asset of each d comes out of it alone and must have the bits the assets-only kernel stored, rows 0 .. n_steps."""
+    n_steps, n_paths, begin, seed = TIE_SHAPES[0]
+    differing, compared = [], 0
+    for d in range(1, 9):
+        gen = dict(seed=seed, dt=DT, n_steps=n_steps, n_paths=n_paths, path_begin=begin, **model_args(dense_model(d)))
+        S = host(eng.gbm_multi(**gen)[0])
+        for a in range(d):
+            for kind in KINDS:
+                none, comb = eng.gbm_multi(combine=kind, weights=isolating_weights(kind, d, a), want_assets=False, **gen)
+                c = host([comb])[0]
+                compared += 1
+                assert none is None and c.shape == S[a].shape
+                if bits(c) != bits(S[a]):
+                    differing.append((d, a, kind, int((c != S[a]).sum())))
+    print(f"{compared} combined-only matrices against the stored assets, differing (d, asset, kind, elements): {differing}")
+    assert compared == 108 and not differing, differing
+
+
+def check_bit_identities(eng, m, gen):
+    """Fused == combine(assets), three shards == one call, repeats == the first call, for every kind."""
     assets, _ = eng.gbm_multi(**gen)
     S = host(list(assets))
     for kind in KINDS:
@@ -151,10 +206,86 @@ def test_bit_identities(eng):
         eng.heston(5, 100.0, R, dt=DT, n_steps=5, n_paths=700, **PARAMS["feller"]).free()
         _, third = eng.gbm_multi(combine=kind, weights=w, want_assets=False, **gen)
         assert bits(host([again])[0]) == bits(f) and bits(host([third])[0]) == bits(f), kind
+
+
+def test_bit_identities(eng):
+    m = MULTI_SETS["eight"]
+    gen = dict(seed=77, dt=DT, n_steps=10, n_paths=1301, path_begin=4097, **model_args(m))
+    check_bit_identities(eng, m, gen)
     # no weights: all ones
     _, c1 = eng.gbm_multi(combine=BASKET, want_assets=False, **gen)
     _, c2 = eng.gbm_multi(combine=BASKET, weights=[1.0] * 8, want_assets=False, **gen)
     assert bits(host([c1])[0]) == bits(host([c2])[0])
+
+
+def test_bit_identities_of_five_assets(eng):
+    """The same at an asset count other than eight, on the dense model: the three k_gbm_multi<5, ., .>, the instantiations with
+    the tightest register allocation, and k_paths_combine of five matrices."""
+    m = MULTI_SETS["dense-5"]
+    gen = dict(seed=SEED64, dt=DT, n_steps=10, n_paths=1301, path_begin=2 ** 33 + 4097, **model_args(m))
+    check_bit_identities(eng, m, gen)
+    print("dense-5, 10 x 1301 from an odd path_begin above 2^33: fused == combine(assets), shards of 513 / 0 / 788 paths and two "
+          "repeats after other work: bit-identical in every kind")
+
+
+def test_combine_at_every_count(eng):
+    """k_paths_combine takes n_assets at run time: n = 1 .. 8 uploaded matrices in every kind, two workgroups and an odd path
+    count.  The basket takes entries and weights of both signs; best-of and worst-of positive ones, as the contract asks."""
+    n_paths, n_cols = 701, 6
+    rng = np.random.default_rng(8)
+    signed = 100.0 * rng.standard_normal((8, n_paths, n_cols))
+    assert (signed < 0.0).any() and (signed > 0.0).any()
+    w_signed = [0.2, -0.1, 0.15, -0.3, 0.05, 0.2, -0.1, 0.25]
+    w_positive = [1.0, 1.1, 0.9, 1.3, 0.7, 1.05, 0.95, 1.2]
+    positive = np.abs(signed) + 1.0
+    up_signed, up_positive = ([eng.from_host(x[a]) for a in range(8)] for x in (signed, positive))
+    worst = 0.0
+    for n in range(1, 9):
+        for kind in KINDS:
+            x, up, w = (signed, up_signed, w_signed[:n]) if kind == BASKET else (positive, up_positive, w_positive[:n])
+            parts = x[:n].transpose(0, 2, 1)                # [n][n_cols][n_paths], as stored
+            M = eng.combine(up[:n], kind, w)
+            assert (M.n_paths, M.n_steps) == (n_paths, n_cols - 1)
+            got = host([M])[0]
+            if kind == BASKET:
+                e = basket_error(got, parts, w)
+                worst = max(worst, e)
+                observed["combine basket"] = max(observed.get("combine basket", 0.0), e)
+                assert e <= (n + 1) * EPS, (n, e)
+            else:
+                assert bits(got) == bits(combine_numpy(parts, kind, w)), (n, kind)
+    print(f"combine of 1 .. 8 uploaded matrices: best-of and worst-of bit-identical to numpy, basket within {worst:.2e} of it "
+          "on the scale sum |w_a S^a|")
+    for M in up_signed + up_positive:
+        M.free()
+
+
+def test_combine_beyond_the_grid_clamp(eng):
+    """k_paths_combine walks rows on blockIdx.y, which the launcher clamps to 65 535: on a matrix of 65 601 rows the rows from
+    65 535 on are written by the second trip of its stride loop alone."""
+    n_paths, n_rows, clamp = 3, 65_601, 65_535
+    rng = np.random.default_rng(65_601)
+    x = 100.0 * np.exp(0.2 * rng.standard_normal((2, n_paths, n_rows)))
+    up = [eng.from_host(x[a]) for a in range(2)]
+    assert all((U.n_paths, U.n_steps) == (n_paths, n_rows - 1) for U in up)
+    parts = x.transpose(0, 2, 1)
+    for kind, w in ((BASKET, [1.0, -0.75]), (BEST_OF, [1.0, 0.9]), (WORST_OF, [1.0, 0.9])):
+        M = eng.combine(up, kind, w)
+        got = M.to_host().T
+        M.free()
+        want = combine_numpy(parts, kind, w)
+        assert got.shape == want.shape == (n_rows, n_paths)
+        if kind == BASKET:
+            e, e2 = basket_error(got, parts, w), basket_error(got[clamp:], parts[:, clamp:], w)
+            print(f"{kind} of two 3 x 65 601 matrices: {e:.2e} of numpy on the scale sum |w_a S^a|, rows 65 535 .. 65 600 {e2:.2e}")
+            observed["combine basket"] = max(observed.get("combine basket", 0.0), e)
+            assert e2 <= 3 * EPS and e <= 3 * EPS, (e, e2)
+        else:
+            wrong, wrong2 = int((got != want).sum()), int((got[clamp:] != want[clamp:]).sum())
+            print(f"{kind} of two 3 x 65 601 matrices: {wrong} elements differ from numpy, {wrong2} in rows 65 535 .. 65 600")
+            assert bits(got[clamp:]) == bits(want[clamp:]) and bits(got) == bits(want), kind
+    for U in up:
+        U.free()
 
 
 def test_combine_on_matrices_of_other_generators(eng):
@@ -337,6 +468,19 @@ def test_statistics_against_the_closed_forms(eng, name):
     _, worst = eng.gbm_multi(combine=WORST_OF, want_assets=False, **gen)
     ST = host(assets)[:, -1]
     check_statistics(s, ST, host([spread])[0][-1], host([best])[0][-1], host([worst])[0][-1], name)
+
+
+def test_covariance_law_of_eight_and_five_assets(eng):
+    """All 36 + 15 covariances and 8 + 5 means of the terminal log-returns of the dense model against sigma_a sigma_b C_ab T and
+    (r - q_a - sigma_a^2 / 2) T, within 4 closed-form standard errors: the check that shares neither the reference's reading
+    of the packed triangle nor its stream numbers.  (numpy on the same 1M paths: 1.79 and 1.78 standard errors.)"""
+    for d in (8, 5):
+        m = dense_model(d)
+        assets, _ = eng.gbm_multi(seed=STAT_SEED, dt=STAT_T / STAT_STEPS, n_steps=STAT_STEPS, n_paths=STAT_PATHS, **model_args(m))
+        ST = np.stack([a.to_host_step_major()[-1] for a in assets])
+        for a in assets:
+            a.free()
+        check_covariances(m, ST, f"MI355X, dense model, {d} assets")
 
 
 def test_launch_accounting(eng):

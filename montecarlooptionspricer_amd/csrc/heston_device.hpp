@@ -15,7 +15,7 @@
 #pragma once
 #include "devmath.hpp"
 #include "fastmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -121,40 +121,24 @@ int launch_heston_scheme(mcg_ctx* ctx, mcg_paths* P, mcg_paths* V, uint64_t seed
     if (n_blocks < 0) return MCG_ERR_INVALID;
     if (V && (V->ld != P->ld || V->n_steps != P->n_steps))
         return fail(MCG_ERR_INVALID, "the variance matrix must have the shape of the price matrix");
-    if (want_payoff) {
-        int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
-        if (rc) return rc;
-    }
+    const PathLaunch launch{ctx, n_blocks, P, want_payoff, K, is_call};
+    const int rc = launch.reserve();
+    if (rc) return rc;
     HestonArgs<typename Scheme::Consts> a;
-    a.out = P->data;
+    set_shape_key(a, P, seed);
+    set_payoff(a, ctx, K, is_call);
     a.var = V ? V->data : nullptr;
-    a.ld = P->ld;
-    a.n_paths = P->n_paths;
-    a.n_steps = P->n_steps;
-    a.path_begin = P->path_begin;
-    a.k0 = (uint32_t)seed;
-    a.k1 = (uint32_t)(seed >> 32);
     a.S0 = S0;
     a.v0 = v0;
     a.c = c;
-    a.K = K;
-    a.is_call = is_call;
-    a.partials = ctx->partials;
     a.tabs = (const double2*)ctx->log_tab;
-    {
-        TimedLaunch t(ctx, MCG_K_HESTON);
-        const dim3 grid((unsigned)n_blocks), block(256);
-        if (want_payoff) {
-            if (V) hipLaunchKernelGGL((k_heston_paths<Scheme, true, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_heston_paths<Scheme, true, false>), grid, block, 0, ctx->stream, a);
-        } else {
-            if (V) hipLaunchKernelGGL((k_heston_paths<Scheme, false, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_heston_paths<Scheme, false, false>), grid, block, 0, ctx->stream, a);
-        }
-    }
-    MCG_HIP(hipGetLastError());
-    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
-    return MCG_OK;
+    return launch.run(MCG_K_HESTON, [&] {
+        dispatch_flags(
+            [&](auto payoff, auto var) {
+                hipLaunchKernelGGL((k_heston_paths<Scheme, payoff.value, var.value>), dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, a);
+            },
+            want_payoff, V != nullptr);
+    });
 }
 
 }  // namespace mcg

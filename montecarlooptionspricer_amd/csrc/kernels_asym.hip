@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "devmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 
 namespace mcg {
 
@@ -55,21 +55,16 @@ int run_asymptotic(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
     const int n_dates = (int)bnd.size();
     int grid = (int)std::min<int64_t>((P->n_paths + 255) / 256, (int64_t)ctx->n_cus * 8);
     if (grid < 1) grid = 1;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)2 * std::max(n_dates, 1));
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * grid);
     if (rc) return rc;
-    rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * grid);
+    HostPiece up[] = {{bnd.data(), (size_t)n_dates * sizeof(double)}, {disc.data(), (size_t)n_dates * sizeof(double)}};
+    rc = upload_params(ctx, up);  // (no dates: nothing is copied)
     if (rc) return rc;
-    if (n_dates > 0) {
-        MCG_HIP(hipMemcpyAsync(ctx->weights, bnd.data(), (size_t)n_dates * sizeof(double), hipMemcpyHostToDevice,
-                               ctx->stream));
-        MCG_HIP(hipMemcpyAsync(ctx->weights + n_dates, disc.data(), (size_t)n_dates * sizeof(double),
-                               hipMemcpyHostToDevice, ctx->stream));
-        MCG_HIP(hipStreamSynchronize(ctx->stream));  // the host vectors die at return
-    }
+    if (n_dates > 0) MCG_HIP(hipStreamSynchronize(ctx->stream));  // the host vectors die at return (upload_params)
     {
         TimedLaunch t(ctx, MCG_K_ASYM);
         hipLaunchKernelGGL(k_asym_scan, dim3(grid), dim3(256), 0, ctx->stream, P->data, P->ld, P->n_paths, n_dates,
-                           ctx->weights, ctx->weights + n_dates, K, is_call, ctx->partials);
+                           up[0].at, up[1].at, K, is_call, ctx->partials);
     }
     MCG_HIP(hipGetLastError());
     double s[3];

@@ -14,7 +14,7 @@
 // The reference draws from an unseeded shared mt19937, so parity of the upper bound is statistical; the lower
 // bound is deterministic.  Sharded use resamples within the local shard (the matrix is never exchanged).
 #include "devmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 
 namespace mcg {
 
@@ -570,32 +570,29 @@ int run_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
 
     int grid = (int)std::min<int64_t>((P->n_paths + 255) / 256, (int64_t)ctx->n_cus * 8);
     if (grid < 1) grid = 1;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)n_cols + (ex.size() + 1) / 2 + 1);
-    if (rc) return rc;
     // k_branch_bounds: launches of one resident wave of workgroups (all of them walk the dates -- and the slices of a
     // date's row -- together), BR_PPT paths per thread
     const int64_t per_wg = 256 * (int64_t)BR_PPT;
     const int bgrid = (int)std::max<int64_t>(1, std::min<int64_t>((P->n_paths + per_wg - 1) / per_wg, (int64_t)ctx->n_cus * BR_WGS_PER_CU));
     const int64_t per_launch = (int64_t)bgrid * per_wg;
     const int64_t n_launches = std::max<int64_t>(1, (P->n_paths + per_launch - 1) / per_launch);
-    rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * (size_t)std::max<int64_t>(grid, bgrid * n_launches));
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * (size_t)std::max<int64_t>(grid, bgrid * n_launches));
     if (rc) return rc;
     void* Fbuf = nullptr;
     rc = pool_alloc(ctx, P->bytes, &Fbuf);
     if (rc) return rc;
-    int* d_ex = reinterpret_cast<int*>(ctx->weights + n_cols);
-    hipError_t e1 = hipMemcpyAsync(ctx->weights, disc.data(), (size_t)n_cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    hipError_t e2 = ex.empty() ? hipSuccess
-                               : hipMemcpyAsync(d_ex, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    hipError_t e3 = hipStreamSynchronize(ctx->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+    HostPiece par[] = {{disc.data(), (size_t)n_cols * sizeof(double)}, {ex.data(), ex.size() * sizeof(int)}};
+    rc = upload_params(ctx, par);
+    // disc and ex die at return (upload_params)
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MCG_OK) rc = fail(MCG_ERR_HIP, "BranchingProcesses: table upload failed");
+    if (rc) {
         pool_release(ctx, Fbuf, P->bytes);
-        return fail(MCG_ERR_HIP, "BranchingProcesses: table upload failed");
+        return rc;
     }
     {
         TimedLaunch t(ctx, MCG_K_BRANCHING);
         hipLaunchKernelGGL(k_branch_suffix, dim3(grid), dim3(256), 0, ctx->stream, P->data, (double*)Fbuf, P->ld, P->n_paths,
-                           n_cols, n_dates, ctx->weights, K, is_call);
+                           n_cols, n_dates, par[0].at, K, is_call);
     }
     BranchArgs a;
     a.S = P->data;
@@ -605,8 +602,8 @@ int run_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
     a.path_begin = P->path_begin;
     a.k0 = (uint32_t)seed;
     a.k1 = (uint32_t)(seed >> 32);
-    a.ex = d_ex;
-    a.disc = ctx->weights;
+    a.ex = reinterpret_cast<const int*>(par[1].at);
+    a.disc = par[0].at;
     a.n_ex = (int)ex.size();
     a.ex_last = ex_last;
     a.n_cols = n_cols;

@@ -10,7 +10,7 @@
 
 #include "devmath.hpp"
 #include "exotic_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 
 namespace mcg {
 
@@ -187,36 +187,37 @@ int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo,
     const int n_rows = P->n_steps - first_row + 1;
     const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0;
     const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
-    const int64_t n_blocks = (lanes + 255) / 256;
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    const dim3 grid((unsigned)n_blocks), block(256);
-    {
-        TimedLaunch t(ctx, MCG_K_EXOTIC);
-#define MCG_XS_LAUNCH(GEO, W) \
-    hipLaunchKernelGGL((k_path_stats<GEO, W>), grid, block, 0, ctx->stream, P->data, P->ld, P->n_paths, first_row, n_rows, d_stats)
-        if (geo && wide) MCG_XS_LAUNCH(true, 2);
-        else if (geo) MCG_XS_LAUNCH(true, 1);
-        else if (wide) MCG_XS_LAUNCH(false, 2);
-        else MCG_XS_LAUNCH(false, 1);
-#undef MCG_XS_LAUNCH
-    }
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    const int64_t n_blocks = launch_units((lanes + 255) / 256);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
+    return PathLaunch{ctx, n_blocks}.run(MCG_K_EXOTIC, [&] {
+        dispatch_flags(
+            [&](auto g, auto w) {
+                hipLaunchKernelGGL((k_path_stats<g.value, w.value ? 2 : 1>), dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, P->data,
+                                   P->ld, P->n_paths, first_row, n_rows, d_stats);
+            },
+            geo, wide);
+    });
 }
 
-int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5) {
-    const size_t bytes = (size_t)XS_Q * P->n_paths * sizeof(double);
+int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch) {
+    const size_t bytes = (size_t)XS_Q * n_paths * sizeof(double);
     void* ws = nullptr;
     int rc = pool_alloc(ctx, bytes, &ws);
     if (rc) return rc;
-    rc = launch_path_stats(ctx, P, first_row, true, (double*)ws);
+    rc = launch((double*)ws);
     if (rc == MCG_OK) {
         hipError_t e = hipMemcpyAsync(host_out5, ws, bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = fail(MCG_ERR_HIP, "download of the path statistics failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(MCG_ERR_HIP, "download of the %s statistics failed: %s", what, hipGetErrorString(e));
+    } else {
+        (void)hipStreamSynchronize(ctx->stream);
     }
     pool_release(ctx, ws, bytes);
     return rc;
+}
+
+int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5) {
+    return download_stats(ctx, P->n_paths, host_out5, "path", [&](double* d) { return launch_path_stats(ctx, P, first_row, true, d); });
 }
 
 // The all-reduce of a payload that may exceed what the node-local collective carries in one call.
@@ -234,29 +235,38 @@ static int exotic_sums(mcg_ctx* ctx, const mcg_paths* P, int first_row, const mc
     const int n_sums = 2 * nc + 1, n_chunks = (nc + XB_CH - 1) / XB_CH;
     const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
     const size_t n_part = (size_t)n_chunks * n_blocks * XB_NF;
-    const size_t bytes = ((size_t)XS_Q * n + n_part + n_sums) * sizeof(double);
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)nc * sizeof(mcg_exotic) / sizeof(double));
-    if (rc) return rc;
+    return exotic_sums_frame(ctx, n, (size_t)XS_Q * n + n_part + n_sums, n_sums, h, [&](double* d_stats, double* d_sums) -> int {
+        double* d_part = d_stats + XS_Q * n;
+        bool geo = false;
+        for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
+        HostPiece up[] = {{book, (size_t)nc * sizeof(mcg_exotic)}};
+        int rc = upload_params(ctx, up);
+        if (rc) return rc;
+        rc = launch_path_stats(ctx, P, first_row, geo, d_stats);
+        if (rc) return rc;
+        {
+            TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
+            hipLaunchKernelGGL(k_exotic_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, geo ? 1 : 0,
+                               reinterpret_cast<const mcg_exotic*>(up[0].at), nc, d_part);
+            hipLaunchKernelGGL(k_exotic_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
+        }
+        MCG_HIP(hipGetLastError());
+        return MCG_OK;
+    });
+}
+
+int exotic_sums_frame(mcg_ctx* ctx, int64_t n, size_t ws_doubles, int n_sums, std::vector<double>& h,
+                      const std::function<int(double* ws, double* d_sums)>& fill) {
     void* ws = nullptr;
-    rc = pool_alloc(ctx, bytes, &ws);
+    int rc = pool_alloc(ctx, ws_doubles * sizeof(double), &ws);
     if (rc) return rc;
-    double *d_stats = (double*)ws, *d_part = d_stats + XS_Q * n, *d_sums = d_part + n_part;
-    const mcg_exotic* d_book = reinterpret_cast<const mcg_exotic*>(ctx->weights);
+    double* d_sums = (double*)ws + (ws_doubles - n_sums);
     auto body = [&]() -> int {
         if (n > 0) {
-            bool geo = false;
-            for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
-            MCG_HIP(hipMemcpyAsync(ctx->weights, book, (size_t)nc * sizeof(mcg_exotic), hipMemcpyHostToDevice, ctx->stream));
-            const int r2 = launch_path_stats(ctx, P, first_row, geo, d_stats);
+            const int r2 = fill((double*)ws, d_sums);
             if (r2) return r2;
-            {
-                TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
-                hipLaunchKernelGGL(k_exotic_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, geo ? 1 : 0, d_book, nc, d_part);
-                hipLaunchKernelGGL(k_exotic_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
-            }
-            MCG_HIP(hipGetLastError());
         } else {
-            MCG_HIP(hipMemsetAsync(d_sums, 0, n_sums * sizeof(double), ctx->stream));  // an empty shard still takes part in the collective
+            MCG_HIP(hipMemsetAsync(d_sums, 0, n_sums * sizeof(double), ctx->stream));
         }
         if (ctx->allreduce) {
             const int r2 = exotic_allreduce_sums(ctx, d_sums, n_sums);
@@ -268,8 +278,8 @@ static int exotic_sums(mcg_ctx* ctx, const mcg_paths* P, int first_row, const mc
         return MCG_OK;
     };
     rc = body();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still use the workspace when it goes back to the pool
-    pool_release(ctx, ws, bytes);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    pool_release(ctx, ws, ws_doubles * sizeof(double));
     return rc;
 }
 

@@ -19,7 +19,7 @@
 #include "devmath.hpp"
 #include "exotic_device.hpp"
 #include "fastmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -205,12 +205,8 @@ static int launch_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* tw, int n_ste
     t.a = tw->sigma * std::sqrt(tw->dt);
     t.m = (tw->r - tw->q - 0.5 * tw->sigma * tw->sigma) * tw->dt;
     t.tabs = (const double2*)ctx->log_tab;
-    {
-        TimedLaunch tl(ctx, MCG_K_EXOTIC);
-        hipLaunchKernelGGL(k_gbm_twin_stats, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, t);
-    }
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    return PathLaunch{ctx, n_blocks}.run(
+        MCG_K_EXOTIC, [&] { hipLaunchKernelGGL(k_gbm_twin_stats, dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, t); });
 }
 
 static int twin_check(const mcg_gbm_twin* tw) {
@@ -222,20 +218,8 @@ static int twin_check(const mcg_gbm_twin* tw) {
 }
 
 static int run_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* tw, int n_steps, int first_row, int64_t n_paths, double* host_out5) {
-    const size_t bytes = (size_t)CV_Q * n_paths * sizeof(double);
-    void* ws = nullptr;
-    int rc = pool_alloc(ctx, bytes, &ws);
-    if (rc) return rc;
-    rc = launch_gbm_twin_stats(ctx, tw, n_steps, first_row, n_paths, (double*)ws);
-    if (rc == MCG_OK) {
-        hipError_t e = hipMemcpyAsync(host_out5, ws, bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = fail(MCG_ERR_HIP, "download of the twin statistics failed: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-    pool_release(ctx, ws, bytes);
-    return rc;
+    return download_stats(ctx, n_paths, host_out5, "twin",
+                          [&](double* d) { return launch_gbm_twin_stats(ctx, tw, n_steps, first_row, n_paths, d); });
 }
 
 static bool reads_g(const mcg_control& k) {
@@ -253,59 +237,39 @@ static int exotic_cv_sums(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* TP,
     const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
     const size_t n_part = (size_t)n_chunks * n_blocks * CV_NF;
     const size_t n_stats = (size_t)CV_Q * n * (twin ? 2 : 1);
-    const size_t bytes = (n_stats + n_part + n_sums) * sizeof(double);
     const size_t book_d = (size_t)nc * sizeof(mcg_exotic) / sizeof(double), ctl_d = (size_t)n_controls * sizeof(mcg_control) / sizeof(double);
     std::vector<double> params(book_d + ctl_d + (size_t)nc);  // 2 nc ints are nc doubles
     std::memcpy(params.data(), book, (size_t)nc * sizeof(mcg_exotic));
     if (n_controls) std::memcpy(params.data() + book_d, controls, (size_t)n_controls * sizeof(mcg_control));
     std::memcpy(params.data() + book_d + ctl_d, ctrl, (size_t)nc * 2 * sizeof(int));
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, params.size());
-    if (rc) return rc;
-    void* ws = nullptr;
-    rc = pool_alloc(ctx, bytes, &ws);
-    if (rc) return rc;
-    double *d_stats = (double*)ws, *d_twin = twin ? d_stats + CV_Q * n : nullptr, *d_part = d_stats + n_stats, *d_sums = d_part + n_part;
-    const mcg_exotic* d_book = reinterpret_cast<const mcg_exotic*>(ctx->weights);
-    const mcg_control* d_ctl = reinterpret_cast<const mcg_control*>(ctx->weights + book_d);
-    const int* d_ctrl = reinterpret_cast<const int*>(ctx->weights + book_d + ctl_d);
-    auto body = [&]() -> int {
-        if (n > 0) {
-            bool geo = false, geo_twin = false;
-            for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
-            for (int k = 0; k < n_controls; ++k) {
-                if (!reads_g(controls[k])) continue;
-                if (controls[k].on_twin) geo_twin = true;
-                else geo = true;
-            }
-            MCG_HIP(hipMemcpyAsync(ctx->weights, params.data(), params.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            int r2 = launch_path_stats(ctx, P, first_row, geo, d_stats);
-            if (r2) return r2;
-            if (TP) r2 = launch_path_stats(ctx, TP, first_row, geo_twin, d_twin);
-            else if (tw) r2 = launch_gbm_twin_stats(ctx, tw, P->n_steps, first_row, n, d_twin);
-            if (r2) return r2;
-            {
-                TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
-                hipLaunchKernelGGL(k_exotic_book_cv, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, d_twin, n, geo ? 1 : 0,
-                                   (geo_twin || tw) ? 1 : 0, d_book, d_ctl, d_ctrl, nc, d_part);
-                hipLaunchKernelGGL(k_exotic_cv_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
-            }
-            MCG_HIP(hipGetLastError());
-        } else {
-            MCG_HIP(hipMemsetAsync(d_sums, 0, n_sums * sizeof(double), ctx->stream));  // an empty shard still takes part in the collective
+    return exotic_sums_frame(ctx, n, n_stats + n_part + n_sums, n_sums, h, [&](double* d_stats, double* d_sums) -> int {
+        double *d_twin = twin ? d_stats + CV_Q * n : nullptr, *d_part = d_stats + n_stats;
+        bool geo = false, geo_twin = false;
+        for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
+        for (int k = 0; k < n_controls; ++k) {
+            if (!reads_g(controls[k])) continue;
+            if (controls[k].on_twin) geo_twin = true;
+            else geo = true;
         }
-        if (ctx->allreduce) {
-            const int r2 = exotic_allreduce_sums(ctx, d_sums, n_sums);
-            if (r2) return r2;
+        HostPiece up[] = {{params.data(), params.size() * sizeof(double)}};
+        int rc = upload_params(ctx, up);
+        if (rc) return rc;
+        rc = launch_path_stats(ctx, P, first_row, geo, d_stats);
+        if (rc) return rc;
+        if (TP) rc = launch_path_stats(ctx, TP, first_row, geo_twin, d_twin);
+        else if (tw) rc = launch_gbm_twin_stats(ctx, tw, P->n_steps, first_row, n, d_twin);
+        if (rc) return rc;
+        {
+            TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
+            hipLaunchKernelGGL(k_exotic_book_cv, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, d_twin, n, geo ? 1 : 0,
+                               (geo_twin || tw) ? 1 : 0, reinterpret_cast<const mcg_exotic*>(up[0].at),
+                               reinterpret_cast<const mcg_control*>(up[0].at + book_d), reinterpret_cast<const int*>(up[0].at + book_d + ctl_d),
+                               nc, d_part);
+            hipLaunchKernelGGL(k_exotic_cv_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
         }
-        h.resize(n_sums);
-        MCG_HIP(hipMemcpyAsync(h.data(), d_sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        MCG_HIP(hipStreamSynchronize(ctx->stream));
+        MCG_HIP(hipGetLastError());
         return MCG_OK;
-    };
-    rc = body();
-    if (rc) (void)hipStreamSynchronize(ctx->stream);  // nothing queued may still use the workspace or `params` afterwards
-    pool_release(ctx, ws, bytes);
-    return rc;
+    });
 }
 
 }  // namespace mcg

@@ -13,7 +13,7 @@
 
 #include "devmath.hpp"
 #include "fastmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 #ifndef MCG_GBM_TABLES
@@ -445,28 +445,18 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
                bool want_payoff, double K, int is_call) {
     const bool wide = gbm_takes_wide(ctx, P->n_paths);
     const int ppl = gbm_paths_per_lane(ctx, P->n_paths);
-    if ((P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns");
     // the units that leave partial sums and stamp the clock: workgroups of the narrow kernel, tiles of the wide one
-    const int64_t n_blocks = wide ? P->ld / WIDE_TILE : (P->n_paths + 256 * ppl - 1) / (256 * ppl);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
-    if (want_payoff) {
-        int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
-        if (rc) return rc;
-    }
+    const int64_t n_blocks = wide ? launch_units(P->ld / WIDE_TILE, P) : launch_blocks(P, ppl);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
+    const PathLaunch launch{ctx, n_blocks, P, want_payoff, K, is_call};
+    const int rc = launch.reserve();
+    if (rc) return rc;
     GbmArgs a;
-    a.out = P->data;
-    a.ld = P->ld;
-    a.n_paths = P->n_paths;
-    a.n_steps = P->n_steps;
-    a.path_begin = P->path_begin;
-    a.k0 = (uint32_t)seed;
-    a.k1 = (uint32_t)(seed >> 32);
+    set_shape_key(a, P, seed);
+    set_payoff(a, ctx, K, is_call);
     a.S0 = S0;
     a.drift = (r - 0.5 * sigma * sigma) * dt;
     a.vol = sigma * std::sqrt(dt);
-    a.K = K;
-    a.is_call = is_call;
-    a.partials = ctx->partials;
     a.log_tab = (const double2*)ctx->log_tab;
     a.sincos2 = (const double2*)ctx->sincos2_tab;
     a.ticket = reinterpret_cast<unsigned*>(ctx->scalars + SC_GBM_TICKET);
@@ -488,27 +478,18 @@ int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, d
     }
     if (wide) MCG_HIP(hipMemsetAsync(a.ticket, 0, sizeof(unsigned), ctx->stream));
     ctx->gbm_last_route = wide ? 2 : 1;
-    {
-        TimedLaunch t(ctx, MCG_K_GBM);
-        const bool small = std::fabs(a.drift) + std::fabs(a.vol) * fm::MAX_ABS_NORMAL <= fm::SMALL_EXP_BOUND;
-        const double reach = std::fabs(a.drift) + std::fabs(a.vol) * fm::MAX_ABS_NORMAL;
-        // vol^2 (-2 ln u) must stay a normal positive double for modes 2 and 3
-        const int mode = !small ? 0 : !(a.vol > 1e-100) ? 1 : reach <= fm::SMALL6_EXP_BOUND ? 3 : 2;
-        a.ls = fm::make_log_scale(a.vol * a.vol);
-        if (wide) {
-            if (want_payoff) launch_gbm_wide_mode<true>(ctx, a, mode);
-            else launch_gbm_wide_mode<false>(ctx, a, mode);
-        } else if (want_payoff) {
-            if (ppl == 2) launch_gbm_mode<true, 2>(ctx, a, mode, (unsigned)n_blocks);
-            else launch_gbm_mode<true, 1>(ctx, a, mode, (unsigned)n_blocks);
-        } else {
-            if (ppl == 2) launch_gbm_mode<false, 2>(ctx, a, mode, (unsigned)n_blocks);
-            else launch_gbm_mode<false, 1>(ctx, a, mode, (unsigned)n_blocks);
-        }
-    }
-    MCG_HIP(hipGetLastError());
-    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
-    return MCG_OK;
+    const double reach = std::fabs(a.drift) + std::fabs(a.vol) * fm::MAX_ABS_NORMAL;
+    // vol^2 (-2 ln u) must stay a normal positive double for modes 2 and 3
+    const int mode = !(reach <= fm::SMALL_EXP_BOUND) ? 0 : !(a.vol > 1e-100) ? 1 : reach <= fm::SMALL6_EXP_BOUND ? 3 : 2;
+    a.ls = fm::make_log_scale(a.vol * a.vol);
+    return launch.run(MCG_K_GBM, [&] {
+        dispatch_flags(
+            [&](auto payoff, auto two) {
+                if (wide) launch_gbm_wide_mode<payoff.value>(ctx, a, mode);
+                else launch_gbm_mode<payoff.value, two.value ? 2 : 1>(ctx, a, mode, (unsigned)n_blocks);
+            },
+            want_payoff, ppl == 2);
+    });
 }
 
 // Median (and range) of the stamping workgroups' clocks of the last GBM launch: cycles / (100 MHz ticks) x 0.1 GHz.

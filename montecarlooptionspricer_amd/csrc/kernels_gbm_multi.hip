@@ -17,7 +17,7 @@
 
 #include "devmath.hpp"
 #include "fastmath.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -227,10 +227,12 @@ __global__ __launch_bounds__(256) void k_paths_combine(CombineArgs a) {
 
 template <int D>
 static void launch_multi_d(mcg_ctx* ctx, const MultiArgs& a, bool assets, bool combined, unsigned n_blocks) {
-    const dim3 grid(n_blocks), block(256);
-    if (assets && combined) hipLaunchKernelGGL((k_gbm_multi<D, true, true>), grid, block, 0, ctx->stream, a);
-    else if (assets) hipLaunchKernelGGL((k_gbm_multi<D, true, false>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((k_gbm_multi<D, false, true>), grid, block, 0, ctx->stream, a);
+    dispatch_flags(
+        [&](auto sa, auto sc) {
+            if constexpr (sa.value || sc.value)  // (a launch stores something: launch_gbm_multi's callers see to it)
+                hipLaunchKernelGGL((k_gbm_multi<D, sa.value, sc.value>), dim3(n_blocks), dim3(256), 0, ctx->stream, a);
+        },
+        assets, combined);
 }
 
 // One launch of k_gbm_multi over the asset matrices (assets: n_assets handles of one shape, or null) and / or the combined
@@ -267,8 +269,7 @@ int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, in
     static_assert(sizeof(a.c) == sizeof(c), "MultiArgs::c carries a MultiConsts");
     std::memcpy(a.c, &c, sizeof c);
     a.tabs = (const double2*)ctx->log_tab;
-    {
-        TimedLaunch t(ctx, MCG_K_MULTI);
+    return PathLaunch{ctx, n_blocks}.run(MCG_K_MULTI, [&] {
         const bool sa = assets != nullptr, sc = comb != nullptr;
         const unsigned g = (unsigned)n_blocks;
         switch (n_assets) {
@@ -281,9 +282,7 @@ int launch_gbm_multi(mcg_ctx* ctx, mcg_paths* const* assets, mcg_paths* comb, in
             case 7: launch_multi_d<7>(ctx, a, sa, sc, g); break;
             default: launch_multi_d<8>(ctx, a, sa, sc, g); break;
         }
-    }
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    });
 }
 
 // One launch of k_paths_combine: out = combination of n_assets matrices of out's shape; weights: never null here.
@@ -302,13 +301,10 @@ int launch_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_ass
     a.n_rows = out->n_steps + 1;
     a.n_assets = n_assets;
     a.kind = kind;
-    {
-        TimedLaunch t(ctx, MCG_K_MULTI);
+    return PathLaunch{ctx, n_blocks}.run(MCG_K_MULTI, [&] {
         const dim3 grid((unsigned)n_blocks, (unsigned)std::min(a.n_rows, 65535)), block(256);
         hipLaunchKernelGGL(k_paths_combine, grid, block, 0, ctx->stream, a);
-    }
-    MCG_HIP(hipGetLastError());
-    return MCG_OK;
+    });
 }
 
 }  // namespace mcg

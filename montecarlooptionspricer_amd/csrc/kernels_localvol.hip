@@ -17,7 +17,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "localvol_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -146,49 +146,31 @@ int launch_localvol(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, const 
     if (n_blocks < 0) return MCG_ERR_INVALID;
     if (n_x < 2 || n_x > LOCALVOL_MAX_NX || (n_slices != 1 && n_slices != P->n_steps))
         return fail(MCG_ERR_INVALID, "local vol: a table of %d slices x %d nodes does not fit %d steps", n_slices, n_x, P->n_steps);
-    const size_t table_doubles = (size_t)n_slices * (size_t)(n_x - 1) * 2;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, table_doubles);
+    const PathLaunch launch{ctx, n_blocks, P, want_payoff, K, is_call};
+    int rc = launch.reserve();
     if (rc) return rc;
-    if (want_payoff) {
-        rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
-        if (rc) return rc;
-    }
-    MCG_HIP(hipMemcpyAsync(ctx->weights, table, table_doubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    // the caller's table may die at return: make sure the copy has been consumed (as launch_rbergomi does)
-    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    HostPiece up[] = {{table, (size_t)n_slices * (size_t)(n_x - 1) * sizeof(double2)}};
+    rc = upload_params(ctx, up);
+    if (rc) return rc;
+    MCG_HIP(hipStreamSynchronize(ctx->stream));  // the caller's table may die at return (upload_params)
     LocalVolArgs a;
-    a.out = P->data;
-    a.ld = P->ld;
-    a.n_paths = P->n_paths;
-    a.n_steps = P->n_steps;
+    set_shape_key(a, P, seed);
+    set_payoff(a, ctx, K, is_call);
     a.nx1 = n_x - 1;
-    a.path_begin = P->path_begin;
-    a.k0 = (uint32_t)seed;
-    a.k1 = (uint32_t)(seed >> 32);
     a.S0 = S0;
     a.inv_dx = c.inv_dx;
     a.u0 = c.u0;
     a.m = c.m;
     a.u_max = (double)(n_x - 1);
-    a.surf = (const double2*)ctx->weights;
-    a.K = K;
-    a.is_call = is_call;
-    a.partials = ctx->partials;
+    a.surf = (const double2*)up[0].at;
     a.tabs = (const double2*)ctx->log_tab;
-    {
-        TimedLaunch t(ctx, MCG_K_LOCALVOL);
-        const dim3 grid((unsigned)n_blocks), block(256);
-        if (n_slices == 1) {
-            if (want_payoff) hipLaunchKernelGGL((k_localvol_paths<true, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_localvol_paths<false, true>), grid, block, 0, ctx->stream, a);
-        } else {
-            if (want_payoff) hipLaunchKernelGGL((k_localvol_paths<true, false>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_localvol_paths<false, false>), grid, block, 0, ctx->stream, a);
-        }
-    }
-    MCG_HIP(hipGetLastError());
-    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
-    return MCG_OK;
+    return launch.run(MCG_K_LOCALVOL, [&] {
+        dispatch_flags(
+            [&](auto payoff, auto one_slice) {
+                hipLaunchKernelGGL((k_localvol_paths<payoff.value, one_slice.value>), dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, a);
+            },
+            want_payoff, n_slices == 1);
+    });
 }
 
 }  // namespace mcg

@@ -25,7 +25,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "lsm_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -264,9 +264,7 @@ static int run_lsm_dual(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const doubl
     const int64_t n_blocks = (n + 255) / 256;
     // the table workspace: the policy's rows, the discounts, the words of stop bits, then the two counters
     const size_t n_coef = (size_t)rows * MCG_LSM_POLICY_STRIDE, n_words = ((size_t)rows + 63) / 64;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, n_coef + (size_t)rows + n_words + 2);
-    if (rc) return rc;
-    rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, 2 * (size_t)n_blocks);
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, 2 * (size_t)n_blocks);
     if (rc) return rc;
     const size_t ws_doubles = per_path * (size_t)batch, c_doubles = cont_out ? (size_t)n_steps * (size_t)n : 0;
     const size_t bytes = (ws_doubles + (size_t)n + c_doubles) * sizeof(double);
@@ -286,9 +284,11 @@ static int run_lsm_dual(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const doubl
             if (j == (size_t)n_steps || coef[j * MCG_LSM_POLICY_STRIDE + 18] == (double)MCG_POL_EXERCISE_RULE) bits |= 1ull << (j - 64 * wd);
         std::memcpy(&table[n_coef + (size_t)rows + wd], &bits, sizeof(bits));
     }
-    unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(ctx->weights + n_coef + rows + n_words);
     auto body = [&]() -> int {
-        MCG_HIP(hipMemcpyAsync(ctx->weights, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HostPiece up[] = {{table.data(), table.size() * sizeof(double)}};
+        const int r1 = upload_params(ctx, up, 2);
+        if (r1) return r1;
+        unsigned long long* d_counters = reinterpret_cast<unsigned long long*>(up[0].at + table.size());
         MCG_HIP(hipMemsetAsync(d_counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
         DualInnerArgs a;
         a.data = P->data;
@@ -306,9 +306,9 @@ static int run_lsm_dual(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const doubl
         a.invK = 1.0 / hdr->K;
         a.a = model->sigma * std::sqrt(hdr->dt);
         a.m = (hdr->r - model->q - 0.5 * model->sigma * model->sigma) * hdr->dt;
-        a.coef = ctx->weights;
-        a.disc = ctx->weights + n_coef;
-        a.stops = reinterpret_cast<const unsigned long long*>(ctx->weights + n_coef + rows);
+        a.coef = up[0].at;
+        a.disc = up[0].at + n_coef;
+        a.stops = reinterpret_cast<const unsigned long long*>(up[0].at + n_coef + rows);
         a.ws = d_ws;
         a.counters = d_counters;
         a.tabs = (const double2*)ctx->log_tab;

@@ -26,7 +26,7 @@
 
 #include "devmath.hpp"
 #include "lsm_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 
 namespace mcg {
 
@@ -156,16 +156,15 @@ int run_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coe
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_chunks, (int64_t)ctx->n_cus * occ));
     // the table workspace: the policy's rows, the discounts, then the counters
     const size_t n_coef = (size_t)rows * MCG_LSM_POLICY_STRIDE;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, n_coef + 2 * (size_t)rows);
-    if (rc) return rc;
-    rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, 2 * (size_t)grid);
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, 2 * (size_t)grid);
     if (rc) return rc;
     std::vector<double> table(n_coef + (size_t)rows);
     std::copy(coef, coef + n_coef, table.begin());
     lsm_policy_discounts(hdr, table.data() + n_coef);
-    unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(ctx->weights + n_coef + rows);
-    // (pageable source: the copy has left `table` when the call returns; finish_sums synchronises before it goes)
-    MCG_HIP(hipMemcpyAsync(ctx->weights, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HostPiece up[] = {{table.data(), table.size() * sizeof(double)}};
+    rc = upload_params(ctx, up, (size_t)rows);  // (finish_sums synchronises before `table` goes: upload_params)
+    if (rc) return rc;
+    unsigned long long* d_hist = reinterpret_cast<unsigned long long*>(up[0].at + n_coef + rows);
     MCG_HIP(hipMemsetAsync(d_hist, 0, (size_t)rows * sizeof(unsigned long long), ctx->stream));
     LsmApplyArgs a;
     a.data = P->data;
@@ -176,8 +175,8 @@ int run_lsm_apply(mcg_ctx* ctx, const mcg_lsm_policy_hdr* hdr, const double* coe
     a.is_call = hdr->is_call;
     a.K = hdr->K;
     a.invK = 1.0 / hdr->K;
-    a.coef = ctx->weights;
-    a.disc = ctx->weights + n_coef;
+    a.coef = up[0].at;
+    a.disc = up[0].at + n_coef;
     a.partials = ctx->partials;
     a.hist = d_hist;
     {

@@ -13,7 +13,7 @@
 // Sharded use: the moments (+ primal sum), the offset sum and the dual sum go through ctx->allreduce.
 #include "devmath.hpp"
 #include "lsm_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 
 namespace mcg {
 
@@ -202,12 +202,12 @@ int run_martingale(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
     }
     int grid = (int)std::min<int64_t>((P->n_paths + 255) / 256, (int64_t)ctx->n_cus * 8);
     if (grid < 1) grid = 1;
-    int rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)n_cols);
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)grid * 48);
     if (rc) return rc;
-    rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)grid * 48);
+    HostPiece up[] = {{disc.data(), (size_t)n_cols * sizeof(double)}};
+    rc = upload_params(ctx, up);
     if (rc) return rc;
-    MCG_HIP(hipMemcpyAsync(ctx->weights, disc.data(), (size_t)n_cols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    MCG_HIP(hipStreamSynchronize(ctx->stream));  // disc dies at return (upload_params)
 
     MoArgs a;
     a.data = P->data;
@@ -215,7 +215,7 @@ int run_martingale(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double 
     a.n = P->n_paths;
     a.n_cols = n_cols;
     a.n_dates = n_dates;
-    a.disc = ctx->weights;
+    a.disc = up[0].at;
     a.K = K;
     a.invK = 1.0 / K;
     a.is_call = is_call;

@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "rbergomi_device.hpp"
 
 namespace mcg {
@@ -236,44 +236,32 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
     const bool generic = M > 2048;  // longer than the in-register transforms reach: launch_rbergomi_generic
     const int64_t n_pairs = (P->n_paths + 1) / 2;
     const int ppb = generic ? 128 : rb_pairs_per_block(M);
-    const int64_t n_blocks = (n_pairs + ppb - 1) / ppb;
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch");
+    const int64_t n_blocks = launch_units((n_pairs + ppb - 1) / ppb, P);
+    if (n_blocks < 0) return MCG_ERR_INVALID;
     // FFT variants: persistent workgroups, RB_WAVES per CU (what their registers admit), each striding over the shares
     const int64_t grid = M < 32 ? n_blocks : std::min<int64_t>(n_blocks, (int64_t)ctx->n_cus * rb_grid_per_cu());
 
-    rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, (size_t)M + (size_t)P->n_steps);
+    const PathLaunch launch{ctx, n_blocks, P, want_payoff && !generic, K, is_call};
+    rc = launch.reserve();
     if (rc) return rc;
-    if (want_payoff && !generic) {
-        rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
-        if (rc) return rc;
-    }
-    MCG_HIP(hipMemcpyAsync(ctx->weights, amp.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MCG_HIP(hipMemcpyAsync(ctx->weights + M, comp.data(), (size_t)P->n_steps * sizeof(double), hipMemcpyHostToDevice,
-                           ctx->stream));
-    // the host vectors die at return: make sure the copies have been consumed
-    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    HostPiece up[] = {{amp.data(), (size_t)M * sizeof(double)}, {comp.data(), (size_t)P->n_steps * sizeof(double)}};
+    rc = upload_params(ctx, up);
+    if (rc) return rc;
+    MCG_HIP(hipStreamSynchronize(ctx->stream));  // amp and comp die at return (upload_params)
 
     RbArgs a;
-    a.out = P->data;
-    a.ld = P->ld;
-    a.n_paths = P->n_paths;
-    a.n_steps = P->n_steps;
+    set_shape_key(a, P, seed);
+    set_payoff(a, ctx, K, is_call);
     a.M = M;
-    a.path_begin = P->path_begin;
-    a.k0 = (uint32_t)seed;
-    a.k1 = (uint32_t)(seed >> 32);
     a.S0 = S0;
     a.logS0 = std::log(S0);
     a.r = r;
     a.xi = xi;
     a.dt = dt;
     a.sqdt = std::sqrt(dt);
-    a.amp = ctx->weights;
-    a.comp = ctx->weights + M;
+    a.amp = up[0].at;
+    a.comp = up[1].at;
     a.log_tab = (const double2*)ctx->log_tab;
-    a.K = K;
-    a.is_call = is_call;
-    a.partials = ctx->partials;
     a.n_blocks = n_blocks;
     a.ticket = reinterpret_cast<unsigned long long*>(ctx->scalars + SC_TICKET);
     if (generic) {
@@ -288,14 +276,9 @@ int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double
     }
     if (M >= 32) MCG_HIP(hipMemsetAsync(a.ticket, 0, sizeof(unsigned long long), ctx->stream));
     const size_t smem = rb_smem_bytes(M, P->n_steps);
-    {
-        TimedLaunch t(ctx, MCG_K_RBERGOMI);
-        if (want_payoff) launch_variant<true>(ctx, a, (unsigned)grid, smem);
-        else launch_variant<false>(ctx, a, (unsigned)grid, smem);
-    }
-    MCG_HIP(hipGetLastError());
-    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
-    return MCG_OK;
+    return launch.run(MCG_K_RBERGOMI, [&] {
+        dispatch_flags([&](auto payoff) { launch_variant<payoff.value>(ctx, a, (unsigned)grid, smem); }, want_payoff);
+    });
 }
 
 }  // namespace mcg

@@ -23,7 +23,7 @@
 #include "devmath.hpp"
 #include "fastmath.hpp"
 #include "localvol_device.hpp"
-#include "mcg_internal.hpp"
+#include "paths_host.hpp"
 #include "paths_device.hpp"
 
 namespace mcg {
@@ -201,25 +201,20 @@ int launch_sobol(mcg_ctx* ctx, mcg_paths* P, const mcg_sobol* sobol, double S0, 
     if (!prog.empty()) memcpy(h_prog, prog.data(), prog.size() * sizeof(BridgeOp));
     int rc = mcg_sobol_table(sobol, n, (uint32_t*)h_v, (uint32_t*)h_shift);
     if (rc) return rc;
-    rc = ensure_cap(ctx, &ctx->weights, &ctx->weights_cap, host.size());
+    const PathLaunch launch{ctx, n_blocks, P, want_payoff, K, is_call};
+    rc = launch.reserve();
     if (rc) return rc;
-    if (want_payoff) {
-        rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)(2 * n_blocks));
-        if (rc) return rc;
-    }
-    MCG_HIP(hipMemcpyAsync(ctx->weights, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    // `host` dies at return: make sure the copy has been consumed (as launch_localvol does)
-    MCG_HIP(hipStreamSynchronize(ctx->stream));
+    HostPiece up[] = {{host.data(), host.size() * sizeof(double)}};
+    rc = upload_params(ctx, up);
+    if (rc) return rc;
+    MCG_HIP(hipStreamSynchronize(ctx->stream));  // `host` dies at return (upload_params)
     const uint64_t last = P->path_begin + (uint64_t)P->n_paths - 1;  // (n_paths > 0: the callers launch nothing otherwise)
     int n_bits = 0;
     while (n_bits < 32 && (last >> n_bits) != 0) ++n_bits;
     SobolArgs a{};
-    a.p.out = P->data;
-    a.p.ld = P->ld;
-    a.p.n_paths = P->n_paths;
-    a.p.n_steps = n;
+    set_shape_key(a.p, P, 0);  // (no Philox key)
+    set_payoff(a.p, ctx, K, is_call);
     a.p.nx1 = lv ? n_x - 1 : 1;
-    a.p.path_begin = P->path_begin;
     a.p.S0 = S0;
     if (lv) {
         a.p.inv_dx = lv->inv_dx;
@@ -227,38 +222,26 @@ int launch_sobol(mcg_ctx* ctx, mcg_paths* P, const mcg_sobol* sobol, double S0, 
         a.p.m = lv->m;
         a.p.u_max = (double)(n_x - 1);
     }
-    a.p.surf = (const double2*)ctx->weights;
-    a.p.K = K;
-    a.p.is_call = is_call;
-    a.p.partials = ctx->partials;
+    a.p.surf = (const double2*)up[0].at;
     a.gm = gm;
     a.gs = gs;
-    a.prog = (const BridgeOp*)(ctx->weights + table_doubles);
-    a.v = (const uint32_t*)(ctx->weights + table_doubles + prog_doubles);
-    a.shift = (const uint32_t*)(ctx->weights + table_doubles + prog_doubles + v_doubles);
+    a.prog = (const BridgeOp*)(up[0].at + table_doubles);
+    a.v = (const uint32_t*)(up[0].at + table_doubles + prog_doubles);
+    a.shift = (const uint32_t*)(up[0].at + table_doubles + prog_doubles + v_doubles);
     a.n_ops = (int)prog.size();
     a.n_bits = n_bits;
     const int model = !lv ? SB_GBM : n_slices == 1 ? SB_LV_ONE_SLICE : SB_LV_SURFACE;
-    {
-        TimedLaunch t(ctx, MCG_K_SOBOL);
+    return launch.run(MCG_K_SOBOL, [&] {
         const dim3 grid((unsigned)n_blocks), block(256);
-        auto go = [&](auto payoff, auto bridge) {
-            constexpr bool PAY = decltype(payoff)::value, BR = decltype(bridge)::value;
-            if (model == SB_GBM) hipLaunchKernelGGL((k_sobol_paths<PAY, SB_GBM, BR>), grid, block, 0, ctx->stream, a);
-            else if (model == SB_LV_ONE_SLICE) hipLaunchKernelGGL((k_sobol_paths<PAY, SB_LV_ONE_SLICE, BR>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((k_sobol_paths<PAY, SB_LV_SURFACE, BR>), grid, block, 0, ctx->stream, a);
-        };
-        if (want_payoff) {
-            if (sobol->bridge) go(std::true_type{}, std::true_type{});
-            else go(std::true_type{}, std::false_type{});
-        } else {
-            if (sobol->bridge) go(std::false_type{}, std::true_type{});
-            else go(std::false_type{}, std::false_type{});
-        }
-    }
-    MCG_HIP(hipGetLastError());
-    if (want_payoff) return keep_sums(finish_sums(ctx, n_blocks, P->n_paths, P->sums), P, K, is_call);
-    return MCG_OK;
+        dispatch_flags(
+            [&](auto payoff, auto bridge) {
+                constexpr bool PAY = payoff.value, BR = bridge.value;
+                if (model == SB_GBM) hipLaunchKernelGGL((k_sobol_paths<PAY, SB_GBM, BR>), grid, block, 0, ctx->stream, a);
+                else if (model == SB_LV_ONE_SLICE) hipLaunchKernelGGL((k_sobol_paths<PAY, SB_LV_ONE_SLICE, BR>), grid, block, 0, ctx->stream, a);
+                else hipLaunchKernelGGL((k_sobol_paths<PAY, SB_LV_SURFACE, BR>), grid, block, 0, ctx->stream, a);
+            },
+            want_payoff, sobol->bridge != 0);
+    });
 }
 
 }  // namespace mcg

@@ -15,22 +15,24 @@ namespace mcg {
 static thread_local std::string g_err;
 Stats g_stats;
 
-void set_error(const char* fmt, ...) {
+static void set_error_v(const char* fmt, va_list ap) {
     char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
     g_err = buf;
 }
 
-int fail(int status, const char* fmt, ...) {
-    char buf[512];
+void set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    set_error_v(fmt, ap);
     va_end(ap);
-    g_err = buf;
+}
+
+int fail(int status, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    set_error_v(fmt, ap);
+    va_end(ap);
     return status;
 }
 
@@ -147,6 +149,29 @@ int paths_new(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, m
     ctx->live_paths.push_back(P);
     *out = P;
     return MCG_OK;
+}
+
+// The tail of a generator's entry point, behind its argument checks: a matrix of n_paths x n_steps for every non-null entry
+// of outs (n_outs <= 9: eight assets and their combination), launch(H) -- H[k] is the handle of outs[k], or null -- when there
+// are paths, and then either every handle freed and no output written, or the handles handed out, the first n_generated
+// entries marked mcg_paths::generated.
+template <class Launch>
+static int generate(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, mcg_paths** const* outs, int n_outs,
+                    int n_generated, Launch&& launch) {
+    mcg_paths* H[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc = MCG_OK;
+    for (int k = 0; k < n_outs && rc == MCG_OK; ++k)
+        if (outs[k]) rc = paths_new(ctx, n_paths, n_steps, path_begin, &H[k]);
+    if (rc == MCG_OK && n_paths > 0) rc = launch(H);
+    for (int k = 0; k < n_outs; ++k) {
+        if (rc) {
+            mcg_paths_free(H[k]);
+        } else if (outs[k]) {
+            H[k]->generated = k < n_generated;
+            *outs[k] = H[k];
+        }
+    }
+    return rc;
 }
 
 // ---- layout conversion -----------------------------------------------------------------------
@@ -353,30 +378,21 @@ static int check_gen_args(mcg_ctx* ctx, double S0, double dt, int n_steps, int64
     return MCG_OK;
 }
 
-// sobol: null for the Philox stream `seed`, otherwise the Sobol' point set (kernels_sobol.hip) and `seed` is unused
+// sobol: null for the Philox stream `seed`; a Sobol' entry point passes the address of its own argument, so that a point set
+// that is NULL is sobol_check_shape's to report (kernels_sobol.hip; `seed` is unused then)
 static int gen_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma, double dt, int n_steps,
                    uint64_t path_begin, int64_t n_paths, bool payoff, double K, int is_call, mcg_paths** out,
-                   const mcg_sobol* sobol = nullptr, bool is_sobol = false) {
-    int rc = is_sobol ? sobol_check_shape(sobol, n_steps, path_begin, n_paths) : MCG_OK;
+                   const mcg_sobol* const* sobol = nullptr) {
+    int rc = sobol ? sobol_check_shape(*sobol, n_steps, path_begin, n_paths) : MCG_OK;
     if (rc) return rc;
     rc = check_gen_args(ctx, S0, dt, n_steps, n_paths, out);
     if (rc) return rc;
     if (!(sigma >= 0.0)) return fail(MCG_ERR_INVALID, "sigma must be >= 0");
-    mcg_paths* P = nullptr;
-    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
-    if (rc) return rc;
-    if (n_paths > 0) {
-        rc = is_sobol ? launch_sobol(ctx, P, sobol, S0, (r - 0.5 * sigma * sigma) * dt, sigma * std::sqrt(dt), nullptr, 0, nullptr, 0,
-                                     payoff, K, is_call)
-                      : launch_gbm(ctx, P, seed, S0, r, sigma, dt, payoff, K, is_call);
-        if (rc) {
-            mcg_paths_free(P);
-            return rc;
-        }
-    }
-    P->generated = true;
-    *out = P;
-    return MCG_OK;
+    return generate(ctx, n_paths, n_steps, path_begin, &out, 1, 1, [&](mcg_paths* const* H) {
+        return sobol ? launch_sobol(ctx, H[0], *sobol, S0, (r - 0.5 * sigma * sigma) * dt, sigma * std::sqrt(dt), nullptr, 0, nullptr, 0,
+                                    payoff, K, is_call)
+                     : launch_gbm(ctx, H[0], seed, S0, r, sigma, dt, payoff, K, is_call);
+    });
 }
 
 int mcg_paths_gbm(mcg_ctx* ctx, uint64_t seed, double S0, double r, double sigma, double dt, int n_steps,
@@ -391,12 +407,12 @@ int mcg_paths_gbm_payoff(mcg_ctx* ctx, uint64_t seed, double S0, double r, doubl
 
 int mcg_paths_gbm_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
                         uint64_t path_begin, int64_t n_paths, mcg_paths** out) {
-    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out, sobol, true);
+    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out, &sobol);
 }
 
 int mcg_paths_gbm_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double sigma, double dt, int n_steps,
                                uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
-    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call, out, sobol, true);
+    return gen_gbm(ctx, 0, S0, r, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call, out, &sobol);
 }
 
 static int gen_rb(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, double H, double eta, double rho,
@@ -409,19 +425,8 @@ static int gen_rb(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, d
     if (!std::isfinite(eta)) return fail(MCG_ERR_INVALID, "eta must be finite");
     if (!(std::fabs(rho) <= 1.0)) return fail(MCG_ERR_INVALID, "|rho| must be <= 1");
     if (n_steps > (1 << 24)) return fail(MCG_ERR_INVALID, "rBergomi n_steps must be <= 2^24 (got %d)", n_steps);  // (66 000 years of trading days)
-    mcg_paths* P = nullptr;
-    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
-    if (rc) return rc;
-    if (n_paths > 0) {
-        rc = launch_rbergomi(ctx, P, seed, S0, r, xi, H, eta, dt, payoff, K, is_call);
-        if (rc) {
-            mcg_paths_free(P);
-            return rc;
-        }
-    }
-    P->generated = true;
-    *out = P;
-    return MCG_OK;
+    return generate(ctx, n_paths, n_steps, path_begin, &out, 1, 1,
+                    [&](mcg_paths* const* P) { return launch_rbergomi(ctx, P[0], seed, S0, r, xi, H, eta, dt, payoff, K, is_call); });
 }
 
 int mcg_paths_rbergomi(mcg_ctx* ctx, uint64_t seed, double S0, double r, double xi, double H, double eta, double rho,
@@ -468,32 +473,13 @@ static int gen_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v
         if (!(std::fabs(mu_j) <= 1.0)) return fail(MCG_ERR_INVALID, "Bates: |mu_j| must be <= 1");
         if (!(sigma_j <= 1.0)) return fail(MCG_ERR_INVALID, "Bates: sigma_j must be <= 1");
     }
-    mcg_paths *P = nullptr, *V = nullptr;
-    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
-    if (rc) return rc;
-    if (var_out) {
-        rc = paths_new(ctx, n_paths, n_steps, path_begin, &V);
-        if (rc) {
-            mcg_paths_free(P);
-            return rc;
-        }
-    }
-    if (n_paths > 0) {
+    mcg_paths** const outs[2] = {out, var_out};  // (the variance matrix is a plain one)
+    return generate(ctx, n_paths, n_steps, path_begin, outs, 2, 1, [&](mcg_paths* const* H) {
         if (jump)
-            rc = launch_bates(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, jump[0], jump[1], jump[2], dt, qe, payoff, K,
-                              is_call);
-        else
-            rc = (qe ? launch_heston_qe : launch_heston)(ctx, P, V, seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
-        if (rc) {
-            mcg_paths_free(P);
-            if (V) mcg_paths_free(V);
-            return rc;
-        }
-    }
-    P->generated = true;
-    *out = P;
-    if (var_out) *var_out = V;
-    return MCG_OK;
+            return launch_bates(ctx, H[0], H[1], seed, S0, r, v0, kappa, theta, sigma_v, rho, jump[0], jump[1], jump[2], dt, qe, payoff, K,
+                                is_call);
+        return (qe ? launch_heston_qe : launch_heston)(ctx, H[0], H[1], seed, S0, r, v0, kappa, theta, sigma_v, rho, dt, payoff, K, is_call);
+    });
 }
 
 int mcg_paths_heston(mcg_ctx* ctx, uint64_t seed, double S0, double r, double v0, double kappa, double theta,
@@ -597,31 +583,12 @@ int mcg_paths_gbm_multi(mcg_ctx* ctx, uint64_t seed, int n_assets, const double*
     int rc = mcg_cholesky_corr(corr, n_assets, L);
     if (rc) return rc;
     MCG_HIP(hipSetDevice(ctx->device));
-    mcg_paths* A[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    mcg_paths* Cm = nullptr;
-    auto drop = [&]() {
-        for (int a = 0; a < n_assets; ++a) mcg_paths_free(A[a]);
-        mcg_paths_free(Cm);
-    };
-    if (assets_out)
-        for (int a = 0; a < n_assets && rc == MCG_OK; ++a) rc = paths_new(ctx, n_paths, n_steps, path_begin, &A[a]);
-    if (rc == MCG_OK && combined_out) rc = paths_new(ctx, n_paths, n_steps, path_begin, &Cm);
-    if (rc == MCG_OK && n_paths > 0)
-        rc = launch_gbm_multi(ctx, assets_out ? A : nullptr, Cm, n_assets, seed, S0, r, q ? q : zeros, sigma, L, dt, combine, w);
-    if (rc) {
-        drop();
-        return rc;
-    }
-    if (assets_out)
-        for (int a = 0; a < n_assets; ++a) {
-            A[a]->generated = true;
-            assets_out[a] = A[a];
-        }
-    if (combined_out) {
-        Cm->generated = true;
-        *combined_out = Cm;
-    }
-    return MCG_OK;
+    mcg_paths** outs[9];  // the assets, then their combination
+    for (int a = 0; a < n_assets; ++a) outs[a] = assets_out ? &assets_out[a] : nullptr;
+    outs[n_assets] = combined_out;
+    return generate(ctx, n_paths, n_steps, path_begin, outs, n_assets + 1, n_assets + 1, [&](mcg_paths* const* H) {
+        return launch_gbm_multi(ctx, assets_out ? H : nullptr, H[n_assets], n_assets, seed, S0, r, q ? q : zeros, sigma, L, dt, combine, w);
+    });
 }
 
 int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets, int kind, const double* weights,
@@ -643,28 +610,17 @@ int mcg_paths_combine(mcg_ctx* ctx, const mcg_paths* const* assets, int n_assets
         generated = generated && assets[a]->generated;
     }
     MCG_HIP(hipSetDevice(ctx->device));
-    mcg_paths* P = nullptr;
-    rc = paths_new(ctx, assets[0]->n_paths, assets[0]->n_steps, assets[0]->path_begin, &P);
-    if (rc) return rc;
-    if (P->n_paths > 0) {
-        rc = launch_paths_combine(ctx, assets, n_assets, kind, w, P);
-        if (rc) {
-            mcg_paths_free(P);
-            return rc;
-        }
-    }
-    P->generated = generated;
-    *out = P;
-    return MCG_OK;
+    return generate(ctx, assets[0]->n_paths, assets[0]->n_steps, assets[0]->path_begin, &out, 1, generated ? 1 : 0,
+                    [&](mcg_paths* const* P) { return launch_paths_combine(ctx, assets, n_assets, kind, w, P[0]); });
 }
 
 // ---- local volatility ------------------------------------------------------------------------------
 static int gen_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
                         double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin, int64_t n_paths,
-                        bool payoff, double K, int is_call, mcg_paths** out, const mcg_sobol* sobol = nullptr, bool is_sobol = false) {
+                        bool payoff, double K, int is_call, mcg_paths** out, const mcg_sobol* const* sobol = nullptr) {
     // (the model is checked before the ctx: what is wrong with a surface is reported on a machine without a GPU too)
     if (!out) return fail(MCG_ERR_INVALID, "local vol: out is NULL");
-    int rc = is_sobol ? sobol_check_shape(sobol, n_steps, path_begin, n_paths) : MCG_OK;
+    int rc = sobol ? sobol_check_shape(*sobol, n_steps, path_begin, n_paths) : MCG_OK;  // (sobol: as gen_gbm's)
     if (rc) return rc;
     *out = nullptr;
     rc = localvol_check_surface(times, n_t, n_x, sigma, dt, n_steps);
@@ -674,23 +630,15 @@ static int gen_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double
     if (n_paths < 0) return fail(MCG_ERR_INVALID, "n_paths must be >= 0 (got %lld)", (long long)n_paths);
     if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
     MCG_HIP(hipSetDevice(ctx->device));
-    mcg_paths* P = nullptr;
-    rc = paths_new(ctx, n_paths, n_steps, path_begin, &P);
-    if (rc) return rc;
-    if (n_paths > 0) {
+    // (not marked `generated`: mcg_internal.hpp)
+    return generate(ctx, n_paths, n_steps, path_begin, &out, 1, 0, [&](mcg_paths* const* P) {
         const int n_slices = n_t == 1 ? 1 : n_steps;
         std::vector<double> table((size_t)n_slices * (size_t)(n_x - 1) * 2);
         localvol_fill_table(times, n_t, n_x, sigma, dt, n_steps, table.data());
         const LocalVolScalars c = localvol_scalars(r, q, x_min, x_max, n_x, dt);
-        rc = is_sobol ? launch_sobol(ctx, P, sobol, S0, 0.0, 0.0, &c, n_x, table.data(), n_slices, payoff, K, is_call)
-                      : launch_localvol(ctx, P, seed, S0, c, n_x, table.data(), n_slices, payoff, K, is_call);
-        if (rc) {
-            mcg_paths_free(P);
-            return rc;
-        }
-    }
-    *out = P;  // (not marked `generated`: mcg_internal.hpp)
-    return MCG_OK;
+        return sobol ? launch_sobol(ctx, P[0], *sobol, S0, 0.0, 0.0, &c, n_x, table.data(), n_slices, payoff, K, is_call)
+                     : launch_localvol(ctx, P[0], seed, S0, c, n_x, table.data(), n_slices, payoff, K, is_call);
+    });
 }
 
 int mcg_paths_localvol(mcg_ctx* ctx, uint64_t seed, double S0, double r, double q, const double* times, int n_t, double x_min,
@@ -711,14 +659,14 @@ int mcg_paths_localvol_sobol(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, do
                              double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps, uint64_t path_begin,
                              int64_t n_paths, mcg_paths** out) {
     return gen_localvol(ctx, 0, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, false, 0.0, 0, out,
-                        sobol, true);
+                        &sobol);
 }
 
 int mcg_paths_localvol_sobol_payoff(mcg_ctx* ctx, const mcg_sobol* sobol, double S0, double r, double q, const double* times,
                                     int n_t, double x_min, double x_max, int n_x, const double* sigma, double dt, int n_steps,
                                     uint64_t path_begin, int64_t n_paths, double K, int is_call, mcg_paths** out) {
     return gen_localvol(ctx, 0, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, dt, n_steps, path_begin, n_paths, true, K, is_call,
-                        out, sobol, true);
+                        out, &sobol);
 }
 
 // ---- host <-> device ---------------------------------------------------------------------------
@@ -1061,9 +1009,10 @@ int mcg_price_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, do
     return run_branching(ctx, P, r, K, maturity, dt, is_call, num_branches, exercise_times, n_ex, seed, price, lower, upper);
 }
 
-int mcg_batch_price_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt,
-                         int num_branches, int poly_order, int max_iterations, uint64_t seed, double* out) {
-    if (!ctx || !out) return fail(MCG_ERR_INVALID, "ctx/out is NULL");
+// What mcg_batch_price_rows and mcg_batch_price_rows6 reject -- all of it BEFORE anything is allocated; out_name: "out" or "out6"
+static int batch_args(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double dt, int poly_order, int max_iterations,
+                      const double* out, const char* out_name) {
+    if (!ctx || !out) return fail(MCG_ERR_INVALID, "ctx/%s is NULL", out_name);
     if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(MCG_ERR_INVALID, "bad rows");
     // (the row kernels serve up to 256 paths per row and orders up to 4 -- the driver uses 250 and 2; anything beyond is
     // priced row by row through the single-contract entry points, run_batch_rows)
@@ -1072,7 +1021,13 @@ int mcg_batch_price_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int 
     if (max_iterations <= 0) return fail(MCG_ERR_INVALID, "MartingaleOptimization: maxIterations must be positive.");
     if (!(dt > 0.0)) return fail(MCG_ERR_INVALID, "dt must be > 0");
     if (n_rows > (int64_t)1 << 31) return fail(MCG_ERR_INVALID, "too many rows for one call (row ids are 32 bits of the Philox counter)");
-    if (n_rows == 0) return MCG_OK;
+    return MCG_OK;
+}
+
+int mcg_batch_price_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt,
+                         int num_branches, int poly_order, int max_iterations, uint64_t seed, double* out) {
+    const int bad = batch_args(ctx, rows, n_rows, n_paths, dt, poly_order, max_iterations, out, "out");
+    if (bad || n_rows == 0) return bad;
     MCG_HIP(hipSetDevice(ctx->device));
     try {  // (the planner's host vectors: nothing may leave an extern "C" entry point as an exception)
         return run_batch_rows(ctx, rows, n_rows, n_paths, r, dt, num_branches, poly_order, max_iterations, seed, out, nullptr);
@@ -1083,15 +1038,8 @@ int mcg_batch_price_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int 
 
 int mcg_batch_price_rows6(mcg_ctx* ctx, const mcg_row* rows, const double* features2, int64_t n_rows, int n_paths, double r,
                           double dt, int num_branches, int poly_order, int max_iterations, uint64_t seed, double* out6) {
-    if (!ctx || !out6) return fail(MCG_ERR_INVALID, "ctx/out6 is NULL");
-    if (n_rows < 0 || (n_rows > 0 && !rows)) return fail(MCG_ERR_INVALID, "bad rows");
-    // (the argument checks are mcg_batch_price_rows's -- all of them BEFORE anything is allocated)
-    if (n_paths < 1) return fail(MCG_ERR_INVALID, "n_paths must be >= 1 (got %d)", n_paths);
-    if (poly_order < 0 || poly_order > 15) return fail(MCG_ERR_INVALID, "poly_order must be in [0,15] (got %d)", poly_order);
-    if (max_iterations <= 0) return fail(MCG_ERR_INVALID, "MartingaleOptimization: maxIterations must be positive.");
-    if (!(dt > 0.0)) return fail(MCG_ERR_INVALID, "dt must be > 0");
-    if (n_rows > (int64_t)1 << 31) return fail(MCG_ERR_INVALID, "too many rows for one call (row ids are 32 bits of the Philox counter)");
-    if (n_rows == 0) return MCG_OK;
+    const int bad = batch_args(ctx, rows, n_rows, n_paths, dt, poly_order, max_iterations, out6, "out6");
+    if (bad || n_rows == 0) return bad;
     std::vector<double> four;
     std::vector<unsigned char> priced;
     try {  // nothing may leave an extern "C" entry point as an exception

@@ -10,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -168,19 +169,6 @@ constexpr int SC_LSM_STATE = 144;  // [144..147) per-date LSM state: date, phase
 int pool_alloc(mcg_ctx* ctx, size_t bytes, void** out);
 void pool_release(mcg_ctx* ctx, void* ptr, size_t bytes);
 int ensure_cap(mcg_ctx* ctx, double** buf, size_t* cap, size_t need_doubles);
-// The grid of a step-major path generator (paths_device.hpp): workgroups of 256 lanes with ppl paths each over n_paths, or
-// over the padded rows of P; -1 after fail(MCG_ERR_INVALID, ...) where one launch cannot cover them
-inline int64_t launch_blocks(int64_t n_paths, int ppl) {
-    const int64_t n_blocks = (n_paths + 256 * ppl - 1) / (256 * ppl);
-    if (n_blocks > 0x7fffffffLL) return fail(MCG_ERR_INVALID, "n_paths too large for one launch"), -1;
-    return n_blocks;
-}
-inline int64_t launch_blocks(const mcg_paths* P, int ppl) {
-    const int64_t n_blocks = launch_blocks(P->n_paths, ppl);
-    if (n_blocks >= 0 && (P->ld & 255) != 0) return fail(MCG_ERR_INVALID, "path matrix rows must be padded to 256 columns"), -1;
-    return n_blocks;
-}
-
 // timing scope: records events around a launch when ctx->timing is on
 struct TimedLaunch {
     mcg_ctx* ctx;
@@ -212,7 +200,9 @@ int peer_arm(mcg_ctx* ctx, double* mbox, int rounds, int n, uint64_t sentinel); 
 int paths_new(mcg_ctx* ctx, int64_t n_paths, int n_steps, uint64_t path_begin, mcg_paths** out);
 
 // generator launchers, each in the .hip file of its name; the Heston and Bates ones derive their scheme's constants and share
-// heston_device.hpp's launch_heston_scheme.  All but launch_gbm and launch_rbergomi size their grid with launch_blocks.
+// heston_device.hpp's launch_heston_scheme.  All of them are written on paths_host.hpp: the grid's checks, the launch frame
+// (PathLaunch), the argument struct's common members, the flag dispatch and the parameter upload are stated there.  launch_gbm
+// and launch_rbergomi count their own units (tiles of the wide route, pairs per share) and pass them through launch_units.
 int launch_gbm(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double sigma, double dt,
                bool want_payoff, double K, int is_call);
 int launch_rbergomi(mcg_ctx* ctx, mcg_paths* P, uint64_t seed, double S0, double r, double xi, double H,
@@ -252,15 +242,6 @@ int sobol_check_shape(const mcg_sobol* s, int n_steps, uint64_t path_begin, int6
 int launch_payoff_sums(mcg_ctx* ctx, const mcg_paths* P, double K, int is_call, double out3[3]);
 int generator_clock(mcg_ctx* ctx, double* ghz_median, int* n_stamps, double* ghz_min, double* ghz_max);  // kernels_gbm.hip
 int finish_sums(mcg_ctx* ctx, int64_t n_blocks, int64_t n_local, double out3[3]);
-// the end of a *_payoff generator: rc is what finish_sums or launch_payoff_sums returned for P->sums; on success P
-// holds the (all-reduced, if a collective is installed) totals of the (K, is_call) payoff
-inline int keep_sums(int rc, mcg_paths* P, double K, int is_call) {
-    if (rc) return rc;
-    P->has_sums = true;
-    P->sums_K = K;
-    P->sums_is_call = is_call;
-    return MCG_OK;
-}
 // {sum, sum of squares, n} of an estimator -> its mean and (std_err may be null) standard error
 inline void sums_to_mean_stderr(double sum, double sum2, double n, double* mean, double* std_err) {
     const double m = sum / n;
@@ -302,6 +283,15 @@ int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_
 int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats);
 // the all-reduce of a payload that may exceed what the node-local collective carries in one call
 int exotic_allreduce_sums(mcg_ctx* ctx, double* d, int count);
+// launch(d_stats) into a pool buffer of 5 n_paths doubles, its download into host_out5, the buffer's release (`what` names the
+// statistics in the message); a failed launch is synchronised first: nothing queued may use a buffer that is back in the pool
+int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch);
+// The frame of a book's sums: a pool workspace of ws_doubles doubles whose last n_sums are the sums; fill(ws, d_sums) queues what
+// computes them from a shard of n > 0 paths, an empty shard's are zeroed (it still takes part in the collective); then the
+// all-reduce where a collective is installed and the download into h.  On an error the stream is synchronised before the
+// workspace goes back to the pool: nothing queued may still use it, or what fill uploaded from.
+int exotic_sums_frame(mcg_ctx* ctx, int64_t n, size_t ws_doubles, int n_sums, std::vector<double>& h,
+                      const std::function<int(double* ws, double* d_sums)>& fill);
 // mcg_api.hip: what mcg_price_exotics rejects of (ctx, paths, first_row) and of one contract (`what` names it in the message)
 int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row);
 int exotic_contract_check(const mcg_exotic& x, const char* what, int index);

@@ -7,7 +7,7 @@
 //   walk_bridge       the depth-first walk over a Brownian bridge of Sobol' dimensions (kernels_sobol.hip)
 //   normal_pairs      Box-Muller on words 0/1 or 2/3 of the lane's Philox blocks
 //   payoff_partials   the terminal-payoff sums of a fused (*_payoff) form
-// and mcg_internal.hpp's launch_blocks the host's share (grid size and shape checks).  A generator supplies its argument
+// and paths_host.hpp the host's share (grid and shape checks, the launch frame, uploads).  A generator supplies its argument
 // struct, what it keeps in registers, and the hooks of walk_blocks: its draws and its step rule.
 // (k_gbm_paths, the benchmark's generator, keeps its own loops and store: kernels_gbm.hip.)
 #pragma once

@@ -217,3 +217,11 @@ def test_launch_accounting(eng):
     eng.timing_enable(False)
     for M in (P, Q, V):
         M.free()
+
+
+def test_launch_frame(eng):
+    """One launch under the generator's kernel id with the variance matrix stored, the fused sums and their reuse
+    (test_gpu_parity.check_launch_frame)."""
+    from test_gpu_parity import FRAME_PATHS, FRAME_STEPS, check_launch_frame
+    check_launch_frame(eng, N.K_HESTON, lambda payoff: eng.heston(1, 100.0, R, dt=DT, n_steps=FRAME_STEPS, n_paths=FRAME_PATHS, payoff=payoff,
+                                                                  want_variance=True, **PARAMS["feller"]))

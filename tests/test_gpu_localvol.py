@@ -207,3 +207,9 @@ def test_empty_matrix_and_errors(eng):
     assert np.abs(Z[-1] / (S0 * math.exp((R - Q) * 11 * DT)) - 1.0).max() <= 1e-14
     many = Surface([0.001 * i for i in range(64)], -1.0, 1.0, [[0.2 + 0.001 * i] * 128 for i in range(64)])
     assert np.isfinite(host(eng.local_vol(1, S0, R, many, DT, 1, 513))).all()
+
+
+def test_launch_frame(eng):
+    """One launch under the generator's kernel id, the fused sums and their reuse (test_gpu_parity.check_launch_frame)."""
+    from test_gpu_parity import FRAME_PATHS, FRAME_STEPS, check_launch_frame
+    check_launch_frame(eng, N.K_LOCALVOL, lambda payoff: eng.local_vol(1, 100.0, R, CEV, DT, FRAME_STEPS, FRAME_PATHS, q=Q, payoff=payoff))

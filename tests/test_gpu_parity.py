@@ -1048,3 +1048,89 @@ def test_rough_regime_prices_and_structure_vs_compiled_reference_sample(eng, ste
         P.free()
         z = (m - fm[idx]) / math.hypot(se, fse[idx])
         assert abs(z) <= 2.0, (steps, STAT_NAMES[idx], m, se, fm[idx], fse[idx], z)
+
+
+# ------------------------------------------------------------------------------------------------
+# The launch frame the generators share (timing span, fused sums, what a failed launcher leaves)
+# ------------------------------------------------------------------------------------------------
+# 513 x 5: two workgroups at two paths per lane, the second one's upper waves beyond the padded row; one whole Philox block
+# and a one-step tail.
+FRAME_PATHS, FRAME_STEPS = 513, 5
+FRAME_K, FRAME_OTHER_K = 100.0, 103.0
+# Launches per kernel id of one call at this shape, counted on the commit BEFORE the launchers were moved onto one frame
+# (csrc/paths_host.hpp) -- not read off the code under test.  The same for every family: GBM (narrow route), rBergomi, Heston
+# and Bates with the variance matrix, local volatility, Sobol' GBM through the bridge.
+FRAME_FUSED = {"own": 1, "payoff": 1}     # the generator, then k_finish_sums over its partial sums
+FRAME_PLAIN = {"own": 1, "payoff": 0}
+FRAME_REPRICE_OTHER_K = 2                 # k_payoff_sums over the last row, then k_finish_sums
+ALL_KERNEL_IDS = range(17)
+
+
+def check_launch_frame(eng, kernel, make):
+    """make(payoff) generates FRAME_PATHS x FRAME_STEPS paths (a PathMatrix, or (prices, variances)), fused when payoff is
+    (K, is_call).  Checks the launch counts under every kernel id for the fused and the plain form, and that
+    mcg_price_european reuses the fused sums for the same (K, is_call) and recomputes them for another K."""
+    def counts():
+        return {k: eng.timing_get(k)[1] for k in ALL_KERNEL_IDS}
+
+    def expect(own, payoff):
+        return {k: (own if k == kernel else payoff if k == N.K_PAYOFF else 0) for k in ALL_KERNEL_IDS}
+
+    def first(x):
+        return x[0] if isinstance(x, tuple) else x
+
+    T = FRAME_STEPS * DT
+    eng.timing_enable(True)
+    try:
+        eng.timing_reset()
+        fused = make((FRAME_K, True))
+        assert counts() == expect(FRAME_FUSED["own"], FRAME_FUSED["payoff"])
+        P = first(fused)
+        assert (P.n_paths, P.n_steps) == (FRAME_PATHS, FRAME_STEPS)
+        eng.timing_reset()
+        m, se = eng.price_european(P, FRAME_K, 0.04, T, True)
+        assert counts() == expect(0, 0)                        # the fused sums, no pass over the last row
+        last = P.to_host_step_major()[-1]
+        pay = math.exp(-0.04 * T) * np.maximum(last - FRAME_K, 0.0)
+        assert abs(m - pay.mean()) <= 1e-12 * max(pay.mean(), 1.0) and abs(se - pay.std(ddof=1) / math.sqrt(FRAME_PATHS)) <= 1e-10 * se
+        eng.timing_reset()
+        m2, _ = eng.price_european(P, FRAME_OTHER_K, 0.04, T, True)
+        assert counts() == expect(0, FRAME_REPRICE_OTHER_K)    # another strike: recomputed
+        pay2 = math.exp(-0.04 * T) * np.maximum(last - FRAME_OTHER_K, 0.0)
+        assert abs(m2 - pay2.mean()) <= 1e-12 * max(pay2.mean(), 1.0)
+        eng.timing_reset()
+        plain = make(None)
+        assert counts() == expect(FRAME_PLAIN["own"], FRAME_PLAIN["payoff"])
+        assert first(plain).to_host_step_major().tobytes() == P.to_host_step_major().tobytes()
+    finally:
+        eng.timing_enable(False)
+    for X in (fused, plain):
+        for M in (X if isinstance(X, tuple) else (X,)):
+            M.free()
+
+
+def test_gbm_launch_frame(eng):
+    check_launch_frame(eng, N.K_GBM, lambda payoff: eng.gbm(SEED, 100.0, 0.04, 0.2, DT, FRAME_STEPS, FRAME_PATHS, payoff=payoff))
+    assert eng.debug_gbm_route() == 1   # the narrow kernel
+
+
+def test_rbergomi_failed_launcher_frees_its_matrix():
+    """An odd path_begin is refused on the host inside launch_rbergomi, after the handle was allocated: the output stays NULL,
+    the matrix goes back to the pool, and the context works on and shuts down cleanly."""
+    import ctypes as C
+    L = N.load_library()
+    ctx = C.c_void_p()
+    assert L.mcg_init(C.byref(ctx), 0) == 0
+    args = (ctx, SEED, 100.0, 0.04, 0.04, 0.1, 1.9, -0.9, DT, FRAME_STEPS)
+    for fused in (False, True):
+        h = C.c_void_p()
+        tail = (100.0, 1, C.byref(h)) if fused else (C.byref(h),)
+        fn = L.mcg_paths_rbergomi_payoff if fused else L.mcg_paths_rbergomi
+        assert fn(*args, 1, FRAME_PATHS, *tail) == 1 and not h
+        assert L.mcg_last_error() == b"rBergomi path_begin must be even (paths are generated in pairs)"
+        assert fn(*args, 2, FRAME_PATHS, *tail) == 0 and h                      # the same shape: the pooled buffer serves it
+        info = [C.c_int64(), C.c_int(), C.c_int64(), C.c_void_p()]
+        assert L.mcg_paths_info(h, *[C.byref(x) for x in info]) == 0 and (info[0].value, info[1].value) == (FRAME_PATHS, FRAME_STEPS)
+        assert L.mcg_paths_free(h) == 0
+    assert L.mcg_trim(ctx) == 0
+    assert L.mcg_finalize(ctx) == 0

@@ -203,3 +203,11 @@ def test_refusals_and_empty_launches(eng):
                 got = M.to_host_step_major()
                 assert got.shape == (M.n_steps + 1, M.n_paths) and (got[0] == 100.0).all() and np.isfinite(got).all(), change
             M.free()
+
+
+def test_launch_frame(eng):
+    """One launch under the generator's kernel id, the fused sums and their reuse (test_gpu_parity.check_launch_frame)."""
+    from montecarlooptionspricer_amd import _native as N
+    from test_gpu_parity import FRAME_PATHS, FRAME_STEPS, check_launch_frame
+    check_launch_frame(eng, N.K_RBERGOMI,
+                       lambda payoff: eng.rbergomi(1, 100.0, 0.04, 0.04, 0.1, 1.9, -0.9, 1.0 / 252.0, FRAME_STEPS, FRAME_PATHS, payoff=payoff))

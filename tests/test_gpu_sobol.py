@@ -447,3 +447,11 @@ def test_rqmc_statistics_of_the_cev_case(eng):
     want = cev_half_closed_form(c["S0"], c["K"], c["r"], c["q"], T, c["sigma0"], True)
     print(f"CEV call {mean:.6f} +- {se:.6f} by rqmc_combine (closed form {want:.6f}: {(mean - want) / se:+.2f} standard errors)")
     assert abs(mean - want) <= 4.0 * se
+
+
+def test_launch_frame(eng):
+    """GBM through the bridge: one launch under the generator's kernel id, the fused sums and their reuse
+    (test_gpu_parity.check_launch_frame)."""
+    from test_gpu_parity import FRAME_PATHS, FRAME_STEPS, check_launch_frame
+    check_launch_frame(eng, N.K_SOBOL,
+                       lambda payoff: eng.gbm_sobol(mc.Sobol(5, 0, "lms", True), 100.0, R, 0.2, DT, FRAME_STEPS, FRAME_PATHS, payoff=payoff))

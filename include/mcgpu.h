@@ -54,7 +54,7 @@ enum mcg_kernel {
     MCG_K_MARTINGALE = 7, /* MartingaleOptimization primal/offset/dual scans */
     MCG_K_BRANCHING = 8,  /* BranchingProcesses suffix-max + bounds kernels   */
     MCG_K_BATCH = 9,      /* the six kernels of mcg_batch_price_rows (one span) */
-    MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics */
+    MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics / mcg_greeks_exotics */
     MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
     MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
     MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
@@ -683,8 +683,9 @@ int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, dou
  * Collectives: on a ctx with a collective (mcg_set_allreduce, RCCL, shm) the 2 n_contracts + 1 sums are all-reduced in one
  * call (the node-local shm collective carries 62 doubles a call: there in pieces of 62) and every rank returns the GLOBAL
  * prices, like mcg_price_european; `sums` lets a caller combine shards by hand.
- * Out of scope: Greeks of these payoffs; early exercise; fusing the statistics into the generators; the batched driver
- * rows; the drop-in classes; continuity corrections for discretely monitored barriers. */
+ * Greeks of these payoffs: mcg_greeks_exotics, below.
+ * Out of scope: early exercise; fusing the statistics into the generators; the batched driver rows; the drop-in classes;
+ * continuity corrections for discretely monitored barriers. */
 enum mcg_exotic_kind {
     MCG_X_ASIAN_ARITH_FIXED = 0, MCG_X_ASIAN_ARITH_FLOAT = 1,
     MCG_X_ASIAN_GEO_FIXED   = 2, MCG_X_ASIAN_GEO_FLOAT   = 3,
@@ -698,6 +699,69 @@ int mcg_path_stats(mcg_ctx* ctx, const mcg_paths* paths, int first_row, double* 
 int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double T, int first_row,
                       const mcg_exotic* book, int n_contracts,
                       double* price, double* std_err /* may be NULL */, double* sums /* may be NULL: {sum, sum^2} per contract, then n */);
+
+/* ---- Greeks of the exotics book ----------------------------------------------------------------- */
+/* mcg_greeks_exotics returns one mcg_greeks per contract of a book of mcg_price_exotics.  One streaming pass over the matrix
+ * reduces every path to ten statistics (mcg_path_tangent_stats), the book is then evaluated on those and on rows 0 and 1
+ * (row 1 for the first step's normal Z_1).  Fields that are undefined are NaN, under the rules of mcg_greeks_european.
+ *
+ * Statistics, out10[q*n_paths + p]; j is the absolute row index, the monitoring rows are first_row .. n_steps, N of them:
+ *   q = 0-4  S_T, A, G, min, max: bit for bit what mcg_path_stats returns
+ *   q = 5    L = mean over the monitoring rows of S_j ln S_j
+ *   q = 6    J = mean over the monitoring rows of j S_j
+ *   q = 7, 8 row index (as a double) of the first minimum and of the first maximum on the monitoring rows (ties resolve to
+ *            the lowest row index)
+ *   q = 9    Q = sum_{i=1..n_steps} (ln S_i - ln S_{i-1})^2, over ALL steps, including rows before first_row
+ * with_logs = 0 (what mcg_greeks_exotics takes when sigma <= 0) skips the one logarithm per element that L and Q need and
+ * writes NaN there; the pass then costs what mcg_path_stats costs.  A path that holds a value below the smallest normal
+ * double keeps mcg_path_stats' rescan rule for G; L, Q and every Greek that reads them are then unspecified: matrices holding
+ * non-positive values are outside the contract for vega.
+ *
+ * Notation: D = e^{-rT}; dt = T / n_steps, t_j = j dt; s0 the path's own row-0 value; c = r - q + sigma^2/2;
+ * mu = (r - q - sigma^2/2) dt; jbar = (first_row + n_steps) / 2; Z_1 = (ln(S_1/s0) - mu) / (sigma sqrt(dt));
+ * W_T = (ln(S_T/s0) - (r - q - sigma^2/2) T) / sigma; f the undiscounted payoff above.  df/dX uses the strict comparisons of
+ * mcg_greeks_european: call 1{X > K}, put -1{X < K}.  For floating strikes the call has df/dS_T = 1{S_T > X} and
+ * df/dX = -1{S_T > X}.
+ * Tangents of the statistics under GBM:
+ *   statistic X   tau_sigma(X) = dX/dsigma                        tau_r(X) = dX/dr
+ *   S_T           S_T (ln(S_T/s0) - c T) / sigma                  T S_T
+ *   A             (L - A ln s0 - c dt J) / sigma                  dt J
+ *   G             G (ln(G/s0) - c dt jbar) / sigma                G dt jbar
+ *   m             m (ln(m/s0) - c dt j_m) / sigma                 dt j_m m
+ *   M             M (ln(M/s0) - c dt j_M) / sigma                 dt j_M M
+ * Kinds 0-5 (Asian, lookback; Lipschitz payoffs): pathwise estimators.
+ *   price       D mean f, always.
+ *   dual_delta  D mean(df/dK), always.  It is exactly 0 with standard error 0 for the floating kinds.
+ *   delta       mean of D (f - K df/dK) / s0.  This uses homogeneity of degree 1 in (S0, K), as mcg_greeks_lsm does.  It is
+ *               filled when row 0 is one positive constant, for every generator.
+ *   rho         mean of D (-T f + sum_X df/dX tau_r(X)).  It is filled when the matrix carries the `generated` mark.
+ *   vega        mean of D sum_X df/dX tau_sigma(X).  It is filled when sigma > 0; the caller asserts GBM with that sigma, r, q
+ *               and T, as for mcg_greeks_european.
+ *   gamma       floating kinds: exactly 0 with standard error 0 whenever delta is defined.
+ *               fixed-strike kinds: D K / (s0^2 sigma sqrt(dt)) mean(1{X > K} Z_1).  X is the statistic the contract reads: A,
+ *               G, M for the lookback call, m for the lookback put.  Calls and puts use the same estimator, by parity.  It is
+ *               filled when sigma > 0, delta is defined and first_row >= 1.  At n_steps = 1 it is mcg_greeks_european's
+ *               gamma.  Its variance grows as 1/dt.
+ * Kinds 6-9 (barriers; discontinuous payoffs): likelihood-ratio estimators.
+ *   price and dual_delta as above.  df/dK acts on the vanilla leg only; the indicator does not depend on K.
+ *   The remaining four are filled when sigma > 0, row 0 is one positive constant and first_row >= 1:
+ *   delta       D f Z_1 / (s0 sigma sqrt(dt))
+ *   gamma       D f [(Z_1^2 - 1) / (s0^2 sigma^2 dt) - Z_1 / (s0^2 sigma sqrt(dt))]
+ *   vega        D f [(sum Z_i^2 - n_steps) / sigma - sqrt(dt) sum Z_i], with
+ *               sum Z_i = (ln(S_T/s0) - n_steps mu) / (sigma sqrt(dt)),
+ *               sum Z_i^2 = (Q - 2 mu ln(S_T/s0) + n_steps mu^2) / (sigma^2 dt)
+ *   rho         D f (W_T/sigma - T)
+ *   The rebate is part of f.  The variance of the vega estimator grows with n_steps.
+ * Every standard error is that of the per-path samples above.  Rules (MCG_ERR_INVALID with a message): everything
+ * mcg_price_exotics rejects; non-finite r, q, sigma or T; T <= 0; a matrix without a step (n_steps < 1); a ctx with a
+ * collective (mcg_set_allreduce, RCCL, shm), like the other Greeks calls.  An empty matrix is MCG_ERR_EMPTY_PATHS.  Repeated
+ * calls are bit-identical (fixed-order reductions, no floating-point atomics), and a contract's result does not depend on
+ * what else is in the book or where in the book it stands.  The launches are booked under MCG_K_EXOTIC.
+ * Out of scope: sharded Greeks; Greeks with control variates; vega or likelihood-ratio Greeks under models other than GBM;
+ * first_row = 0 for the likelihood-ratio fields; continuity corrections. */
+int mcg_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* paths, int first_row, int with_logs, double* host_out10);
+int mcg_greeks_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double q, double sigma, double T, int first_row,
+                       const mcg_exotic* book, int n_contracts, mcg_greeks* out /* [n_contracts] */);
 
 /* ---- control variates for the exotics book ---------------------------------------------------- */
 /* mcg_price_exotics_cv prices the book of mcg_price_exotics with up to two control variates a contract, in the SAME one

@@ -35,6 +35,8 @@ EXOTIC_KINDS = {"asian_arith_fixed": X_ASIAN_ARITH_FIXED, "asian_arith_float": X
                 "lookback_fixed": X_LOOKBACK_FIXED, "lookback_float": X_LOOKBACK_FLOAT,
                 "barrier_up_out": X_BARRIER_UP_OUT, "barrier_up_in": X_BARRIER_UP_IN,
                 "barrier_down_out": X_BARRIER_DOWN_OUT, "barrier_down_in": X_BARRIER_DOWN_IN}
+# the rows of mcg_path_tangent_stats' out10 (include/mcgpu.h), in order
+TANGENT_STATS = ("S_T", "A", "G", "min", "max", "L", "J", "j_min", "j_max", "Q")
 
 # enum mcg_control_form (include/mcgpu.h)
 CV_PAYOFF, CV_VANILLA, CV_ST, CV_A, CV_G = range(5)
@@ -253,7 +255,10 @@ def load_library():
     newer("mcg_price_exotics_cv", [vp, vp, vp, C.POINTER(GbmTwin), C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,
                                    C.POINTER(Control), C.c_int, C.POINTER(C.c_int), dp, dp, dp, dp, dp, dp])
     newer("mcg_exotics_cv_from_sums", [dp, C.c_int, C.POINTER(C.c_int), C.c_double, C.c_double, dp, dp, dp, dp, dp])
-    newer("mcg_gbm_twin_stats", [vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
+    newer("mcg_path_tangent_stats", [vp, vp, C.c_int, C.c_int, dp])
+    newer("mcg_greeks_exotics", [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,
+                                 C.POINTER(Greeks)])
+    newer("mcg_gbm_twin_stats",[vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
     newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_compat_asymptotic_price.argtypes = [dp, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]

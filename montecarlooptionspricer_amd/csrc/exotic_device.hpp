@@ -1,10 +1,35 @@
-// The payoff of one mcg_exotic contract on a path's five statistics: shared by the book kernels of kernels_exotic.hip and
-// kernels_exotic_cv.hip.  Device-only code for gfx950.
+// The payoff of one mcg_exotic contract on a path's five statistics: shared by the book kernels of kernels_exotic.hip,
+// kernels_exotic_cv.hip and kernels_exotic_greeks.hip; and the pieces of the streaming scan that reduces a path to its
+// statistics.  Device-only code for gfx950.
 #pragma once
 #include "../../include/mcgpu.h"
 #include "devmath.hpp"
 
 namespace mcg {
+
+// The pieces of a streaming scan of the matrix that k_path_stats (kernels_exotic.hip) and k_path_tangent_stats
+// (kernels_exotic_greeks.hip) share: the rows of a group, the load of a lane's W adjacent paths, the mantissa split.
+typedef double xs_d2 __attribute__((ext_vector_type(2)));
+
+constexpr int XS_ROWS = 8;   // rows per unrolled group: 8 x 16 B in flight per lane, 32 KiB per workgroup
+
+template <int W>
+__device__ __forceinline__ void xs_load(const double* p, double (&x)[W]) {
+    if constexpr (W == 2) {
+        const xs_d2 v = __builtin_nontemporal_load(reinterpret_cast<const xs_d2*>(p));
+        x[0] = v.x;
+        x[1] = v.y;
+    } else {
+        x[0] = __builtin_nontemporal_load(p);
+    }
+}
+
+// x = m 2^k with m in [1, 2), for a positive normal x: returns m and adds k to e (three integer instructions, no log).
+__device__ __forceinline__ double xs_split(double x, int& e) {
+    const int hi = __double2hiint(x);
+    e += ((hi >> 20) & 0x7ff) - 1023;
+    return __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(x));
+}
 
 // The undiscounted payoffs of include/mcgpu.h, on one path's statistics.  Strike and barrier tests are plain comparisons
 // of the stored doubles.

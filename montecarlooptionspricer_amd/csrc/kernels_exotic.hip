@@ -14,30 +14,9 @@
 
 namespace mcg {
 
-typedef double xs_d2 __attribute__((ext_vector_type(2)));
-
-constexpr int XS_ROWS = 8;   // rows per unrolled group: 8 x 16 B in flight per lane, 32 KiB per workgroup
 constexpr int XS_Q = 5;      // statistics per path: 0 S_T, 1 A, 2 G, 3 min, 4 max
 constexpr int XB_CH = 8;     // contracts one workgroup of k_exotic_book keeps in registers
 constexpr int XB_NF = 2 * XB_CH;
-
-template <int W>
-__device__ __forceinline__ void xs_load(const double* p, double (&x)[W]) {
-    if constexpr (W == 2) {
-        const xs_d2 v = __builtin_nontemporal_load(reinterpret_cast<const xs_d2*>(p));
-        x[0] = v.x;
-        x[1] = v.y;
-    } else {
-        x[0] = __builtin_nontemporal_load(p);
-    }
-}
-
-// x = m 2^k with m in [1, 2), for a positive normal x: returns m and adds k to e (three integer instructions, no log).
-__device__ __forceinline__ double xs_split(double x, int& e) {
-    const int hi = __double2hiint(x);
-    e += ((hi >> 20) & 0x7ff) - 1023;
-    return __hiloint2double((hi & 0x000fffff) | 0x3ff00000, __double2loint(x));
-}
 
 // Statistics of W adjacent paths over n_rows rows from col on.  The rows of a group of XS_ROWS are loaded first and then
 // combined pairwise (sum, min, max, product of mantissas), so a group costs one dependent step per accumulator.
@@ -199,8 +178,9 @@ int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo,
     });
 }
 
-int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch) {
-    const size_t bytes = (size_t)XS_Q * n_paths * sizeof(double);
+int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch,
+                   int n_stats) {
+    const size_t bytes = (size_t)n_stats * n_paths * sizeof(double);
     void* ws = nullptr;
     int rc = pool_alloc(ctx, bytes, &ws);
     if (rc) return rc;

@@ -6,37 +6,10 @@
 #include <limits>
 
 #include "devmath.hpp"
+#include "greeks_device.hpp"
 #include "mcg_internal.hpp"
 
 namespace mcg {
-
-// Partials of one block: NE estimators {sum[0..NE), sum of squares[NE..2NE)}, then min and max of row 0 (NF = 2 NE + 2).
-template <int NE>
-__device__ __forceinline__ void greeks_block_store(double (&e)[2 * NE], double lo, double hi, double* red, double* out) {
-    constexpr int NW = 4;
-    __shared__ double mm[2 * NW];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, o));
-        hi = fmax(hi, __shfl_xor(hi, o));
-    }
-    if (lane == 0) {
-        mm[wave] = lo;
-        mm[NW + wave] = hi;
-    }
-    block_sum<2 * NE, NW>(e, red);  // (its barrier also publishes mm)
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 2 * NE; ++q) out[q] = e[q];
-        for (int w = 1; w < NW; ++w) {
-            lo = fmin(lo, mm[w]);
-            hi = fmax(hi, mm[NW + w]);
-        }
-        out[2 * NE] = lo;
-        out[2 * NE + 1] = hi;
-    }
-}
 
 // European: reads row 0 (S0) and row n_steps (S_T) once, 16 B per path.  Undiscounted per-path estimators:
 //   0 payoff   1 f' S_T / S0 (delta)   2 1{S_T > K} W_T K / (S0^2 sigma T) (gamma)   3 f' S_T (W_T - sigma T) (vega)
@@ -141,22 +114,6 @@ static int greeks_reduce(mcg_ctx* ctx, int n_blocks, int ne, double* host) {
     MCG_HIP(hipStreamSynchronize(ctx->stream));
     for (int q = 0; q < nf; ++q) host[q] = ctx->h_scalars[SC_GREEKS + q];
     return MCG_OK;
-}
-
-// mean and standard error of an estimator from its sum and sum of squares over n paths, times `scale`
-static void mean_se(double sum, double sum2, double n, double scale, double* mean, double* se) {
-    sums_to_mean_stderr(sum, sum2, n, mean, se);
-    *mean = scale * *mean;
-    *se = std::fabs(scale) * *se;
-}
-
-static void greeks_all_nan(mcg_greeks* out) {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    *out = mcg_greeks{nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan};
-}
-
-static int greeks_blocks(const mcg_ctx* ctx, int64_t n) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
 }
 
 int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,

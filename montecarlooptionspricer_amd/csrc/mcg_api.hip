@@ -954,6 +954,36 @@ int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int 
     return run_exotics(ctx, P, r, T, first_row, book, n_contracts, price, std_err, sums);
 }
 
+int mcg_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, int with_logs, double* host_out10) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (!host_out10) return fail(MCG_ERR_INVALID, "host_out10 is NULL");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to take statistics of");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_path_tangent_stats(ctx, P, first_row, with_logs != 0, host_out10);
+}
+
+int mcg_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, double sigma, double T, int first_row,
+                       const mcg_exotic* book, int n_contracts, mcg_greeks* out) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (!book || !out) return fail(MCG_ERR_INVALID, "book/out is NULL");
+    if (ctx->allreduce || ctx->rccl_comm || ctx->shm)
+        return fail(MCG_ERR_INVALID, "sharded Greeks are not supported yet: this ctx holds a collective");
+    if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
+    for (int c = 0; c < n_contracts; ++c) {
+        rc = exotic_contract_check(book[c], "contract", c);
+        if (rc) return rc;
+    }
+    if (!std::isfinite(r) || !std::isfinite(q) || !std::isfinite(sigma) || !std::isfinite(T))
+        return fail(MCG_ERR_INVALID, "r, q, sigma and T must be finite");
+    if (!(T > 0.0)) return fail(MCG_ERR_INVALID, "T must be positive (got %g)", T);
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    if (P->n_steps < 1) return fail(MCG_ERR_INVALID, "the matrix must hold at least one step (row 1 carries the first step's normal)");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_greeks_exotics(ctx, P, r, q, sigma, T, first_row, book, n_contracts, out);
+}
+
 int mcg_lsm_one_launch_enabled(mcg_ctx* ctx, int* enabled) {
     if (!ctx || !enabled) return fail(MCG_ERR_INVALID, "ctx/enabled is NULL");
     *enabled = ctx->coop_launch ? 1 : 0;

@@ -274,6 +274,27 @@ int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, do
 int run_lsm_greeks(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
                    int poly_order, mcg_greeks* out);
 int greeks_lsm_final(mcg_ctx* ctx, const mcg_paths* P, double K, const double* V, const double* dV, mcg_greeks* out);
+// ... the host arithmetic every Greeks entry point ends in:
+// mean and standard error of an estimator from its sum and sum of squares over n paths, times `scale`
+inline void mean_se(double sum, double sum2, double n, double scale, double* mean, double* se) {
+    sums_to_mean_stderr(sum, sum2, n, mean, se);
+    *mean = scale * *mean;
+    *se = std::fabs(scale) * *se;
+}
+inline void greeks_all_nan(mcg_greeks* out) {
+    const double nan = std::nan("");
+    *out = mcg_greeks{nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan};
+}
+// the x grid of a Greeks kernel: it depends on the path count only
+inline int greeks_blocks(const mcg_ctx* ctx, int64_t n) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+}
+// Greeks of the exotics book (kernels_exotic_greeks.hip): k_path_tangent_stats over rows first_row .. n_steps (and, with logs,
+// the rows before them for Q) of P into d_stats[10][n_paths]; one launch under MCG_K_EXOTIC
+int launch_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool logs, double* d_stats);
+int run_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool logs, double* host_out10);
+int run_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, double sigma, double T, int first_row,
+                       const mcg_exotic* book, int n_contracts, mcg_greeks* out);
 // path-dependent European payoffs (kernels_exotic.hip)
 int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5);
 int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
@@ -284,8 +305,10 @@ int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo,
 // the all-reduce of a payload that may exceed what the node-local collective carries in one call
 int exotic_allreduce_sums(mcg_ctx* ctx, double* d, int count);
 // launch(d_stats) into a pool buffer of 5 n_paths doubles, its download into host_out5, the buffer's release (`what` names the
-// statistics in the message); a failed launch is synchronised first: nothing queued may use a buffer that is back in the pool
-int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch);
+// statistics in the message); a failed launch is synchronised first: nothing queued may use a buffer that is back in the pool.
+// n_stats: the statistics per path where they are not five (the ten of mcg_path_tangent_stats)
+int download_stats(mcg_ctx* ctx, int64_t n_paths, double* host_out5, const char* what, const std::function<int(double*)>& launch,
+                   int n_stats = 5);
 // The frame of a book's sums: a pool workspace of ws_doubles doubles whose last n_sums are the sums; fill(ws, d_sums) queues what
 // computes them from a shard of n > 0 paths, an empty shard's are zeroed (it still takes part in the collective); then the
 // all-reduce where a collective is installed and the download into h.  On an error the stream is synchronised before the

@@ -502,6 +502,29 @@ class PathEngine:
                                         se.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
         return (price, se, sums) if return_sums else (price, se)
 
+    def path_tangent_stats(self, paths: PathMatrix, first_row: int = 1, with_logs: bool = True) -> np.ndarray:
+        """The ten per-path statistics behind greeks_exotics (mcg_path_tangent_stats): [10][n_paths], rows in the order of
+        _native.TANGENT_STATS -- the five of path_stats bit for bit, then L = mean S_j ln S_j, J = mean j S_j, the row of the
+        first minimum and of the first maximum, and Q = sum of squared log-returns over all steps.  with_logs=False skips the
+        logarithms: L and Q are NaN."""
+        paths._alive()
+        out = np.empty((10, paths.n_paths), dtype=np.float64)
+        check(self._L.mcg_path_tangent_stats(self._ctx, paths._h, int(first_row), int(bool(with_logs)),
+                                             out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def greeks_exotics(self, paths: PathMatrix, r: float, T: float, book, sigma: float = 0.0, q: float = 0.0,
+                       first_row: int = 1) -> list:
+        """Price, delta, gamma, vega, rho, dual delta and their std errors of every contract of a price_exotics book
+        (mcg_greeks_exotics): a list of dicts like greeks_european's, NaN where a Greek is not defined for these inputs.
+        sigma, q: the GBM volatility and dividend yield the paths were generated with (vega, gamma, the barriers' Greeks)."""
+        paths._alive()
+        arr = make_book(book)
+        n = len(arr)
+        out = (N.Greeks * n)()
+        check(self._L.mcg_greeks_exotics(self._ctx, paths._h, r, q, float(sigma), T, int(first_row), arr, n, out))
+        return [g.as_dict() for g in out]
+
     def gbm_twin_stats(self, twin, n_steps: int, n_paths: int, first_row: int = 1) -> np.ndarray:
         """The five statistics of path_stats for the GBM twin computed in registers (mcg_gbm_twin_stats): twin is a dict or
         tuple of the mcg_gbm_twin fields (seed, S0, r, q, sigma, dt, path_begin).  No matrix is stored."""

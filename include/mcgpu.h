@@ -54,7 +54,7 @@ enum mcg_kernel {
     MCG_K_MARTINGALE = 7, /* MartingaleOptimization primal/offset/dual scans */
     MCG_K_BRANCHING = 8,  /* BranchingProcesses suffix-max + bounds kernels   */
     MCG_K_BATCH = 9,      /* the six kernels of mcg_batch_price_rows (one span) */
-    MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics / mcg_greeks_exotics */
+    MCG_K_EXOTIC = 10,    /* path statistics + contract book of mcg_path_stats / mcg_price_exotics / mcg_greeks_exotics / mcg_price_barriers_bridge */
     MCG_K_HESTON = 11,    /* Heston path generation (+ fused payoff partials) */
     MCG_K_MULTI = 12,     /* multi-asset GBM path generation and mcg_paths_combine */
     MCG_K_LOCALVOL = 13,  /* local-volatility path generation (+ fused payoff partials) */
@@ -684,8 +684,9 @@ int mcg_greeks_lsm(mcg_ctx* ctx, const mcg_paths* paths, double r, double K, dou
  * call (the node-local shm collective carries 62 doubles a call: there in pieces of 62) and every rank returns the GLOBAL
  * prices, like mcg_price_european; `sums` lets a caller combine shards by hand.
  * Greeks of these payoffs: mcg_greeks_exotics, below.
- * Out of scope: early exercise; fusing the statistics into the generators; the batched driver rows; the drop-in classes;
- * continuity corrections for discretely monitored barriers. */
+ * Out of scope: early exercise; fusing the statistics into the generators; the batched driver rows; the drop-in classes.
+ * Barriers here are monitored on the stored dates only; continuously monitored barriers are priced by
+ * mcg_price_barriers_bridge, below. */
 enum mcg_exotic_kind {
     MCG_X_ASIAN_ARITH_FIXED = 0, MCG_X_ASIAN_ARITH_FLOAT = 1,
     MCG_X_ASIAN_GEO_FIXED   = 2, MCG_X_ASIAN_GEO_FLOAT   = 3,
@@ -758,10 +759,65 @@ int mcg_price_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double T, 
  * calls are bit-identical (fixed-order reductions, no floating-point atomics), and a contract's result does not depend on
  * what else is in the book or where in the book it stands.  The launches are booked under MCG_K_EXOTIC.
  * Out of scope: sharded Greeks; Greeks with control variates; vega or likelihood-ratio Greeks under models other than GBM;
- * first_row = 0 for the likelihood-ratio fields; continuity corrections. */
+ * first_row = 0 for the likelihood-ratio fields; Greeks of continuously monitored barriers (mcg_price_barriers_bridge, below,
+ * returns prices only). */
 int mcg_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* paths, int first_row, int with_logs, double* host_out10);
 int mcg_greeks_exotics(mcg_ctx* ctx, const mcg_paths* paths, double r, double q, double sigma, double T, int first_row,
                        const mcg_exotic* book, int n_contracts, mcg_greeks* out /* [n_contracts] */);
+
+/* ---- continuously monitored barriers: Brownian-bridge survival probabilities -------------------- */
+/* mcg_price_barriers_bridge prices the barrier contracts of an mcg_price_exotics book under CONTINUOUS monitoring: between two
+ * stored dates a path that is on the safe side of the barrier at both still crosses it with the probability of a Brownian bridge
+ * in ln S, and the indicator "not hit" of mcg_price_exotics becomes the path's survival probability P.  Under GBM the estimator
+ * is exact in law at any step count; under Heston, Bates and local volatility it is the first-order correction with the step's
+ * variance frozen.  One streaming pass over the matrix (and the variance matrix, if given) computes P.
+ *
+ * Definitions.  A level is a pair (B, up) with B > 0 finite.  l_j = ln S_j: the device logarithm of the stored double;
+ * h = ln B: computed on the host in binary64 and handed to the kernel; d_j = l_j - h.  Row j is SAFE when S_j > B (down level)
+ * or S_j < B (up level): plain comparisons of the stored doubles, the complement of mcg_price_exotics' hit rule.
+ * Monitoring window: rows first_row .. n_steps and every interval [j, j+1] with first_row <= j < n_steps
+ * (0 <= first_row <= n_steps; continuous monitoring from t = 0 is first_row = 0).
+ * Step variance w_j of the interval [j, j+1]: the scalar route, var == NULL, w = (sigma sigma) dt with sigma >= 0 finite; or the
+ * matrix route, w_j = max(v_j, 0) dt, with `var` a matrix of this ctx and of the paths' shape whose row j holds v_j -- what
+ * mcg_paths_heston* / mcg_paths_bates* return in var_out, or anything passed through mcg_paths_from_host (sigma is then not read).
+ * Survival of a path for a level:
+ *   P = 0 if any monitored row is not safe; otherwise
+ *   P = prod_j (1 - exp(x_j)) over the intervals, x_j = -2 max(d_j d_{j+1}, 0) / w_j (evaluated as max(d_j d_{j+1}, 0) times the
+ *   rounded quotient -2 / w_j, which every level shares); an interval with w_j = 0 contributes the factor 1.
+ * The max keeps the factor in [0, 1) when a logarithm rounds d to 0 or to the wrong sign.  The product runs over the intervals
+ * in ascending order.  A path's P for a level depends on that path's column and that level only (not on the other levels, the
+ * other paths, the shard or the route: the scalar route equals the matrix route on a constant matrix of sigma sigma bit for bit).
+ * With first_row = n_steps there is no interval and P is the safe indicator of the last row.  The kernel leaves an exponential
+ * out where x_j <= -38 on every lane of a wave: there 1 - exp(x_j) rounds to 1, so this changes no bit.
+ * Sample per contract: only kinds MCG_X_BARRIER_UP_OUT .. MCG_X_BARRIER_DOWN_IN are accepted (anything else: MCG_ERR_INVALID).
+ * With f the vanilla payoff on S_T = row n_steps (max(S_T - K, 0) / max(K - S_T, 0)):
+ *   out: Y = f P + rebate (1 - P);      in: Y = f (1 - P) + rebate P.
+ * The rebate is paid at T, as in mcg_price_exotics.  price[c] = e^{-rT} mean Y, std_err[c] from {sum Y, sum Y^2}; dt = T / n_steps.
+ * sums = {sum Y, sum Y^2} per contract in book order, then n.
+ * The book's levels: duplicates (B and the direction compared bitwise) are computed once and their contracts share P; the
+ * distinct levels are walked in groups of MCG_BRIDGE_L_MAX, the matrix is read once per group, and the workspace stays at
+ * MCG_BRIDGE_L_MAX n_paths doubles whatever the book holds.
+ * mcg_barrier_survival returns P itself, host_out[l*n_paths + p] for the levels (barriers[l], is_up[l]), 1 <= n_levels <= 1024
+ * (no duplicates are removed); it takes dt itself.
+ * Rules (MCG_ERR_INVALID with a message): everything mcg_price_exotics rejects for these kinds; a barrier that is not positive;
+ * sigma negative or not finite (scalar route); r or T not finite, T <= 0; dt <= 0 or not finite; a matrix without a step
+ * (n_steps < 1); var of another ctx or another shape; first_row outside [0, n_steps].  An empty matrix on a ctx without a
+ * collective is MCG_ERR_EMPTY_PATHS.  Repeated calls are bit-identical (fixed-order reductions, no floating-point atomics), and a
+ * contract's result does not depend on what else is in the book or where in the book it stands.  Matrices holding non-positive
+ * or non-finite values are outside the contract.  The launches are booked under MCG_K_EXOTIC.
+ * Collectives: as mcg_price_exotics -- the 2 n_contracts + 1 sums are all-reduced (the node-local shm collective: in pieces of
+ * 62), every rank returns the global prices, an empty shard still takes part.
+ * Out of scope: Greeks of the bridge estimator; control variates on it; double barriers; a local-volatility sigma(t, S)
+ * evaluated in the kernel (hand a variance matrix instead); jump crossings under Bates (the bridge sees the diffusion only);
+ * the batched driver rows, the coalescing layer and the drop-in classes. */
+#define MCG_BRIDGE_L_MAX 8   /* levels one pass over the matrix keeps in registers */
+#define MCG_BRIDGE_ROWS  4   /* rows one lane loads ahead of their logarithms */
+int mcg_barrier_survival(mcg_ctx* ctx, const mcg_paths* paths, const mcg_paths* var /* NULL: the scalar route */, double sigma,
+                         double dt, int first_row, const double* barriers, const int* is_up, int n_levels,
+                         double* host_out /* [n_levels * n_paths] */);
+int mcg_price_barriers_bridge(mcg_ctx* ctx, const mcg_paths* paths, const mcg_paths* var /* NULL: the scalar route */, double sigma,
+                              double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
+                              double* price, double* std_err /* may be NULL */, double* sums /* may be NULL: {sum, sum^2} per contract, then n */);
 
 /* ---- control variates for the exotics book ---------------------------------------------------- */
 /* mcg_price_exotics_cv prices the book of mcg_price_exotics with up to two control variates a contract, in the SAME one

@@ -12,6 +12,7 @@ from ._native import (X_ASIAN_ARITH_FIXED, X_ASIAN_ARITH_FLOAT, X_ASIAN_GEO_FIXE
                       X_BARRIER_DOWN_OUT, X_BARRIER_UP_IN, X_BARRIER_UP_OUT, X_LOOKBACK_FIXED, X_LOOKBACK_FLOAT)
 from ._native import CV_A, CV_G, CV_PAYOFF, CV_ST, CV_VANILLA  # noqa: F401
 from ._native import TANGENT_STATS  # noqa: F401
+from ._native import BRIDGE_L_MAX, BRIDGE_ROWS  # noqa: F401
 from .engine import CvResult, control, exotics_cv_from_sums, gbm_expectation  # noqa: F401
 from ._native import POL_CONTINUE, POL_EXERCISE_RULE, POL_TERMINAL  # noqa: F401
 from .engine import DualResult, LsmPolicy  # noqa: F401
@@ -26,4 +27,4 @@ __all__ = ["McgError", "PathEngine", "PathMatrix", "RoughVolatility", "LSM", "As
            "exotic", "cholesky_corr", "LocalVolSurface", "local_vol_table", "X_ASIAN_ARITH_FIXED", "X_ASIAN_ARITH_FLOAT", "X_ASIAN_GEO_FIXED", "X_ASIAN_GEO_FLOAT", "X_LOOKBACK_FIXED",
            "X_LOOKBACK_FLOAT", "X_BARRIER_UP_OUT", "X_BARRIER_UP_IN", "X_BARRIER_DOWN_OUT", "X_BARRIER_DOWN_IN",
            "control", "gbm_expectation", "exotics_cv_from_sums", "CvResult", "LsmPolicy", "DualResult", "POL_CONTINUE", "POL_EXERCISE_RULE", "POL_TERMINAL", "CV_PAYOFF", "CV_VANILLA", "CV_ST", "CV_A", "CV_G",
-           "Sobol", "sobol_table", "sobol_bridge", "rqmc_combine", "TANGENT_STATS"]
+           "Sobol", "sobol_table", "sobol_bridge", "rqmc_combine", "TANGENT_STATS", "BRIDGE_L_MAX", "BRIDGE_ROWS"]

@@ -35,6 +35,9 @@ EXOTIC_KINDS = {"asian_arith_fixed": X_ASIAN_ARITH_FIXED, "asian_arith_float": X
                 "lookback_fixed": X_LOOKBACK_FIXED, "lookback_float": X_LOOKBACK_FLOAT,
                 "barrier_up_out": X_BARRIER_UP_OUT, "barrier_up_in": X_BARRIER_UP_IN,
                 "barrier_down_out": X_BARRIER_DOWN_OUT, "barrier_down_in": X_BARRIER_DOWN_IN}
+# MCG_BRIDGE_L_MAX, MCG_BRIDGE_ROWS (include/mcgpu.h): the levels one pass of the bridge survival kernel keeps in registers,
+# and the rows of one of its load groups
+BRIDGE_L_MAX, BRIDGE_ROWS = 8, 4
 # the rows of mcg_path_tangent_stats' out10 (include/mcgpu.h), in order
 TANGENT_STATS = ("S_T", "A", "G", "min", "max", "L", "J", "j_min", "j_max", "Q")
 
@@ -258,6 +261,8 @@ def load_library():
     newer("mcg_path_tangent_stats", [vp, vp, C.c_int, C.c_int, dp])
     newer("mcg_greeks_exotics", [vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int,
                                  C.POINTER(Greeks)])
+    newer("mcg_barrier_survival", [vp, vp, vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(C.c_int), C.c_int, dp])
+    newer("mcg_price_barriers_bridge", [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
     newer("mcg_gbm_twin_stats",[vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
     newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]

@@ -12,6 +12,9 @@ namespace mcg {
 typedef double xs_d2 __attribute__((ext_vector_type(2)));
 
 constexpr int XS_ROWS = 8;   // rows per unrolled group: 8 x 16 B in flight per lane, 32 KiB per workgroup
+// The book layout k_exotic_book and k_bridge_book (kernels_barrier_bridge.hip) share, and k_exotic_reduce reads:
+constexpr int XB_CH = 8;     // contracts one workgroup of a book kernel keeps in registers
+constexpr int XB_NF = 2 * XB_CH;
 
 template <int W>
 __device__ __forceinline__ void xs_load(const double* p, double (&x)[W]) {

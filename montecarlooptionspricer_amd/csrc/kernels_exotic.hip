@@ -15,8 +15,6 @@
 namespace mcg {
 
 constexpr int XS_Q = 5;      // statistics per path: 0 S_T, 1 A, 2 G, 3 min, 4 max
-constexpr int XB_CH = 8;     // contracts one workgroup of k_exotic_book keeps in registers
-constexpr int XB_NF = 2 * XB_CH;
 
 // Statistics of W adjacent paths over n_rows rows from col on.  The rows of a group of XS_ROWS are loaded first and then
 // combined pairwise (sum, min, max, product of mantissas), so a group costs one dependent step per accumulator.
@@ -162,6 +160,11 @@ __global__ __launch_bounds__(256) void k_exotic_reduce(const double* partials, i
     if (blockIdx.x == 0 && threadIdx.x == 0) sums[2 * n_contracts] = n_local;
 }
 
+void enqueue_exotic_reduce(mcg_ctx* ctx, const double* d_part, int n_blocks, int n_contracts, double n_local, double* d_sums) {
+    hipLaunchKernelGGL(k_exotic_reduce, dim3((n_contracts + XB_CH - 1) / XB_CH), dim3(256), 0, ctx->stream, d_part, n_blocks, n_contracts,
+                       n_local, d_sums);
+}
+
 int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats) {
     const int n_rows = P->n_steps - first_row + 1;
     const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0;
@@ -228,7 +231,7 @@ static int exotic_sums(mcg_ctx* ctx, const mcg_paths* P, int first_row, const mc
             TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
             hipLaunchKernelGGL(k_exotic_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, geo ? 1 : 0,
                                reinterpret_cast<const mcg_exotic*>(up[0].at), nc, d_part);
-            hipLaunchKernelGGL(k_exotic_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
+            enqueue_exotic_reduce(ctx, d_part, n_blocks, nc, (double)n, d_sums);
         }
         MCG_HIP(hipGetLastError());
         return MCG_OK;

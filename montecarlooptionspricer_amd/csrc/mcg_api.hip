@@ -7,6 +7,7 @@
 #include <new>
 #include <vector>
 
+#include "../host/barrier_bridge.hpp"
 #include "fastmath_tables.hpp"
 #include "mcg_internal.hpp"
 
@@ -982,6 +983,61 @@ int mcg_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, dou
     if (P->n_steps < 1) return fail(MCG_ERR_INVALID, "the matrix must hold at least one step (row 1 carries the first step's normal)");
     MCG_HIP(hipSetDevice(ctx->device));
     return run_greeks_exotics(ctx, P, r, q, sigma, T, first_row, book, n_contracts, out);
+}
+
+// ---- continuous barriers: Brownian-bridge survival probabilities ------------------------------
+} // extern "C"
+namespace mcg {
+// what both bridge entry points reject of (paths, var, sigma, dt) beyond exotic_args
+static int bridge_args(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double dt) {
+    if (P->n_steps < 1) return fail(MCG_ERR_INVALID, "the matrix must hold at least one step (n_steps = %d)", P->n_steps);
+    if (V) {
+        if (V->ctx != ctx) return fail(MCG_ERR_INVALID, "var belongs to a different ctx");
+        if (V->n_paths != P->n_paths || V->n_steps != P->n_steps)
+            return fail(MCG_ERR_INVALID, "var must have the shape of paths (%lld x %d; got %lld x %d)", (long long)P->n_paths, P->n_steps,
+                        (long long)V->n_paths, V->n_steps);
+    }
+    return bridge_check_variance(V != nullptr, sigma, dt);
+}
+}  // namespace mcg
+extern "C" {
+
+int mcg_barrier_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* var, double sigma, double dt, int first_row,
+                         const double* barriers, const int* is_up, int n_levels, double* host_out) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (n_levels < 1 || n_levels > 1024) return fail(MCG_ERR_INVALID, "n_levels must be in [1, 1024] (got %d)", n_levels);
+    if (!barriers || !is_up || !host_out) return fail(MCG_ERR_INVALID, "barriers/is_up/host_out is NULL");
+    for (int l = 0; l < n_levels; ++l) {
+        rc = bridge_check_level(barriers[l], "level", l);
+        if (rc) return rc;
+    }
+    rc = bridge_args(ctx, P, var, sigma, dt);
+    if (rc) return rc;
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to take survival probabilities of");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_barrier_survival(ctx, P, var, sigma, dt, first_row, barriers, is_up, n_levels, host_out);
+}
+
+int mcg_price_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* var, double sigma, double r, double T, int first_row,
+                              const mcg_exotic* book, int n_contracts, double* price, double* std_err, double* sums) {
+    int rc = exotic_args(ctx, P, first_row);
+    if (rc) return rc;
+    if (!book || !price) return fail(MCG_ERR_INVALID, "book/price is NULL");
+    if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
+    for (int c = 0; c < n_contracts; ++c) {
+        rc = bridge_check_kind(book[c], c);
+        if (!rc) rc = exotic_contract_check(book[c], "contract", c);
+        if (!rc) rc = bridge_check_level(book[c].barrier, "contract", c);
+        if (rc) return rc;
+    }
+    if (!std::isfinite(r) || !std::isfinite(T)) return fail(MCG_ERR_INVALID, "r and T must be finite");
+    if (!(T > 0.0)) return fail(MCG_ERR_INVALID, "T must be positive (got %g)", T);
+    rc = bridge_args(ctx, P, var, sigma, P->n_steps >= 1 ? T / (double)P->n_steps : 1.0);
+    if (rc) return rc;
+    if (P->n_paths < 1 && !ctx->allreduce) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_barriers_bridge(ctx, P, var, sigma, r, T, first_row, book, n_contracts, price, std_err, sums);
 }
 
 int mcg_lsm_one_launch_enabled(mcg_ctx* ctx, int* enabled) {

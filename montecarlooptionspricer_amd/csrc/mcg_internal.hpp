@@ -318,6 +318,14 @@ int exotic_sums_frame(mcg_ctx* ctx, int64_t n, size_t ws_doubles, int n_sums, st
 // mcg_api.hip: what mcg_price_exotics rejects of (ctx, paths, first_row) and of one contract (`what` names it in the message)
 int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row);
 int exotic_contract_check(const mcg_exotic& x, const char* what, int index);
+// k_exotic_reduce over the (n_contracts + XB_CH - 1) / XB_CH chunks of a book kernel's partials (no timing span of its own)
+void enqueue_exotic_reduce(mcg_ctx* ctx, const double* d_part, int n_blocks, int n_contracts, double n_local, double* d_sums);
+// Brownian-bridge barrier prices (kernels_barrier_bridge.hip; the host part in host/barrier_bridge.cpp).  V: the variance
+// matrix of P's shape, or null for the scalar route w = (sigma sigma) dt.
+int run_barrier_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double dt, int first_row,
+                         const double* barriers, const int* is_up, int n_levels, double* host_out);
+int run_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double r, double T, int first_row,
+                        const mcg_exotic* book, int n_contracts, double* price, double* std_err, double* sums);
 
 // MartingaleOptimization's refit (its driver re-accumulates on request): mo_mode 1 = first pass, leave the refinement
 // request in the coefficient block; 2 = the moments are about mo_mu, solve them with lsm_solve_centered.

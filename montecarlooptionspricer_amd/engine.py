@@ -525,6 +525,51 @@ class PathEngine:
         check(self._L.mcg_greeks_exotics(self._ctx, paths._h, r, q, float(sigma), T, int(first_row), arr, n, out))
         return [g.as_dict() for g in out]
 
+    @staticmethod
+    def _bridge_variance(sigma, var):
+        """(var handle or None, sigma) of the bridge calls: exactly one of sigma and var is given."""
+        if (sigma is None) == (var is None):
+            raise ValueError("give exactly one of sigma (the scalar route) and var (a variance matrix)")
+        if var is None:
+            return None, float(sigma)
+        if not isinstance(var, PathMatrix):
+            raise ValueError("var must be a PathMatrix (a generator's var_out, or from_host)")
+        var._alive()
+        return var._h, 0.0
+
+    def barrier_survival(self, paths: PathMatrix, levels, dt: float, sigma: Optional[float] = None, var: Optional[PathMatrix] = None,
+                         first_row: int = 0) -> np.ndarray:
+        """Brownian-bridge survival probabilities of every path for every level (mcg_barrier_survival): [n_levels][n_paths].
+        levels: a sequence of (barrier, is_up).  Rows first_row .. n_steps and the intervals between them are monitored; the
+        step variance is sigma * sigma * dt, or max(var, 0) * dt row by row from a variance matrix of the paths' shape.
+        Exactly one of sigma and var must be given (ValueError otherwise)."""
+        paths._alive()
+        var_h, sig = self._bridge_variance(sigma, var)
+        levels = list(levels)
+        n = len(levels)
+        B = np.ascontiguousarray([float(lv[0]) for lv in levels], dtype=np.float64)
+        up = (C.c_int * max(n, 1))(*[int(bool(lv[1])) for lv in levels])
+        out = np.empty((n, paths.n_paths), dtype=np.float64)
+        dp = C.POINTER(C.c_double)
+        check(self._L.mcg_barrier_survival(self._ctx, paths._h, var_h, sig, float(dt), int(first_row), B.ctypes.data_as(dp), up, n,
+                                           out.ctypes.data_as(dp)))
+        return out
+
+    def price_barriers_bridge(self, paths: PathMatrix, r: float, T: float, book, sigma: Optional[float] = None,
+                              var: Optional[PathMatrix] = None, first_row: int = 0, return_sums: bool = False):
+        """Continuously monitored barrier contracts from Brownian-bridge survival probabilities (mcg_price_barriers_bridge).
+        book: exotic(...) tuples of the four barrier kinds, as for price_exotics; returns (price[n], std_err[n]), plus
+        sums[2 n + 1] when return_sums.  dt = T / n_steps; exactly one of sigma and var must be given (ValueError otherwise)."""
+        paths._alive()
+        var_h, sig = self._bridge_variance(sigma, var)
+        arr = make_book(book)
+        n = len(arr)
+        dp = C.POINTER(C.c_double)
+        price, se, sums = np.empty(n), np.empty(n), np.empty(2 * n + 1)
+        check(self._L.mcg_price_barriers_bridge(self._ctx, paths._h, var_h, sig, r, T, int(first_row), arr, n, price.ctypes.data_as(dp),
+                                                se.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
+        return (price, se, sums) if return_sums else (price, se)
+
     def gbm_twin_stats(self, twin, n_steps: int, n_paths: int, first_row: int = 1) -> np.ndarray:
         """The five statistics of path_stats for the GBM twin computed in registers (mcg_gbm_twin_stats): twin is a dict or
         tuple of the mcg_gbm_twin fields (seed, S0, r, q, sigma, dt, path_begin).  No matrix is stored."""

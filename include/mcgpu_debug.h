@@ -98,6 +98,14 @@ int mcg_debug_lsm_hooks(mcg_ctx* ctx, long long spin_limit, int poll_delay);
 int mcg_debug_lsm_date_fault(mcg_ctx* ctx, int mode, int date, int workgroup, int delay, long long spin_limit);
 /* Test hook: workspace bytes one chunk of mcg_batch_price_rows* may use (0: the default, a quarter of free memory). */
 int mcg_debug_batch_budget(mcg_ctx* ctx, size_t bytes);
+/* Test hook: mcg_batch_price_rows with the same arguments -- the same classification, plan, chunks and launches, the same `out`
+ * bit for bit -- that also copies out what the row kernels held for row `row` when its chunk had finished: amp[M] (M = the
+ * power of two >= n_steps), comp[n_steps] (both written by k_batch_weights) and block[(n_steps + 1) x n_paths], the row's path
+ * matrix, step-major.  MCG_ERR_INVALID, before anything runs, for a row index outside the call, an invalid row (the call answers
+ * it with zeros) and a row that is priced singly (more than 1020 steps, more than 256 paths per row, or an order above 4). */
+int mcg_debug_batch_row_dump(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt, int num_branches,
+                             int poly_order, int max_iterations, uint64_t seed, double* out, int64_t row, double* amp, double* comp,
+                             double* block);
 /* Class-API coalescing (mcg_compat_set_coalescing): at most max_slots calling threads get a matrix slot of the device arena from
  * now on (< 0: the default, 512); a thread that gets none prices on a context of its own.  For the test of that fall-back. */
 int mcg_debug_coalesce_slots(int max_slots);

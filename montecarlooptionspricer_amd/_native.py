@@ -200,6 +200,8 @@ def load_library():
     newer("mcg_debug_eval_v", [vp, C.c_int, dp, C.c_int, dp, C.c_int, dp, C.c_int64])
     newer("mcg_debug_bates_constants", [C.c_double] * 4 + [C.POINTER(C.c_uint32), dp])
     newer("mcg_debug_lsm_solve", [vp, C.c_int, C.c_int, dp, C.c_int, dp, dp, C.c_int64])
+    newer("mcg_debug_batch_row_dump", [vp, C.POINTER(Row), C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                       C.c_uint64, dp, C.c_int64, dp, dp, dp])
     L.mcg_paths_gbm.argtypes = [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
                                 C.c_uint64, C.c_int64, C.POINTER(vp)]
     L.mcg_paths_gbm_payoff.argtypes = [vp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,

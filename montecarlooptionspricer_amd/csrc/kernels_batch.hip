@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void k_batch_martingale(BatchArgs a) {
         if (threadIdx.x == 0) {
 #pragma unroll
             for (int q = 0; q < NM; ++q) sm_mom[q] = mc[q];
-            lsm_solve_centered(sm_mom, NB, mu, row.strike, sm_coef, sm_ws);
+            lsm_solve_centered_everywhere(sm_mom, NB, mu, row.strike, sm_coef, sm_ws);
         }
         __syncthreads();
     }
@@ -562,6 +562,20 @@ static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, 
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (also: the host vectors `h` and `wg_map` have outlived their uploads)
     else (void)hipStreamSynchronize(ctx->stream);                // (nothing of this chunk may still read the map when it goes back to the pool)
     if (e != hipSuccess) return fail(MCG_ERR_HIP, "batch run failed: %s", hipGetErrorString(e));
+    if (BatchDump* dump = ctx->batch_dump) {  // mcg_debug_batch_row_dump: the next chunk writes over these buffers
+        for (const BatchRow& d : h) {
+            if ((int64_t)d.id != dump->row) continue;
+            const size_t width = sizeof(double) * (size_t)a.n_paths;
+            e = hipMemcpyAsync(dump->amp, a.w + d.woff, sizeof(double) * (size_t)d.M, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(dump->comp, a.w + d.woff + d.M, sizeof(double) * (size_t)d.n_steps, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess)
+                e = hipMemcpy2DAsync(dump->block, width, a.S + d.off, sizeof(double) * (size_t)BATCH_LD, width, (size_t)d.n_steps + 1, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            else (void)hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) return fail(MCG_ERR_HIP, "batch row dump failed: %s", hipGetErrorString(e));
+            dump->found = true;
+        }
+    }
     for (int64_t k = 0; k < n; ++k) {
         const int64_t i = (int64_t)h[(size_t)k].id;
         const bool bad = four[(size_t)(4 * n + k)] != 0.0;  // inf / nan among the row's paths: zeros, like the driver (:752-777)
@@ -597,6 +611,18 @@ static bool paths_hold_non_finite(mcg_ctx* ctx, const mcg_paths* P) {
 #define BT_US(a, b) (std::chrono::duration<double, std::micro>((b) - (a)).count())
 #endif
 
+// a row the reference's driver would answer with zeros (no steps, non-finite paths, a throwing pricer)
+bool batch_row_valid(const mcg_row& s) {
+    return s.n_steps >= 1 && s.S0 > 0.0 && std::isfinite(s.S0) && s.xi >= 0.0 && std::isfinite(s.xi) && s.H >= 0.0 &&
+           std::isfinite(s.H) && std::isfinite(s.eta) && std::fabs(s.rho) <= 1.0 && s.strike > 0.0 &&
+           std::isfinite(s.strike) && s.sigma > 0.0 && std::isfinite(s.maturity);
+}
+
+// A row longer than the row kernels' LDS tables reach (more than four years of trading days), or any row of a call
+// with more than 256 paths per row or an order above 4, is priced after the batch through the single-contract
+// entry points, on the same Philox path ids: never refused, never answered with zeros.
+bool batch_row_singly(const mcg_row& s, int n_paths, int poly_order) { return s.n_steps > BATCH_MAX_STEPS || n_paths > 256 || poly_order > 4; }
+
 int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt, int num_branches,
                    int poly_order, int max_iterations, uint64_t seed, double* out, unsigned char* priced) {
     g_stats.batch_calls.fetch_add(1, std::memory_order_relaxed);
@@ -607,16 +633,10 @@ int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_path
     for (int64_t i = 0; i < n_rows; ++i) {
         const mcg_row& s = rows[i];
         out[4 * i] = out[4 * i + 1] = out[4 * i + 2] = out[4 * i + 3] = 0.0;
-        // a row the reference's driver would answer with zeros (no steps, non-finite paths, a throwing pricer)
-        const bool valid = s.n_steps >= 1 && s.S0 > 0.0 && std::isfinite(s.S0) && s.xi >= 0.0 && std::isfinite(s.xi) && s.H >= 0.0 &&
-                           std::isfinite(s.H) && std::isfinite(s.eta) && std::fabs(s.rho) <= 1.0 && s.strike > 0.0 &&
-                           std::isfinite(s.strike) && s.sigma > 0.0 && std::isfinite(s.maturity);
+        const bool valid = batch_row_valid(s);
         if (priced) priced[i] = valid ? 1 : 0;
         if (!valid) continue;
-        // A row longer than the row kernels' LDS tables reach (more than four years of trading days), or any row of a call
-        // with more than 256 paths per row or an order above 4, is priced after the batch through the single-contract
-        // entry points, on the same Philox path ids: never refused, never answered with zeros.
-        if (s.n_steps > BATCH_MAX_STEPS || n_paths > 256 || poly_order > 4) {
+        if (batch_row_singly(s, n_paths, poly_order)) {
             long_rows.push_back(i);
             continue;
         }

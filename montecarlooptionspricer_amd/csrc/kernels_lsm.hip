@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void k_lsm_reduce_solve(const double* partials
         const double* mc = do_reduce ? sm : moments;
         if (rf.centered) {
             if (mc[0] >= min_count) {
-                lsm_solve_centered(mc, nb, rf.mu, rf.K, sm_c, sm_ws);
+                lsm_solve_centered_everywhere(mc, nb, rf.mu, rf.K, sm_c, sm_ws);  // (MartingaleOptimization's re-fit: run_martingale)
             } else {  // too few samples: coefficients stay 0 (as in lsm_solve_nb)
                 for (int t = 0; t < LSM_COEF_DOUBLES; ++t) sm_c[t] = 0.0;
                 sm_c[LSM_C_COUNT] = mc[0];

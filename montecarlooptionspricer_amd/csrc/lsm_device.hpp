@@ -344,6 +344,57 @@ __device__ __noinline__ void lsm_solve_centered(const double* mc, int nb, double
     }
 }
 
+// The refined solve for a caller that evaluates the fitted polynomial AWAY from the regression's samples: MartingaleOptimization,
+// whose martingale M(S) is read at every date of every path (MartingaleOptimizationPricer.cpp:100-121, :178-187).  Where the
+// samples hold fewer distinct prices than the basis has functions (kk < nb above: two paths that both stop at date 0 put S0
+// into the regression twice), the least-squares polynomial is not unique.  All of them agree AT the samples, which is all LSM
+// reads, so lsm_solve_centered is free to return F^-1 P_k z, the one of minimum norm in the equilibrated y coefficients; Eigen's
+// is the one of minimum norm in the RAW monomial coefficients, c_raw = V_k S_k^-1 W_k^T z, and away from the samples that is
+// another polynomial (measured: 8.5e-4 K in the price of a two-path row at order 3).  lsm_solve_centered leaves what this
+// needs in its workspace: the rotated rows of B are sigma_e v_e^T, so c_raw = sum_e B_e (W^T z)_e / sigma_e^2 over the kept e,
+// and the coefficients in y are T c_raw.  Wherever the fit is unique (kk == nb) the result is lsm_solve_centered's, bit for bit.
+// Two calls one after the other, lsm_solve_centered itself untouched: the kernels that call only that one stay as they are.
+__device__ __noinline__ void lsm_raw_minimum_norm(const double* mc, int nb, double* coef, double* ws) {
+    double* T = ws + 4 * nb * nb;   // (the carve-up of lsm_solve_centered)
+    double* B = T + nb * nb;
+    double* W = B + nb * nb;
+    double* craw = W + nb * nb;     // d[]: free once F is built
+    double* z = craw + nb;
+    double* sig = z + nb;
+    int kk = 0;
+    while (kk < nb && !(sig[kk] < 0.0)) ++kk;
+    if (kk == 0 || kk == nb) return;
+    double smax = 0.0;
+#pragma unroll 1
+    for (int e = 0; e < kk; ++e) smax = fmax(smax, sig[e]);
+    const double thr = fmin(mc[0], (double)nb) * 2.220446049250313e-16 * smax;  // Eigen: min(rows, cols) eps sigma_max
+#pragma unroll 1
+    for (int k = 0; k < nb; ++k) craw[k] = 0.0;
+#pragma unroll 1
+    for (int e = 0; e < kk; ++e) {
+        if (!(sig[e] > thr)) continue;
+        double proj = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < kk; ++a) proj += W[a * kk + e] * z[a];
+        const double w = proj / (sig[e] * sig[e]);
+#pragma unroll 1
+        for (int k = 0; k < nb; ++k) craw[k] += B[e * nb + k] * w;
+    }
+#pragma unroll 1
+    for (int a = 0; a < nb; ++a) {
+        double v = 0.0;
+#pragma unroll 1
+        for (int k = a; k < nb; ++k) v += T[a * nb + k] * craw[k];
+        coef[a] = v;
+    }
+}
+__device__ __forceinline__ void lsm_solve_centered_everywhere(const double* mc, int nb, double mu, double K, double* coef, double* ws) {
+    double* sig = ws + 7 * nb * nb + 2 * nb;
+    for (int e = 0; e < nb; ++e) sig[e] = -1.0;  // lsm_solve_centered writes sig[e] >= 0 for its kk kept directions only
+    lsm_solve_centered(mc, nb, mu, K, coef, ws);
+    lsm_raw_minimum_norm(mc, nb, coef, ws);
+}
+
 // The centred re-fit of the K-tangent sweep (mcg_greeks_lsm): mc[3p+2 .. 4p+3) are the tangent's cross sums.  The
 // eigen- and singular-vector work and Eigen's rank rule read the power sums only, so the tangent coefficients are the same
 // projector applied to the tangent's right-hand side: the solve above once more with those cross sums in place (mc is

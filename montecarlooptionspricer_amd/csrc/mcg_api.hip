@@ -1231,6 +1231,34 @@ int mcg_debug_batch_budget(mcg_ctx* ctx, size_t bytes) {
     return MCG_OK;
 }
 
+int mcg_debug_batch_row_dump(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt, int num_branches,
+                             int poly_order, int max_iterations, uint64_t seed, double* out, int64_t row, double* amp, double* comp,
+                             double* block) {
+    const int bad = batch_args(ctx, rows, n_rows, n_paths, dt, poly_order, max_iterations, out, "out");
+    if (bad) return bad;
+    if (!amp || !comp || !block) return fail(MCG_ERR_INVALID, "amp/comp/block is NULL");
+    if (row < 0 || row >= n_rows) return fail(MCG_ERR_INVALID, "row %lld is not one of the call's %lld rows", (long long)row, (long long)n_rows);
+    if (!batch_row_valid(rows[row])) return fail(MCG_ERR_INVALID, "row %lld is invalid (the call answers it with zeros): nothing to dump", (long long)row);
+    if (batch_row_singly(rows[row], n_paths, poly_order))
+        return fail(MCG_ERR_INVALID, "row %lld is priced singly (more than 1020 steps, more than 256 paths or an order above 4): the row kernels hold nothing of it",
+                    (long long)row);
+    MCG_HIP(hipSetDevice(ctx->device));
+    BatchDump dump{row, amp, comp, block, false};
+    struct Unset {   // the context forgets the dump on every way out
+        mcg_ctx* c;
+        ~Unset() { c->batch_dump = nullptr; }
+    } unset{ctx};
+    ctx->batch_dump = &dump;
+    int rc;
+    try {
+        rc = run_batch_rows(ctx, rows, n_rows, n_paths, r, dt, num_branches, poly_order, max_iterations, seed, out, nullptr);
+    } catch (const std::exception& e) {
+        return fail(MCG_ERR_OOM, "mcg_debug_batch_row_dump: %s", e.what());
+    }
+    if (rc == MCG_OK && !dump.found) return fail(MCG_ERR_INVALID, "row %lld was in no chunk of the call", (long long)row);
+    return rc;
+}
+
 // ---- host-only pieces --------------------------------------------------------------------------
 int mcg_estimate_params(const double* hist, size_t n, double out5[5]) {
     if (!out5) return fail(MCG_ERR_INVALID, "out5 is NULL");

@@ -63,6 +63,12 @@ struct EventPair {
     int64_t launches;  // kernel launches the pair brackets (1, or a whole queued sequence: TimedLaunch)
 };
 
+struct BatchDump {  // mcg_debug_batch_row_dump: where the chunk that holds `row` copies that row's device data (run_batch_chunk)
+    int64_t row;
+    double *amp, *comp, *block;
+    bool found;
+};
+
 struct ShmComm;  // comm_shm.cpp: node-local collective over POSIX shared memory
 constexpr int SHM_MAX_RANKS = 16;     // processes (GPUs) sharing one segment
 constexpr int SHM_MAX_ROUNDS = 4096;  // exchange rounds of one LSM sweep the device mailbox holds (2 per exercise date at most)
@@ -83,6 +89,7 @@ struct mcg_ctx {
     long long lsm_date_spin_limit = -1;  // mcg_debug_lsm_date_fault: polls before a consumer of k_lsm_date gives a slot up (< 0: default)
     int lsm_date_hook[4] = {0, 0, 0, 0}; //   {mode, date, workgroup, delay}: that workgroup's partial moments never land (1) / land late (2)
     size_t batch_budget = 0;             // mcg_debug_batch_budget: workspace bytes of one chunk of mcg_batch_price_rows (0: a quarter of free memory)
+    mcg::BatchDump* batch_dump = nullptr;  // mcg_debug_batch_row_dump: set for the length of its one call
     // batched rows (kernels_batch.hip): the two latency-bound row pricers run beside the two issue-bound ones on a second stream
     hipStream_t batch_aux = nullptr;
     hipEvent_t batch_fork = nullptr, batch_join = nullptr;
@@ -338,6 +345,10 @@ int run_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
 // priced (optional, n_rows bytes): 1 where the row was priced, 0 where the driver's own checks answer it with zeros
 int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt, int num_branches,
                    int poly_order, int max_iterations, uint64_t seed, double* out, unsigned char* priced);
+// run_batch_rows' own two questions about a row: would the reference's driver answer it with zeros, and does it leave the row
+// kernels for the single-contract entry points (mcg_debug_batch_row_dump asks them before it runs anything)
+bool batch_row_valid(const mcg_row& s);
+bool batch_row_singly(const mcg_row& s, int n_paths, int poly_order);
 int probe_write_ceiling(mcg_ctx* ctx, int64_t n_paths, int n_steps, int reps, double* gb_per_s, double* ms_per_launch);  // kernels_probe.hip
 int run_asymptotic(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
                    double sigma, double dividend, double* price);

@@ -676,6 +676,25 @@ class PathEngine:
                                             int(poly_order), int(max_iterations), int(seed), out.ctypes.data_as(dp)))
         return out
 
+    def debug_batch_row_dump(self, rows, row: int, n_paths: int = 250, r: float = 0.04, dt: float = 1.0 / 252.0,
+                             num_branches: int = 10, poly_order: int = 2, max_iterations: int = 5, seed: int = 0):
+        """Test hook (mcg_debug_batch_row_dump): batch_price_rows with the same arguments, and what the row kernels held for
+        row `row`.  Returns (prices [n_rows][4], amp [M], comp [n_steps], block [n_steps + 1][n_paths], step-major)."""
+        arr = rows if isinstance(rows, C.Array) else make_rows(rows)
+        n = len(arr)
+        dp = C.POINTER(C.c_double)
+        steps = int(arr[row].n_steps) if 0 <= row < n else 0
+        M = 1
+        while M < steps:
+            M <<= 1
+        out = np.zeros((n, 4), dtype=np.float64)
+        amp, comp = np.zeros(M), np.zeros(max(steps, 1))
+        block = np.zeros((max(steps, 0) + 1, max(int(n_paths), 1)))
+        check(self._L.mcg_debug_batch_row_dump(self._ctx, arr, n, int(n_paths), r, dt, int(num_branches), int(poly_order),
+                                               int(max_iterations), int(seed), out.ctypes.data_as(dp), int(row),
+                                               amp.ctypes.data_as(dp), comp.ctypes.data_as(dp), block.ctypes.data_as(dp)))
+        return out, amp, comp[:steps], block
+
     def debug_batch_budget(self, nbytes: int) -> None:
         """Test hook (mcg_debug_batch_budget): workspace bytes of one chunk of the batched rows (0: the default)."""
         check(self._L.mcg_debug_batch_budget(self._ctx, int(nbytes)))

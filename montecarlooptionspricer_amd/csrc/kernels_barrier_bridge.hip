@@ -3,7 +3,8 @@
 // read, 16 B on the matrix route; one fp64 logarithm per element shared by up to BRIDGE_L_MAX levels kept in registers)
 // reduces every path to its survival probability P for each level of a group; the group's contracts are then evaluated on
 // row n_steps and P (k_bridge_book: the layout of k_exotic_book, per-block {sum, sum^2} through block_sum) and, after the
-// last group, reduced by k_exotic_reduce in a fixed order.  No float atomics: repeated calls are bit-identical, a path's P
+// last group, reduced by k_book_reduce in a fixed order (the entry of a per-path kernel, the book's frame and the reduction
+// are exotic_device.hpp's).  No float atomics: repeated calls are bit-identical, a path's P
 // for a level depends on that path's column and that level only, and a contract's sums do not depend on the rest of the book.
 #include <algorithm>
 #include <cmath>
@@ -151,14 +152,10 @@ __device__ __forceinline__ void bridge_scan(const BridgeArgs& a, int64_t p0) {
     }
 }
 
-// One lane per W adjacent paths, as k_path_stats.  W = 2 needs 16-byte aligned rows in both matrices (even ld, aligned base:
-// what paths_new makes); the last path of an odd count is scanned alone by its lane.
+// One lane per W adjacent paths (lane_paths); W = 2 needs 16-byte aligned rows in both matrices.
 template <bool VAR, int NL, int W>
 __global__ __launch_bounds__(256) void k_bridge_survival(const BridgeArgs a) {
-    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;
-    if (p0 >= a.n_paths) return;
-    if (W == 2 && p0 + 1 == a.n_paths) bridge_scan<VAR, NL, 1>(a, p0);
-    else bridge_scan<VAR, NL, W>(a, p0);
+    lane_paths<W>(a.n_paths, [&](int64_t p0, int64_t, auto w) { bridge_scan<VAR, NL, w.value>(a, p0); });
 }
 
 // Y of include/mcgpu.h: the vanilla payoff f on S_T weighted by the survival probability, the rebate by its complement
@@ -169,39 +166,33 @@ __device__ __forceinline__ double bridge_payoff(const mcg_exotic& c, double st, 
 }
 
 // k_exotic_book's layout over the contracts [c_lo, c_hi) of one level group, in the order of BridgePlan::order: blockIdx.y
-// counts the chunks of XB_CH contracts from c_lo's chunk on, blockIdx.x strides over the paths (a grid that depends on the
-// path count only).  A chunk that two groups share is visited by both launches; each writes the fields of its own contracts
-// only (and the one that holds the last contract zeroes the fields behind it), so k_exotic_reduce finds every field written once.
+// counts the chunks of XB_CH contracts from c_lo's chunk on, blockIdx.x strides over the paths (book_partials).  A chunk
+// that two groups share is visited by both launches; each writes the fields of its own contracts only (and the one that
+// holds the last contract zeroes the fields behind it), so k_book_reduce finds every field written once.
 __global__ __launch_bounds__(256) void k_bridge_book(const double* st_row, const double* surv, int64_t n, const mcg_exotic* book,
                                                      const int* slot, int c_lo, int c_hi, int n_contracts, int n_blocks,
                                                      double* partials) {
     __shared__ double red[XB_NF * 4];
     const int chunk = c_lo / XB_CH + blockIdx.y;
     const int c0 = chunk * XB_CH;
-    double e[XB_NF];
+    book_partials<XB_NF>(
+        n, red, partials + ((int64_t)chunk * n_blocks + blockIdx.x) * XB_NF,
+        [&](int64_t i, double (&e)[XB_NF]) {
+            const double st = st_row[i];
 #pragma unroll
-    for (int q = 0; q < XB_NF; ++q) e[q] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double st = st_row[i];
-#pragma unroll
-        for (int q = 0; q < XB_CH; ++q) {
-            const int c = c0 + q;
-            if (c >= c_lo && c < c_hi) {
-                const double x = bridge_payoff(book[c], st, surv[(int64_t)slot[c] * n + i]);
-                e[q] += x;
-                e[XB_CH + q] = fma(x, x, e[XB_CH + q]);
+            for (int q = 0; q < XB_CH; ++q) {
+                const int c = c0 + q;
+                if (c >= c_lo && c < c_hi) {
+                    const double x = bridge_payoff(book[c], st, surv[(int64_t)slot[c] * n + i]);
+                    e[XB_NS * q] += x;
+                    e[XB_NS * q + 1] = fma(x, x, e[XB_NS * q + 1]);
+                }
             }
-        }
-    }
-    block_sum<XB_NF, 4>(e, red);
-    if (threadIdx.x == 0) {
-        double* out = partials + ((int64_t)chunk * n_blocks + blockIdx.x) * XB_NF;
-#pragma unroll
-        for (int q = 0; q < XB_NF; ++q) {
-            const int c = c0 + q % XB_CH;
-            if ((c >= c_lo && c < c_hi) || (c >= n_contracts && c_hi == n_contracts)) out[q] = e[q];
-        }
-    }
+        },
+        [&](int q) {
+            const int c = c0 + q / XB_NS;
+            return (c >= c_lo && c < c_hi) || (c >= n_contracts && c_hi == n_contracts);
+        });
 }
 
 // The levels [at, at + n_live) of (barriers, is_up) as one pass's argument
@@ -221,11 +212,8 @@ static BridgeLevels bridge_levels(const double* barriers, const int* is_up, int 
 // MCG_K_EXOTIC.  V null: the scalar route with w = (sigma sigma) dt.
 static int launch_bridge_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double dt, int first_row,
                                   const BridgeLevels& lv, double* d_out) {
-    const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0 &&
-                      (!V || ((V->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(V->data) & 15) == 0));
-    const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
-    const int64_t n_blocks = launch_units((lanes + 255) / 256);
-    if (n_blocks < 0) return MCG_ERR_INVALID;
+    const StreamGrid g = stream_grid(P, V);
+    if (g.n_blocks < 0) return MCG_ERR_INVALID;
     BridgeArgs a{};
     a.data = P->data;
     a.var = V ? V->data : nullptr;
@@ -239,13 +227,13 @@ static int launch_bridge_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_pa
     a.out = d_out;
     a.lv = lv;
     const int nl = lv.n_live <= 1 ? 1 : lv.n_live <= 2 ? 2 : lv.n_live <= 4 ? 4 : BRIDGE_L_MAX;
-    return PathLaunch{ctx, n_blocks}.run(MCG_K_EXOTIC, [&] {
+    return PathLaunch{ctx, g.n_blocks}.run(MCG_K_EXOTIC, [&] {
         dispatch_flags(
             [&](auto var, auto w, auto hi, auto lo) {
                 constexpr int NL = hi.value ? (lo.value ? BRIDGE_L_MAX : 4) : (lo.value ? 2 : 1);
-                hipLaunchKernelGGL((k_bridge_survival<var.value, NL, w.value ? 2 : 1>), dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream, a);
+                hipLaunchKernelGGL((k_bridge_survival<var.value, NL, w.value ? 2 : 1>), dim3((unsigned)g.n_blocks), dim3(256), 0, ctx->stream, a);
             },
-            V != nullptr, wide, nl >= 4, nl == 2 || nl == BRIDGE_L_MAX);
+            V != nullptr, g.wide, nl >= 4, nl == 2 || nl == BRIDGE_L_MAX);
     });
 }
 
@@ -288,7 +276,7 @@ int run_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, do
         slot[(size_t)s] = plan.level_of[(size_t)plan.order[(size_t)s]] % BRIDGE_L_MAX;
     }
     const int n_sums = 2 * nc + 1, n_chunks = (nc + XB_CH - 1) / XB_CH;
-    const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+    const int n_blocks = book_blocks(ctx, n);
     const size_t n_part = (size_t)n_chunks * n_blocks * XB_NF;
     std::vector<double> h;
     const int rc = exotic_sums_frame(ctx, n, (size_t)BRIDGE_L_MAX * n + n_part + n_sums, n_sums, h, [&](double* d_surv, double* d_sums) -> int {
@@ -314,22 +302,7 @@ int run_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, do
         return MCG_OK;
     });
     if (rc) return rc;
-    const double np = h[2 * (size_t)nc];
-    if (!(np >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
-    const double disc = std::exp(-r * T);
-    for (int s = 0; s < nc; ++s) {
-        const int c = plan.order[(size_t)s];
-        double se;
-        sums_to_mean_stderr(h[2 * (size_t)s], h[2 * (size_t)s + 1], np, &price[c], &se);
-        price[c] = disc * price[c];
-        if (std_err) std_err[c] = disc * se;
-        if (sums) {
-            sums[2 * (size_t)c] = h[2 * (size_t)s];
-            sums[2 * (size_t)c + 1] = h[2 * (size_t)s + 1];
-        }
-    }
-    if (sums) sums[2 * (size_t)nc] = np;
-    return MCG_OK;
+    return exotic_prices_from_sums(h, nc, plan.order.data(), r, T, price, std_err, sums);
 }
 
 }  // namespace mcg

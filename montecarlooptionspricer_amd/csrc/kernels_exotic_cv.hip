@@ -7,8 +7,8 @@
 //                    issue-bound on the VALU like the GBM generator's loop.
 // k_exotic_book_cv   k_exotic_book with nine sums a contract instead of two: {Y, Y^2, d_a, d_a^2, Y d_a, d_b, d_b^2, Y d_b,
 //                    d_a d_b}, d = control - its mean, the controls read from the paths' statistics or the twin's.  Four
-//                    contracts (36 accumulators) a workgroup on blockIdx.y, a grid over the paths that depends on the path
-//                    count only, block_sum, then k_exotic_cv_reduce in a fixed order.  No float atomics.
+//                    contracts (36 accumulators) a workgroup on blockIdx.y, on the same frame (book_partials), then
+//                    k_book_reduce<CV_CH, CV_NS> in a fixed order (both exotic_device.hpp's).  No float atomics.
 // The host arithmetic on the sums is host/exotics_cv.cpp.
 #include <algorithm>
 #include <cmath>
@@ -129,10 +129,7 @@ __global__ __launch_bounds__(256) void k_exotic_book_cv(const double* stats, con
     __shared__ double red[CV_NF * 4];
     const int c0 = blockIdx.y * CV_CH;
     const int live = min(CV_CH, n_contracts - c0);
-    double e[CV_NF];
-#pragma unroll
-    for (int q = 0; q < CV_NF; ++q) e[q] = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    book_partials<CV_NF>(n, red, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CV_NF, [&](int64_t i, double (&e)[CV_NF]) {
         const double st = stats[i], A = stats[n + i], G = geo ? stats[2 * n + i] : 0.0, mn = stats[3 * n + i], mx = stats[4 * n + i];
         double tst = 0.0, tA = 0.0, tG = 0.0, tmn = 0.0, tmx = 0.0;
         if (twin) {
@@ -165,29 +162,7 @@ __global__ __launch_bounds__(256) void k_exotic_book_cv(const double* stats, con
                 s[8] = fma(da, db, s[8]);
             }
         }
-    }
-    block_sum<CV_NF, 4>(e, red);
-    if (threadIdx.x == 0) {
-        double* out = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * CV_NF;
-#pragma unroll
-        for (int q = 0; q < CV_NF; ++q) out[q] = e[q];
-    }
-}
-
-// One workgroup per chunk, like k_exotic_reduce: wave w takes the fields w, w + 4, ...; lane l the blocks l, l + 64, ...,
-// then the butterfly.  sums = nine per contract, then the local path count.
-__global__ __launch_bounds__(256) void k_exotic_cv_reduce(const double* partials, int n_blocks, int n_contracts, double n_local,
-                                                          double* sums) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double* src = partials + (int64_t)blockIdx.x * n_blocks * CV_NF;
-    for (int q = wave; q < CV_NF; q += 4) {
-        double s = 0.0;
-        for (int b = lane; b < n_blocks; b += 64) s += src[(int64_t)b * CV_NF + q];
-        s = wave_sum(s);
-        const int c = blockIdx.x * CV_CH + q / CV_NS;
-        if (lane == 0 && c < n_contracts) sums[CV_NS * c + q % CV_NS] = s;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) sums[CV_NS * n_contracts] = n_local;
+    });
 }
 
 static int launch_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* tw, int n_steps, int first_row, int64_t n_paths, double* d_stats) {
@@ -222,10 +197,6 @@ static int run_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* tw, int n_steps,
                           [&](double* d) { return launch_gbm_twin_stats(ctx, tw, n_steps, first_row, n_paths, d); });
 }
 
-static bool reads_g(const mcg_control& k) {
-    return k.form == MCG_CV_G || (k.form == MCG_CV_PAYOFF && (k.x.kind == MCG_X_ASIAN_GEO_FIXED || k.x.kind == MCG_X_ASIAN_GEO_FLOAT));
-}
-
 // Workspace (one pool buffer): [5 n statistics][5 n twin statistics, with a twin][n_chunks * n_blocks * CV_NF partials]
 // [9 n_contracts + 1 sums].  Parameters (ctx->weights): [book][controls][ctrl].
 static int exotic_cv_sums(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* TP, const mcg_gbm_twin* tw, int first_row,
@@ -234,7 +205,7 @@ static int exotic_cv_sums(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* TP,
     const int64_t n = P->n_paths;
     const bool twin = TP || tw;
     const int n_sums = CV_NS * nc + 1, n_chunks = (nc + CV_CH - 1) / CV_CH;
-    const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+    const int n_blocks = book_blocks(ctx, n);
     const size_t n_part = (size_t)n_chunks * n_blocks * CV_NF;
     const size_t n_stats = (size_t)CV_Q * n * (twin ? 2 : 1);
     const size_t book_d = (size_t)nc * sizeof(mcg_exotic) / sizeof(double), ctl_d = (size_t)n_controls * sizeof(mcg_control) / sizeof(double);
@@ -244,13 +215,9 @@ static int exotic_cv_sums(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* TP,
     std::memcpy(params.data() + book_d + ctl_d, ctrl, (size_t)nc * 2 * sizeof(int));
     return exotic_sums_frame(ctx, n, n_stats + n_part + n_sums, n_sums, h, [&](double* d_stats, double* d_sums) -> int {
         double *d_twin = twin ? d_stats + CV_Q * n : nullptr, *d_part = d_stats + n_stats;
-        bool geo = false, geo_twin = false;
-        for (int c = 0; c < nc; ++c) geo = geo || book[c].kind == MCG_X_ASIAN_GEO_FIXED || book[c].kind == MCG_X_ASIAN_GEO_FLOAT;
-        for (int k = 0; k < n_controls; ++k) {
-            if (!reads_g(controls[k])) continue;
-            if (controls[k].on_twin) geo_twin = true;
-            else geo = true;
-        }
+        bool geo = std::any_of(book, book + nc, [](const mcg_exotic& c) { return reads_g(c); }), geo_twin = false;
+        for (int k = 0; k < n_controls; ++k)
+            if (reads_g(controls[k])) (controls[k].on_twin ? geo_twin : geo) = true;
         HostPiece up[] = {{params.data(), params.size() * sizeof(double)}};
         int rc = upload_params(ctx, up);
         if (rc) return rc;
@@ -265,7 +232,7 @@ static int exotic_cv_sums(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* TP,
                                (geo_twin || tw) ? 1 : 0, reinterpret_cast<const mcg_exotic*>(up[0].at),
                                reinterpret_cast<const mcg_control*>(up[0].at + book_d), reinterpret_cast<const int*>(up[0].at + book_d + ctl_d),
                                nc, d_part);
-            hipLaunchKernelGGL(k_exotic_cv_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
+            hipLaunchKernelGGL((k_book_reduce<CV_CH, CV_NS>), dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
         }
         MCG_HIP(hipGetLastError());
         return MCG_OK;

@@ -2,8 +2,9 @@
 // five statistics of k_path_stats and the five more their tangents need (k_path_tangent_stats: the same stream of 8 B per
 // path and date, 80 B per path written; with LOGS one fp64 logarithm per element); a book of contracts is then evaluated on
 // those statistics and on rows 0 and 1 (k_exotic_greeks_book: per-block {sum, sum^2} of six estimators a contract through
-// greeks_block_store, k_exotic_greeks_reduce: fixed order).  No float atomics: repeated calls are bit-identical, and a
-// contract's sums do not depend on the rest of the book.  The estimators are stated in include/mcgpu.h.
+// greeks_block_store, k_greeks_reduce with one workgroup per chunk: fixed order).  No float atomics: repeated calls are
+// bit-identical, and a contract's sums do not depend on the rest of the book.  The estimators are stated in include/mcgpu.h.
+// The scan and the entry of a per-path kernel are exotic_device.hpp's.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -22,162 +23,15 @@ constexpr int GX_E = 6;               // estimators per contract: 0 price, 1 del
 constexpr int GX_NE = GX_E * GX_CH;
 constexpr int GX_NF = 2 * GX_NE + 2;  // greeks_block_store's fields of one chunk
 
-// Statistics of W adjacent paths over n_rows rows from col on; row0 is the same lane's place in row 0 of the matrix.
-// S_T, A, G, min and max are path_stats_scan<true, W>'s, operation for operation (sum, min, max and the product of mantissas
-// pairwise within a group of XS_ROWS rows, then one dependent step per accumulator): bit-identical to mcg_path_stats.
-// On top of them, per group: J's terms pairwise like the sum; the first row of the group that holds the group's minimum
-// (maximum) by comparing the rows against it from the last to the first, taken over only where the group's minimum is
-// strictly below the running one -- the values of min and max are fmin's and fmax's as before, ties go to the lowest row.
-// LOGS: one logarithm per element feeds L (x ln x) and Q (the squared difference to the row before, rows below first_row
-// included: they are walked first, one row at a time).
-template <bool LOGS, int W>
-__device__ __forceinline__ void path_tangent_scan(const double* col, const double* row0, int64_t ld, int first_row, int n_rows,
-                                                  int64_t n_paths, int64_t p0, double* out10) {
-    double sum[W], mn[W], mx[W], last[W], prod[W], sj[W], sl[W], qq[W], lprev[W];
-    long long es[W];
-    int imn[W], imx[W];
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        sum[w] = 0.0;
-        mn[w] = std::numeric_limits<double>::infinity();
-        mx[w] = -std::numeric_limits<double>::infinity();
-        last[w] = 0.0;
-        prod[w] = 1.0;
-        es[w] = 0;
-        sj[w] = 0.0;
-        sl[w] = 0.0;
-        qq[w] = 0.0;
-        lprev[w] = 0.0;
-        imn[w] = 0;
-        imx[w] = 0;
-    }
-    if constexpr (LOGS) {
-        // ln of row 0, then the steps that end below first_row.  With first_row = 0 the scan's first row is row 0 again: its
-        // difference to lprev is exactly zero.
-        double x[W];
-        xs_load<W>(row0, x);
-#pragma unroll
-        for (int w = 0; w < W; ++w) lprev[w] = log(x[w]);
-        for (int i = 1; i < first_row; ++i) {
-            xs_load<W>(row0 + (int64_t)i * ld, x);
-#pragma unroll
-            for (int w = 0; w < W; ++w) {
-                const double l = log(x[w]), d = l - lprev[w];
-                qq[w] = fma(d, d, qq[w]);
-                lprev[w] = l;
-            }
-        }
-    }
-    int j = 0;
-    for (; j + XS_ROWS <= n_rows; j += XS_ROWS) {
-        double x[XS_ROWS][W];
-#pragma unroll
-        for (int k = 0; k < XS_ROWS; ++k) xs_load<W>(col + (int64_t)(j + k) * ld, x[k]);
-        const double jd = (double)(first_row + j);
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            double s[XS_ROWS], lo[XS_ROWS], hi[XS_ROWS], m[XS_ROWS], t[XS_ROWS];
-            int e = 0;
-#pragma unroll
-            for (int k = 0; k < XS_ROWS; ++k) {
-                s[k] = lo[k] = hi[k] = x[k][w];
-                m[k] = xs_split(x[k][w], e);
-                t[k] = (jd + (double)k) * x[k][w];
-            }
-#pragma unroll
-            for (int h = XS_ROWS / 2; h >= 1; h >>= 1) {
-#pragma unroll
-                for (int k = 0; k < h; ++k) {
-                    s[k] += s[k + h];
-                    lo[k] = fmin(lo[k], lo[k + h]);
-                    hi[k] = fmax(hi[k], hi[k + h]);
-                    m[k] *= m[k + h];
-                    t[k] += t[k + h];
-                }
-            }
-            int klo = XS_ROWS - 1, khi = XS_ROWS - 1;
-#pragma unroll
-            for (int k = XS_ROWS - 2; k >= 0; --k) {
-                klo = x[k][w] == lo[0] ? k : klo;
-                khi = x[k][w] == hi[0] ? k : khi;
-            }
-            imn[w] = lo[0] < mn[w] ? j + klo : imn[w];
-            imx[w] = hi[0] > mx[w] ? j + khi : imx[w];
-            sum[w] += s[0];
-            mn[w] = fmin(mn[w], lo[0]);
-            mx[w] = fmax(mx[w], hi[0]);
-            last[w] = x[XS_ROWS - 1][w];
-            prod[w] = xs_split(prod[w] * m[0], e);  // < 2 * 2^8 before, [1, 2) after
-            es[w] += e;
-            sj[w] += t[0];
-            if constexpr (LOGS) {
-#pragma unroll
-                for (int k = 0; k < XS_ROWS; ++k) {
-                    const double l = log(x[k][w]), d = l - lprev[w];
-                    qq[w] = fma(d, d, qq[w]);
-                    sl[w] = fma(x[k][w], l, sl[w]);
-                    lprev[w] = l;
-                }
-            }
-        }
-    }
-    for (; j < n_rows; ++j) {  // at most XS_ROWS - 1 rows: prod stays below 2^8
-        double x[W];
-        xs_load<W>(col + (int64_t)j * ld, x);
-        const double jd = (double)(first_row + j);
-#pragma unroll
-        for (int w = 0; w < W; ++w) {
-            imn[w] = x[w] < mn[w] ? j : imn[w];
-            imx[w] = x[w] > mx[w] ? j : imx[w];
-            sum[w] += x[w];
-            mn[w] = fmin(mn[w], x[w]);
-            mx[w] = fmax(mx[w], x[w]);
-            last[w] = x[w];
-            int e = 0;
-            prod[w] *= xs_split(x[w], e);
-            es[w] += e;
-            sj[w] = fma(jd, x[w], sj[w]);
-            if constexpr (LOGS) {
-                const double l = log(x[w]), d = l - lprev[w];
-                qq[w] = fma(d, d, qq[w]);
-                sl[w] = fma(x[w], l, sl[w]);
-                lprev[w] = l;
-            }
-        }
-    }
-    const double nd = (double)n_rows, nan = std::numeric_limits<double>::quiet_NaN();
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-        const int64_t p = p0 + w;
-        out10[0 * n_paths + p] = last[w];
-        out10[1 * n_paths + p] = sum[w] / nd;
-        out10[3 * n_paths + p] = mn[w];
-        out10[4 * n_paths + p] = mx[w];
-        double ls = (double)es[w] * 0.6931471805599453094 + log(prod[w]);
-        if (!(mn[w] >= std::numeric_limits<double>::min())) {
-            ls = 0.0;
-            for (int k = 0; k < n_rows; ++k) ls += log(col[(int64_t)k * ld + w]);
-        }
-        out10[2 * n_paths + p] = exp(ls / nd);
-        out10[5 * n_paths + p] = LOGS ? sl[w] / nd : nan;
-        out10[6 * n_paths + p] = sj[w] / nd;
-        out10[7 * n_paths + p] = (double)(first_row + imn[w]);
-        out10[8 * n_paths + p] = (double)(first_row + imx[w]);
-        out10[9 * n_paths + p] = LOGS ? qq[w] : nan;
-    }
-}
-
-// One lane per W adjacent paths, as k_path_stats.  W = 2 needs 16-byte aligned rows (even ld, aligned base: what paths_new
-// makes); the last path of an odd count is scanned alone by its lane.
+// One lane per W adjacent paths (lane_paths): path_scan with the tangent statistics.  S_T, A, G, min and max are
+// bit-identical to k_path_stats<true, W>'s: the one scan computes both.
 template <bool LOGS, int W>
 __global__ __launch_bounds__(256) void k_path_tangent_stats(const double* data, int64_t ld, int64_t n_paths, int first_row, int n_rows,
                                                             double* out10) {
-    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;
-    if (p0 >= n_paths) return;
-    const double* row0 = data + p0;
-    const double* col = row0 + (int64_t)first_row * ld;
-    if (W == 2 && p0 + 1 == n_paths) path_tangent_scan<LOGS, 1>(col, row0, ld, first_row, n_rows, n_paths, p0, out10);
-    else path_tangent_scan<LOGS, W>(col, row0, ld, first_row, n_rows, n_paths, p0, out10);
+    lane_paths<W>(n_paths, [&](int64_t p0, int64_t n, auto w) {
+        const double* row0 = data + p0;
+        path_scan<true, true, LOGS, w.value>(row0 + (int64_t)first_row * ld, row0, ld, first_row, n_rows, n, p0, out10);
+    });
 }
 
 // What the book kernel reads of the model and the grid; the host derives it once (run_greeks_exotics).  lr: sigma > 0 (the
@@ -293,7 +147,7 @@ __device__ __forceinline__ void gx_sample(const mcg_exotic& c, const GxModel& g,
 
 // blockIdx.y: a chunk of GX_CH contracts; blockIdx.x strides over the paths (a grid that depends on the path count only).
 // partials[(chunk * gridDim.x + blockIdx.x) * GX_NF + ...]: greeks_block_store's fields, estimator e of the chunk's contract
-// q at GX_E q + e.
+// q at GX_E q + e.  (Not on book_partials: the walk also takes the range of row 0 and ends in greeks_block_store.)
 __global__ __launch_bounds__(256) void k_exotic_greeks_book(const double* stats, const double* row0, const double* row1, int64_t n,
                                                             GxModel g, const mcg_exotic* book, int n_contracts, double* partials) {
     __shared__ double red[2 * GX_NE * 4];
@@ -327,45 +181,17 @@ __global__ __launch_bounds__(256) void k_exotic_greeks_book(const double* stats,
     greeks_block_store<GX_NE>(e, lo, hi, red, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * GX_NF);
 }
 
-// One workgroup per chunk, k_greeks_reduce's order: wave w takes the fields w, w + 4, ...; lane l the blocks l, l + 64, ...,
-// then the butterfly.  The last two fields are a minimum and a maximum, the others sums.  sums[chunk * GX_NF + field].
-// (k_greeks_reduce serves one set of fields a launch and is kept instruction for instruction; a book has up to 256 chunks.)
-__global__ __launch_bounds__(256) void k_exotic_greeks_reduce(const double* partials, int n_blocks, double* sums) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double* src = partials + (int64_t)blockIdx.x * n_blocks * GX_NF;
-    for (int q = wave; q < GX_NF; q += 4) {
-        const int kind = q == GX_NF - 2 ? 1 : q == GX_NF - 1 ? 2 : 0;  // 0 sum, 1 min, 2 max
-        double s = kind == 0 ? 0.0 : kind == 1 ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity();
-        for (int b = lane; b < n_blocks; b += 64) {
-            const double x = src[(int64_t)b * GX_NF + q];
-            s = kind == 0 ? s + x : kind == 1 ? fmin(s, x) : fmax(s, x);
-        }
-        if (kind == 0) {
-            s = wave_sum(s);
-        } else {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const double y = __shfl_xor(s, o);
-                s = kind == 1 ? fmin(s, y) : fmax(s, y);
-            }
-        }
-        if (lane == 0) sums[(int64_t)blockIdx.x * GX_NF + q] = s;
-    }
-}
-
 int launch_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool logs, double* d_stats) {
     const int n_rows = P->n_steps - first_row + 1;
-    const bool wide = (P->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(P->data) & 15) == 0;
-    const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
-    const int64_t n_blocks = launch_units((lanes + 255) / 256);
-    if (n_blocks < 0) return MCG_ERR_INVALID;
-    return PathLaunch{ctx, n_blocks}.run(MCG_K_EXOTIC, [&] {
+    const StreamGrid g = stream_grid(P);
+    if (g.n_blocks < 0) return MCG_ERR_INVALID;
+    return PathLaunch{ctx, g.n_blocks}.run(MCG_K_EXOTIC, [&] {
         dispatch_flags(
             [&](auto l, auto w) {
-                hipLaunchKernelGGL((k_path_tangent_stats<l.value, w.value ? 2 : 1>), dim3((unsigned)n_blocks), dim3(256), 0, ctx->stream,
+                hipLaunchKernelGGL((k_path_tangent_stats<l.value, w.value ? 2 : 1>), dim3((unsigned)g.n_blocks), dim3(256), 0, ctx->stream,
                                    P->data, P->ld, P->n_paths, first_row, n_rows, d_stats);
             },
-            logs, wide);
+            logs, g.wide);
     });
 }
 
@@ -374,13 +200,14 @@ int run_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool
         ctx, P->n_paths, host_out10, "tangent", [&](double* d) { return launch_path_tangent_stats(ctx, P, first_row, logs, d); }, XT_Q);
 }
 
-// Workspace (one pool buffer): [10 n statistics][n_chunks * n_blocks * GX_NF partials][n_chunks * GX_NF sums].
+// Workspace (one pool buffer): [10 n statistics][n_chunks * n_blocks * GX_NF partials][n_chunks * GX_NF sums]
+// (sums[chunk * GX_NF + field]).
 int run_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, double sigma, double T, int first_row,
                        const mcg_exotic* book, int nc, mcg_greeks* out) {
     const int64_t n = P->n_paths;
     const bool lr = sigma > 0.0;
     const int n_chunks = (nc + GX_CH - 1) / GX_CH, n_sums = n_chunks * GX_NF;
-    const int n_blocks = greeks_blocks(ctx, n);
+    const int n_blocks = book_blocks(ctx, n);
     const size_t n_part = (size_t)n_chunks * n_blocks * GX_NF;
     GxModel g{};
     g.T = T;
@@ -408,7 +235,7 @@ int run_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, dou
             TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
             hipLaunchKernelGGL(k_exotic_greeks_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, P->data, P->data + P->ld,
                                n, g, reinterpret_cast<const mcg_exotic*>(up[0].at), nc, d_part);
-            hipLaunchKernelGGL(k_exotic_greeks_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, d_sums);
+            enqueue_greeks_reduce(ctx, d_part, n_blocks, GX_NF, n_chunks, d_sums);
         }
         MCG_HIP(hipGetLastError());
         return MCG_OK;

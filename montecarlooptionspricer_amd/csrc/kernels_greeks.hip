@@ -77,10 +77,13 @@ __global__ __launch_bounds__(256) void k_greeks_lsm(const double* V, const doubl
     greeks_block_store<GK_LSM>(e, lo, hi, red, partials + (int64_t)blockIdx.x * (2 * GK_LSM + 2));
 }
 
-// partials[n_blocks][nf] -> out[nf] in a fixed order: wave w takes the fields w, w + 4, ...; lane l the blocks l, l + 64, ...,
-// then the butterfly.  The last two fields are a minimum and a maximum, the others sums.
+// partials[chunk][n_blocks][nf] -> out[chunk][nf], one workgroup per chunk (blockIdx.x; the European and LSM Greeks have
+// one, the exotics book one per GX_CH contracts), in a fixed order: wave w takes the fields w, w + 4, ...; lane l the blocks
+// l, l + 64, ..., then the butterfly.  The last two fields are a minimum and a maximum, the others sums.
 __global__ __launch_bounds__(256) void k_greeks_reduce(const double* partials, int n_blocks, int nf, double* out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    partials += (int64_t)blockIdx.x * n_blocks * nf;
+    out += (int64_t)blockIdx.x * nf;
     for (int q = wave; q < nf; q += 4) {
         const int kind = q == nf - 2 ? 1 : q == nf - 1 ? 2 : 0;  // 0 sum, 1 min, 2 max
         double s = kind == 0 ? 0.0 : kind == 1 ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity();
@@ -101,13 +104,17 @@ __global__ __launch_bounds__(256) void k_greeks_reduce(const double* partials, i
     }
 }
 
+void enqueue_greeks_reduce(mcg_ctx* ctx, const double* d_part, int n_blocks, int nf, int n_chunks, double* d_out) {
+    hipLaunchKernelGGL(k_greeks_reduce, dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nf, d_out);
+}
+
 // Reduce NE estimators' partials of n_blocks blocks and bring {sums, sums of squares, min, max of row 0} to the host.
 static int greeks_reduce(mcg_ctx* ctx, int n_blocks, int ne, double* host) {
     const int nf = 2 * ne + 2;
     double* d = ctx->scalars + SC_GREEKS;
     {
         TimedLaunch t(ctx, MCG_K_PAYOFF);
-        hipLaunchKernelGGL(k_greeks_reduce, dim3(1), dim3(256), 0, ctx->stream, ctx->partials, n_blocks, nf, d);
+        enqueue_greeks_reduce(ctx, ctx->partials, n_blocks, nf, 1, d);
     }
     MCG_HIP(hipGetLastError());
     MCG_HIP(hipMemcpyAsync(ctx->h_scalars + SC_GREEKS, d, nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -119,7 +126,7 @@ static int greeks_reduce(mcg_ctx* ctx, int n_blocks, int ne, double* host) {
 int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, double T, int is_call, double sigma,
                         mcg_greeks* out) {
     const int64_t n = P->n_paths;
-    const int n_blocks = greeks_blocks(ctx, n);
+    const int n_blocks = book_blocks(ctx, n);
     constexpr int nf = 2 * GK_EU + 2;
     int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)n_blocks * nf);
     if (rc) return rc;
@@ -147,7 +154,7 @@ int run_greeks_european(mcg_ctx* ctx, const mcg_paths* P, double K, double r, do
 
 int greeks_lsm_final(mcg_ctx* ctx, const mcg_paths* P, double K, const double* V, const double* dV, mcg_greeks* out) {
     const int64_t n = P->n_paths;
-    const int n_blocks = greeks_blocks(ctx, n);
+    const int n_blocks = book_blocks(ctx, n);
     constexpr int nf = 2 * GK_LSM + 2;
     int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)n_blocks * nf);
     if (rc) return rc;

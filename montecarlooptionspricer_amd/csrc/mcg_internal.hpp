@@ -292,10 +292,12 @@ inline void greeks_all_nan(mcg_greeks* out) {
     const double nan = std::nan("");
     *out = mcg_greeks{nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan, nan};
 }
-// the x grid of a Greeks kernel: it depends on the path count only
-inline int greeks_blocks(const mcg_ctx* ctx, int64_t n) {
+// the x grid of a Greeks or book kernel: it depends on the path count only
+inline int book_blocks(const mcg_ctx* ctx, int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
 }
+// k_greeks_reduce over n_chunks sets of n_blocks x nf partials into d_out[n_chunks][nf] (no timing span of its own)
+void enqueue_greeks_reduce(mcg_ctx* ctx, const double* d_part, int n_blocks, int nf, int n_chunks, double* d_out);
 // Greeks of the exotics book (kernels_exotic_greeks.hip): k_path_tangent_stats over rows first_row .. n_steps (and, with logs,
 // the rows before them for Q) of P into d_stats[10][n_paths]; one launch under MCG_K_EXOTIC
 int launch_path_tangent_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool logs, double* d_stats);
@@ -306,7 +308,11 @@ int run_greeks_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double q, dou
 int run_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, double* host_out5);
 int run_exotics(mcg_ctx* ctx, const mcg_paths* P, double r, double T, int first_row, const mcg_exotic* book, int n_contracts,
                 double* price, double* std_err, double* sums);
-// ... their pieces, shared with the control-variate pricer (kernels_exotic_cv.hip):
+// ... their pieces, shared with the control-variate pricer (kernels_exotic_cv.hip) and the bridge pricer
+// (kernels_barrier_bridge.hip); the device's share is exotic_device.hpp:
+// does this contract, or this control, read the geometric mean
+inline bool reads_g(const mcg_exotic& x) { return x.kind == MCG_X_ASIAN_GEO_FIXED || x.kind == MCG_X_ASIAN_GEO_FLOAT; }
+inline bool reads_g(const mcg_control& k) { return k.form == MCG_CV_G || (k.form == MCG_CV_PAYOFF && reads_g(k.x)); }
 // k_path_stats over rows first_row .. n_steps of P into d_stats[5][n_paths] (G only with geo); one launch under MCG_K_EXOTIC
 int launch_path_stats(mcg_ctx* ctx, const mcg_paths* P, int first_row, bool geo, double* d_stats);
 // the all-reduce of a payload that may exceed what the node-local collective carries in one call
@@ -325,8 +331,14 @@ int exotic_sums_frame(mcg_ctx* ctx, int64_t n, size_t ws_doubles, int n_sums, st
 // mcg_api.hip: what mcg_price_exotics rejects of (ctx, paths, first_row) and of one contract (`what` names it in the message)
 int exotic_args(mcg_ctx* ctx, const mcg_paths* P, int first_row);
 int exotic_contract_check(const mcg_exotic& x, const char* what, int index);
-// k_exotic_reduce over the (n_contracts + XB_CH - 1) / XB_CH chunks of a book kernel's partials (no timing span of its own)
+// k_book_reduce<XB_CH, XB_NS> over the (n_contracts + XB_CH - 1) / XB_CH chunks of the partials of k_exotic_book or
+// k_bridge_book (no timing span of its own)
 void enqueue_exotic_reduce(mcg_ctx* ctx, const double* d_part, int n_blocks, int n_contracts, double n_local, double* d_sums);
+// The end of run_exotics and run_barriers_bridge: h = {sum, sum^2} of n_contracts payoffs, slot s that of contract order[s]
+// (order null: the book's own), then the path count -> discounted price and std_err (optional) per contract, and sums
+// (optional) as include/mcgpu.h states them, in the book's order
+int exotic_prices_from_sums(const std::vector<double>& h, int n_contracts, const int* order, double r, double T, double* price,
+                            double* std_err, double* sums);
 // Brownian-bridge barrier prices (kernels_barrier_bridge.hip; the host part in host/barrier_bridge.cpp).  V: the variance
 // matrix of P's shape, or null for the scalar route w = (sigma sigma) dt.
 int run_barrier_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double dt, int first_row,

@@ -2,6 +2,7 @@
 // (launch_gbm, launch_rbergomi, launch_heston_scheme, launch_localvol, launch_sobol, launch_gbm_multi / launch_paths_combine,
 // launch_gbm_twin_stats) does around its kernel.  This header states once
 //   launch_blocks     the grid of a generator: workgroups of 256 lanes, the launch limit, rows padded to 256 columns
+//   stream_grid       the grid of a kernel that reads the matrix back, one lane per one or two adjacent paths
 //   PathLaunch        the launch frame: the partial sums' buffer, the timing span, the launch error, the fused sums
 //   keep_sums         what a *_payoff generator leaves in its matrix handle
 //   set_shape_key, set_payoff   the members every generator's argument struct has under the same names
@@ -28,6 +29,19 @@ inline int64_t launch_blocks(int64_t n_paths, int ppl, const mcg_paths* P = null
     return launch_units((n_paths + 256 * ppl - 1) / (256 * ppl), P);
 }
 inline int64_t launch_blocks(const mcg_paths* P, int ppl) { return launch_blocks(P->n_paths, ppl, P); }
+
+// The grid of a kernel that streams P (and V, where given) with one lane per W adjacent paths (lane_paths, exotic_device.hpp):
+// wide, W = 2, where every row of either matrix is 16-byte aligned (even ld, aligned base); n_blocks as launch_units gives it
+struct StreamGrid {
+    bool wide;
+    int64_t n_blocks;
+};
+inline StreamGrid stream_grid(const mcg_paths* P, const mcg_paths* V = nullptr) {
+    auto aligned = [](const mcg_paths* M) { return !M || ((M->ld & 1) == 0 && (reinterpret_cast<uintptr_t>(M->data) & 15) == 0); };
+    const bool wide = aligned(P) && aligned(V);
+    const int64_t lanes = wide ? (P->n_paths + 1) / 2 : P->n_paths;
+    return {wide, launch_units((lanes + 255) / 256)};
+}
 
 // the end of a *_payoff generator: rc is what finish_sums or launch_payoff_sums returned for P->sums; on success P
 // holds the (all-reduced, if a collective is installed) totals of the (K, is_call) payoff

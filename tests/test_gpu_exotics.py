@@ -224,6 +224,27 @@ def test_path_counts(eng, n_paths):
         P.free()
 
 
+@pytest.mark.parametrize("n_paths", [1, 2, 257])           # the lone path, one full vector lane, an odd count over a block edge
+@pytest.mark.parametrize("n_rows", [1, 2, 7, 8, 9, 15, 16, 17])
+def test_scan_groups_and_tails(eng, n_rows, n_paths):
+    """The scan's groups of 8 rows and its tail of up to 7, at every monitored row count around one and two groups, reached
+    with first_row = 1 and (from two rows on) first_row = 0; the tangent statistics' first five are the same bits."""
+    for first_row in (1, 0) if n_rows > 1 else (1,):
+        n_steps = n_rows + first_row - 1
+        where = (n_rows, n_paths, first_row)
+        P = eng.gbm(17, 100.0, 0.04, 0.3, 0.02, n_steps, n_paths)
+        X = P.to_host()
+        assert X[:, first_row:].shape == (n_paths, n_rows)
+        got = eng.path_stats(P, first_row)
+        check_stats(got, stats_numpy(X, first_row), where)
+        for with_logs in (True, False):
+            t = eng.path_tangent_stats(P, first_row, with_logs=with_logs)
+            assert t.shape == (10, n_paths) and bits(t[:5]) == bits(got), (where, with_logs)
+            assert np.array_equal(t[7], first_row + np.argmin(X[:, first_row:], axis=1)), (where, with_logs)
+            assert np.array_equal(t[8], first_row + np.argmax(X[:, first_row:], axis=1)), (where, with_logs)
+        P.free()
+
+
 def test_other_sources_of_a_matrix(eng):
     # uploaded from the host, with a zero among its values (numpy: log 0 = -inf, G = 0) ...
     rng = np.random.default_rng(5)

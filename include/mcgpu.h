@@ -895,6 +895,61 @@ int mcg_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* twin, int n_steps, int 
 int mcg_gbm_expectation(const mcg_control* c, double S0, double r, double q, double sigma, double dt,
         int n_steps, int first_row, double* mean);
 
+/* ---- notes on an observation schedule: autocallables and cliquets ------------------------------ */
+/* mcg_price_scheduled prices a book of structured notes whose payoff is a small state machine walked over a few dates of the
+ * matrix ("called yet?", "coupons missed so far", "knocked in?", "last reset level"): no function of the five statistics above.
+ * One kernel reads only the scheduled rows of the step-major matrix (no statistics pass, no workspace per path), and a
+ * wavefront whose paths have all been called stops reading: the pass is bounded by the bytes actually needed.
+ *
+ * Schedule: ONE per call, shared by the book.  obs[k].row is strictly increasing in 0 .. n_steps; 1 <= n_obs <= n_steps + 1;
+ * t_k = obs[k].row dt; disc_k = exp(-r (row_k dt)), formed on the host in binary64.  obs[k].flags: any of MCG_OBS_COUPON,
+ * MCG_OBS_CALL, MCG_OBS_KI (autocallables read these) and MCG_OBS_RESET (cliquets read this one).
+ * Per path: s0 is the path's own row-0 value, X_k = S[row_k] / s0 (one IEEE division), and every level test is a plain
+ * comparison of X_k.  Y is the path's PRESENT value: price = mean Y, std_err its Monte Carlo standard error; nothing further
+ * is discounted.  stop is the index of the observation at which the note ended, n_obs at maturity.
+ *
+ * MCG_S_AUTOCALL.  State alive = true, missed = 0, ki = false, Y = 0.  For k = 0 .. n_obs - 1, while alive, in this order:
+ *   1. if flags & KI and X_k <= ki_level: ki = true;
+ *   2. if flags & COUPON: if X_k >= coupon_level, Y += coupon (1 + (memory ? missed : 0)) disc_k and missed = 0;
+ *      else missed += 1;
+ *   3. if flags & CALL and X_k >= call_level: Y += disc_k, alive = false, stop = k.
+ * A path still alive after the last observation takes the maturity leg: R = (ki && X_last < put_strike) ? X_last / put_strike
+ * : 1; Y += R disc_last; stop = n_obs.  ki_level = 0 means no knock-in; call_level = +inf means never called.
+ * MCG_S_CLIQUET.  The dates flagged RESET are t_0 < ... < t_m; the first only sets the reference.  r_i = S(t_i) / S(t_{i-1}) - 1,
+ * c_i = fmin(local_cap, fmax(local_floor, r_i)), added in sequence from i = 1; Y = fmin(global_cap, fmax(global_floor, sum))
+ * disc(t_m); stop = n_obs.  +-inf is allowed in the four bounds.  With RESET on {t_1, T}, floor 0 and no caps this is the
+ * at-the-money forward-start call on the return.
+ *
+ * sums = {sum Y, sum Y^2} per contract in book order, then n.  stop_hist[c * (n_obs + 1) + k] counts the paths of contract c
+ * with stop == k: exact, integer atomics only.  mcg_sched_path_values returns Y itself, host_values[c * n_paths + p], and
+ * stop likewise: the same device function.
+ * Rules (MCG_ERR_INVALID with a message): a NULL ctx, paths, obs, book or price (host_values); paths of another ctx;
+ * n_contracts outside [1, 1024]; n_obs out of range; rows not strictly increasing or outside the matrix; flags outside the
+ * mask; a kind out of range; a non-finite r; dt <= 0 or not finite; autocall: put_strike <= 0, a non-finite coupon,
+ * coupon_level or ki_level, a NaN call_level; cliquet: fewer than two RESET dates in the schedule, a NaN bound, a floor above
+ * its cap; stop_hist on a ctx with a collective (counts of shards add by hand).  An empty matrix on a ctx without a collective
+ * is MCG_ERR_EMPTY_PATHS.  Matrices holding non-positive or non-finite values are outside the contract.
+ * Repeated calls are bit-identical (fixed-order reductions, no floating-point atomics), and a contract's sums, values and
+ * counts do not depend on what else is in the book or where in the book it stands.  The launches are booked under MCG_K_EXOTIC.
+ * Collectives: as mcg_price_exotics -- the 2 n_contracts + 1 sums are all-reduced (the node-local shm collective: in pieces of
+ * 62), every rank returns the global prices, an empty shard still takes part.
+ * Out of scope: per-contract schedules; a knock-in between observation dates (a Brownian bridge); Greeks; control variates;
+ * fusing the walk into the generators; the batched driver rows, the coalescing layer and the drop-in classes. */
+enum mcg_obs_flag   { MCG_OBS_COUPON = 1, MCG_OBS_CALL = 2, MCG_OBS_KI = 4, MCG_OBS_RESET = 8 };
+typedef struct mcg_obs   { int row; int flags; } mcg_obs;
+enum mcg_sched_kind { MCG_S_AUTOCALL = 0, MCG_S_CLIQUET = 1 };
+typedef struct mcg_sched { int kind; int memory;
+                           double call_level, coupon_level, coupon, ki_level, put_strike;   /* autocall */
+                           double local_floor, local_cap, global_floor, global_cap;         /* cliquet  */ } mcg_sched;
+
+int mcg_price_scheduled(mcg_ctx* ctx, const mcg_paths* paths, double r, double dt, const mcg_obs* obs, int n_obs,
+        const mcg_sched* book, int n_contracts, double* price, double* std_err /* may be NULL */,
+        double* sums /* may be NULL: {sum Y, sum Y^2} per contract, then n */,
+        int64_t* stop_hist /* may be NULL: [n_contracts][n_obs + 1] */);
+int mcg_sched_path_values(mcg_ctx* ctx, const mcg_paths* paths, double r, double dt, const mcg_obs* obs, int n_obs,
+        const mcg_sched* book, int n_contracts, double* host_values /* [c * n_paths + p] */,
+        int32_t* host_stop /* may be NULL, same layout */);
+
 /* Whether this ctx currently uses the one-launch LSM sweep (one launch per price up to 8.37M paths per GPU, order <= 4):
  * it is switched off for the next eight LSM prices when the in-kernel hand-shake between workgroups times out
  * (another process holding part of the GPU); mcg_price_lsm answers those -- and the call that timed out -- from the

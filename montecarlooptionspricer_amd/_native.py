@@ -45,6 +45,11 @@ TANGENT_STATS = ("S_T", "A", "G", "min", "max", "L", "J", "j_min", "j_max", "Q")
 CV_PAYOFF, CV_VANILLA, CV_ST, CV_A, CV_G = range(5)
 CONTROL_FORMS = {"payoff": CV_PAYOFF, "vanilla": CV_VANILLA, "st": CV_ST, "a": CV_A, "g": CV_G}
 
+# enum mcg_obs_flag and enum mcg_sched_kind (include/mcgpu.h): the observation schedule of mcg_price_scheduled
+OBS_COUPON, OBS_CALL, OBS_KI, OBS_RESET = 1, 2, 4, 8
+OBS_FLAGS = {"coupon": OBS_COUPON, "call": OBS_CALL, "ki": OBS_KI, "reset": OBS_RESET}
+S_AUTOCALL, S_CLIQUET = range(2)
+
 # enum mcg_combine_kind (include/mcgpu.h)
 C_NONE, C_BASKET, C_BEST_OF, C_WORST_OF = -1, 0, 1, 2
 COMBINE_KINDS = {"basket": C_BASKET, "best_of": C_BEST_OF, "worst_of": C_WORST_OF}
@@ -115,6 +120,17 @@ class GbmTwin(C.Structure):
     """mcg_gbm_twin (include/mcgpu.h): the GBM path computed in registers from the generators' own price stream."""
     _fields_ = [("seed", C.c_uint64), ("S0", C.c_double), ("r", C.c_double), ("q", C.c_double), ("sigma", C.c_double),
                 ("dt", C.c_double), ("path_begin", C.c_uint64)]
+
+
+class Obs(C.Structure):
+    """mcg_obs (include/mcgpu.h): one date of an observation schedule."""
+    _fields_ = [("row", C.c_int), ("flags", C.c_int)]
+
+
+class Sched(C.Structure):
+    """mcg_sched (include/mcgpu.h): one autocallable or cliquet of a mcg_price_scheduled book."""
+    _fields_ = [("kind", C.c_int), ("memory", C.c_int)] + [(k, C.c_double) for k in (
+        "call_level", "coupon_level", "coupon", "ki_level", "put_strike", "local_floor", "local_cap", "global_floor", "global_cap")]
 
 
 class McgError(RuntimeError):
@@ -265,6 +281,10 @@ def load_library():
                                  C.POINTER(Greeks)])
     newer("mcg_barrier_survival", [vp, vp, vp, C.c_double, C.c_double, C.c_int, dp, C.POINTER(C.c_int), C.c_int, dp])
     newer("mcg_price_barriers_bridge", [vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
+    newer("mcg_price_scheduled", [vp, vp, C.c_double, C.c_double, C.POINTER(Obs), C.c_int, C.POINTER(Sched), C.c_int, dp, dp, dp,
+                                  C.POINTER(C.c_int64)])
+    newer("mcg_sched_path_values", [vp, vp, C.c_double, C.c_double, C.POINTER(Obs), C.c_int, C.POINTER(Sched), C.c_int, dp,
+                                    C.POINTER(C.c_int32)])
     newer("mcg_gbm_twin_stats",[vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
     newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]

@@ -1040,6 +1040,73 @@ int mcg_price_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths*
     return run_barriers_bridge(ctx, P, var, sigma, r, T, first_row, book, n_contracts, price, std_err, sums);
 }
 
+// ---- notes on an observation schedule: autocallables and cliquets -----------------------------
+} // extern "C"
+namespace mcg {
+// what both schedule entry points reject of (ctx, paths, r, dt, the schedule, the book)
+static int sched_args(mcg_ctx* ctx, const mcg_paths* P, double r, double dt, const mcg_obs* obs, int n_obs, const mcg_sched* book,
+                      int n_contracts) {
+    if (!ctx || !P || !obs || !book) return fail(MCG_ERR_INVALID, "ctx/paths/obs/book is NULL");
+    if (P->ctx != ctx) return fail(MCG_ERR_INVALID, "paths belong to a different ctx");
+    if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
+    if (n_obs < 1 || n_obs > P->n_steps + 1)
+        return fail(MCG_ERR_INVALID, "n_obs must be in [1, n_steps + 1 = %d] (got %d)", P->n_steps + 1, n_obs);
+    if (!std::isfinite(r)) return fail(MCG_ERR_INVALID, "r must be finite");
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(MCG_ERR_INVALID, "dt must be positive and finite (got %g)", dt);
+    const int mask = MCG_OBS_COUPON | MCG_OBS_CALL | MCG_OBS_KI | MCG_OBS_RESET;
+    int n_reset = 0;
+    for (int k = 0; k < n_obs; ++k) {
+        if (obs[k].row < 0 || obs[k].row > P->n_steps)
+            return fail(MCG_ERR_INVALID, "observation %d: row must be in [0, n_steps = %d] (got %d)", k, P->n_steps, obs[k].row);
+        if (k > 0 && obs[k].row <= obs[k - 1].row)
+            return fail(MCG_ERR_INVALID, "observation %d: rows must be strictly increasing (%d after %d)", k, obs[k].row, obs[k - 1].row);
+        if ((obs[k].flags & ~mask) != 0) return fail(MCG_ERR_INVALID, "observation %d: flags outside the mask 0x%x (got 0x%x)", k, mask, obs[k].flags);
+        if ((obs[k].flags & MCG_OBS_RESET) != 0) ++n_reset;
+    }
+    for (int c = 0; c < n_contracts; ++c) {
+        const mcg_sched& s = book[c];
+        if (s.kind == MCG_S_AUTOCALL) {
+            if (!(s.put_strike > 0.0)) return fail(MCG_ERR_INVALID, "contract %d: put_strike must be positive (got %g)", c, s.put_strike);
+            if (!std::isfinite(s.coupon) || !std::isfinite(s.coupon_level) || !std::isfinite(s.ki_level))
+                return fail(MCG_ERR_INVALID, "contract %d: coupon, coupon_level and ki_level must be finite", c);
+            if (std::isnan(s.call_level)) return fail(MCG_ERR_INVALID, "contract %d: call_level is NaN", c);
+        } else if (s.kind == MCG_S_CLIQUET) {
+            if (n_reset < 2) return fail(MCG_ERR_INVALID, "contract %d: a cliquet needs two RESET dates in the schedule (it has %d)", c, n_reset);
+            if (std::isnan(s.local_floor) || std::isnan(s.local_cap) || std::isnan(s.global_floor) || std::isnan(s.global_cap))
+                return fail(MCG_ERR_INVALID, "contract %d: a cliquet bound is NaN", c);
+            if (s.local_floor > s.local_cap || s.global_floor > s.global_cap)
+                return fail(MCG_ERR_INVALID, "contract %d: a floor lies above its cap", c);
+        } else {
+            return fail(MCG_ERR_INVALID, "contract %d: kind must be in [0, 1] (got %d)", c, s.kind);
+        }
+    }
+    return MCG_OK;
+}
+}  // namespace mcg
+extern "C" {
+
+int mcg_price_scheduled(mcg_ctx* ctx, const mcg_paths* P, double r, double dt, const mcg_obs* obs, int n_obs, const mcg_sched* book,
+                        int n_contracts, double* price, double* std_err, double* sums, int64_t* stop_hist) {
+    int rc = sched_args(ctx, P, r, dt, obs, n_obs, book, n_contracts);
+    if (rc) return rc;
+    if (!price) return fail(MCG_ERR_INVALID, "price is NULL");
+    if (stop_hist && (ctx->allreduce || ctx->rccl_comm || ctx->shm))
+        return fail(MCG_ERR_INVALID, "this ctx holds a collective: take stop_hist per shard and add the shards' counts");
+    if (P->n_paths < 1 && !ctx->allreduce) return fail(MCG_ERR_EMPTY_PATHS, "no paths to price");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_sched_book(ctx, P, r, dt, obs, n_obs, book, n_contracts, price, std_err, sums, stop_hist);
+}
+
+int mcg_sched_path_values(mcg_ctx* ctx, const mcg_paths* P, double r, double dt, const mcg_obs* obs, int n_obs, const mcg_sched* book,
+                          int n_contracts, double* host_values, int32_t* host_stop) {
+    int rc = sched_args(ctx, P, r, dt, obs, n_obs, book, n_contracts);
+    if (rc) return rc;
+    if (!host_values) return fail(MCG_ERR_INVALID, "host_values is NULL");
+    if (P->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "no paths to take values of");
+    MCG_HIP(hipSetDevice(ctx->device));
+    return run_sched_values(ctx, P, r, dt, obs, n_obs, book, n_contracts, host_values, host_stop);
+}
+
 int mcg_lsm_one_launch_enabled(mcg_ctx* ctx, int* enabled) {
     if (!ctx || !enabled) return fail(MCG_ERR_INVALID, "ctx/enabled is NULL");
     *enabled = ctx->coop_launch ? 1 : 0;

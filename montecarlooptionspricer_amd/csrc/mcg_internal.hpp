@@ -345,6 +345,12 @@ int run_barrier_survival(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, d
                          const double* barriers, const int* is_up, int n_levels, double* host_out);
 int run_barriers_bridge(mcg_ctx* ctx, const mcg_paths* P, const mcg_paths* V, double sigma, double r, double T, int first_row,
                         const mcg_exotic* book, int n_contracts, double* price, double* std_err, double* sums);
+// notes on an observation schedule (kernels_sched.hip): the book kernel's sums and stop counts, and the per-path values.
+// mcg_api.hip has checked the arguments (sched_args)
+int run_sched_book(mcg_ctx* ctx, const mcg_paths* P, double r, double dt, const mcg_obs* obs, int n_obs, const mcg_sched* book,
+                   int n_contracts, double* price, double* std_err, double* sums, int64_t* stop_hist);
+int run_sched_values(mcg_ctx* ctx, const mcg_paths* P, double r, double dt, const mcg_obs* obs, int n_obs, const mcg_sched* book,
+                     int n_contracts, double* host_values, int32_t* host_stop);
 
 // MartingaleOptimization's refit (its driver re-accumulates on request): mo_mode 1 = first pass, leave the refinement
 // request in the coefficient block; 2 = the moments are about mo_mu, solve them with lsm_solve_centered.

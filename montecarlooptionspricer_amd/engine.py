@@ -604,6 +604,37 @@ class PathEngine:
                                            pp.ctypes.data_as(dp), ps.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
         return CvResult(price, se, beta, pp, ps, sums if return_sums else None)
 
+    def price_scheduled(self, paths: PathMatrix, r: float, dt: float, schedule, book, return_sums: bool = False,
+                        return_hist: bool = False):
+        """Autocallables and cliquets on an observation schedule (mcg_price_scheduled).  schedule: what schedule(...) takes;
+        book: a sequence of autocall(...) / cliquet(...) tuples or dicts with the mcg_sched fields.  Returns (price[n],
+        std_err[n]) of the paths' present values, then sums[2 n + 1] when return_sums and stop_hist[n][n_obs + 1] (int64: the
+        paths that ended at each observation, the last column at maturity) when return_hist."""
+        paths._alive()
+        obs, arr = schedule_array(schedule), make_sched_book(book)
+        n = len(arr)
+        dp = C.POINTER(C.c_double)
+        price, se, sums = np.empty(n), np.empty(n), np.empty(2 * n + 1)
+        hist = np.zeros((n, len(obs) + 1), dtype=np.int64)
+        check(self._L.mcg_price_scheduled(self._ctx, paths._h, r, float(dt), obs, len(obs), arr, n, price.ctypes.data_as(dp),
+                                          se.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None,
+                                          hist.ctypes.data_as(C.POINTER(C.c_int64)) if return_hist else None))
+        return (price, se) + ((sums,) if return_sums else ()) + ((hist,) if return_hist else ())
+
+    def sched_path_values(self, paths: PathMatrix, r: float, dt: float, schedule, book, return_stop: bool = True):
+        """The present value of every path under every contract of a price_scheduled book (mcg_sched_path_values):
+        values[n][n_paths], and stop[n][n_paths] (int32: the observation at which the note ended, n_obs at maturity) when
+        return_stop."""
+        paths._alive()
+        obs, arr = schedule_array(schedule), make_sched_book(book)
+        n = len(arr)
+        values = np.empty((n, paths.n_paths), dtype=np.float64)
+        stop = np.empty((n, paths.n_paths), dtype=np.int32)
+        check(self._L.mcg_sched_path_values(self._ctx, paths._h, r, float(dt), obs, len(obs), arr, n,
+                                            values.ctypes.data_as(C.POINTER(C.c_double)),
+                                            stop.ctypes.data_as(C.POINTER(C.c_int32)) if return_stop else None))
+        return (values, stop) if return_stop else values
+
     def lsm_one_launch_enabled(self) -> bool:
         """False once the one-launch LSM sweep's hand-shake has timed out on this ctx (mcg_lsm_one_launch_enabled)."""
         v = C.c_int()
@@ -987,6 +1018,81 @@ def make_book(book):
     for i, c in enumerate(book):
         vals = [c.get(k, 0) for k in names] if isinstance(c, dict) else c
         arr[i] = N.Exotic(int(vals[0]), int(bool(vals[1])), float(vals[2]), float(vals[3]), float(vals[4]))
+    return arr
+
+
+def schedule(entries) -> list:
+    """The observation schedule of price_scheduled as a list of (row, flags).  entries: a sequence of (row, flags) with flags
+    an int (_native.OBS_* or-ed) or names joined by "|" or given as a sequence ("coupon|call", ("ki",): _native.OBS_FLAGS).
+    Rows must be non-negative and strictly increasing; what the matrix allows is checked by the library."""
+    out = []
+    for e in entries:
+        row, flags = e
+        if isinstance(flags, str):
+            flags = [f for f in flags.replace(" ", "").split("|") if f]
+        if not isinstance(flags, (int, np.integer)):
+            names = list(flags)
+            unknown = [f for f in names if not isinstance(f, str) or f.lower() not in N.OBS_FLAGS]
+            if unknown:
+                raise McgError(f"unknown observation flag {unknown[0]!r}: one of {sorted(N.OBS_FLAGS)}", 1)
+            flags = 0
+            for f in names:
+                flags |= N.OBS_FLAGS[f.lower()]
+        flags = int(flags)
+        if flags & ~(N.OBS_COUPON | N.OBS_CALL | N.OBS_KI | N.OBS_RESET) or flags < 0:
+            raise McgError(f"observation flags {flags:#x} outside the mask 0xf", 1)
+        if int(row) != row or int(row) < 0:
+            raise McgError(f"observation row must be a non-negative integer (got {row!r})", 1)
+        if out and int(row) <= out[-1][0]:
+            raise McgError(f"observation rows must be strictly increasing ({int(row)} after {out[-1][0]})", 1)
+        out.append((int(row), flags))
+    if not out:
+        raise McgError("a schedule needs at least one observation", 1)
+    return out
+
+
+def schedule_array(entries):
+    """ctypes array of mcg_obs from what schedule(...) takes; an array of _native.Obs passes as it is (the library checks it)."""
+    if isinstance(entries, C.Array) and entries._type_ is N.Obs:
+        return entries
+    obs = schedule(entries)
+    return (N.Obs * len(obs))(*[N.Obs(row, flags) for row, flags in obs])
+
+
+def autocall(call_level: float, coupon: float, coupon_level: float = 0.0, ki_level: float = 0.0, put_strike: float = 1.0,
+             memory: bool = False) -> tuple:
+    """One autocallable of a price_scheduled book, in the order of the mcg_sched fields.  Levels are fractions of the path's
+    own row-0 value; call_level = inf: never called; ki_level = 0: no knock-in."""
+    vals = (float(call_level), float(coupon_level), float(coupon), float(ki_level), float(put_strike))
+    if math.isnan(vals[0]) or not all(math.isfinite(v) for v in vals[1:4]):
+        raise McgError("autocall: coupon, coupon_level and ki_level must be finite, call_level not NaN", 1)
+    if not vals[4] > 0.0:
+        raise McgError(f"autocall: put_strike must be positive (got {put_strike!r})", 1)
+    return (N.S_AUTOCALL, int(bool(memory))) + vals + (0.0, 0.0, 0.0, 0.0)
+
+
+def cliquet(local_floor: float = -math.inf, local_cap: float = math.inf, global_floor: float = -math.inf,
+            global_cap: float = math.inf) -> tuple:
+    """One cliquet of a price_scheduled book, in the order of the mcg_sched fields: the sum of the period returns between the
+    schedule's RESET dates, each clamped to [local_floor, local_cap], the sum to [global_floor, global_cap]."""
+    vals = (float(local_floor), float(local_cap), float(global_floor), float(global_cap))
+    if any(math.isnan(v) for v in vals):
+        raise McgError("cliquet: a bound is NaN", 1)
+    if vals[0] > vals[1] or vals[2] > vals[3]:
+        raise McgError("cliquet: a floor lies above its cap", 1)
+    return (N.S_CLIQUET, 0, 0.0, 0.0, 0.0, 0.0, 1.0) + vals
+
+
+def make_sched_book(book):
+    """ctypes array of mcg_sched from a sequence of autocall(...) / cliquet(...) tuples or dicts with the mcg_sched fields
+    (fields a dict leaves out are 0).  Kinds, values and counts are checked by the library."""
+    names = [k for k, _ in N.Sched._fields_]
+    arr = (N.Sched * len(book))()
+    for i, c in enumerate(book):
+        vals = [c.get(k, 0) for k in names] if isinstance(c, dict) else c
+        if len(vals) != len(names):
+            raise McgError(f"contract {i}: expected the {len(names)} fields of mcg_sched (got {len(vals)})", 1)
+        arr[i] = N.Sched(int(vals[0]), int(bool(vals[1])), *[float(v) for v in vals[2:]])
     return arr
 
 

@@ -78,6 +78,15 @@ int mcg_debug_sincos2_tables(double* coarse, double* fine);
  * narrow kernel (k_gbm_paths), 2 = the wide one (k_gbm_paths_wide), -1 = leave it as it is; *last_route (may be NULL) = what
  * the last GBM launch took (1 or 2; 0 before the first). */
 int mcg_debug_gbm_route(mcg_ctx* ctx, int route, int* last_route);
+/* Test hook: which kernels mcg_price_branching runs on this context -- route 0 = by size (the product's choice), 1 = one launch
+ * over all dates (k_branch_bounds), 2 = a launch per exercise date (k_branch_date), 3 = the same with the indices sorted into
+ * bins (k_branch_date_binned), 4 = the XCD-affine gathers (k_branch_date_xcd), -1 = leave route and slice_shift as they are.
+ * slice_shift: the gathered row is walked in slices of 2^slice_shift paths (0: the default, 18), raised until the route's slice
+ * count holds (8 on routes 1 and 2, 16 on route 3; route 4 has no slices).  A forced route is taken only where it can run: at
+ * least one path, one to twelve branches, an exercise date within the maturity, and fewer than 2^30 - 1 paths for routes 3 and
+ * 4; otherwise the size decides.  *last_route (may be NULL) = what the last mcg_price_branching took (1..4; 0 before the first).
+ * No price depends on the route beyond the order in which a path's branch values are added. */
+int mcg_debug_branch_route(mcg_ctx* ctx, int route, int slice_shift, int* last_route);
 /* Measurement hook: the path-steps the wavefronts of this context's last mcg_lsm_dual_upper ran through -- for every step a
  * wavefront executed, the outer paths it holds, whether the inner path of each was still alive or not.  inner_steps over this
  * is the share of live lane-steps (1 where no inner path stops before the last date). */

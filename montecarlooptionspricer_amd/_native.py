@@ -213,6 +213,7 @@ def load_library():
                                     C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_double)])
     newer("mcg_debug_sincos2_tables", [dp, dp])
     newer("mcg_debug_gbm_route", [vp, C.c_int, C.POINTER(C.c_int)])
+    newer("mcg_debug_branch_route", [vp, C.c_int, C.c_int, C.POINTER(C.c_int)])
     newer("mcg_debug_eval_v", [vp, C.c_int, dp, C.c_int, dp, C.c_int, dp, C.c_int64])
     newer("mcg_debug_bates_constants", [C.c_double] * 4 + [C.POINTER(C.c_uint32), dp])
     newer("mcg_debug_lsm_solve", [vp, C.c_int, C.c_int, dp, C.c_int, dp, dp, C.c_int64])

@@ -222,4 +222,13 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* lds /* NV*NW 
     }
 }
 
+// a workgroup of four waves' {sum v[0], sum v[1]} -> partials[blockIdx.x][2]
+__device__ __forceinline__ void block_sum_store2(double (&v)[2], double* lds /* 8 doubles */, double* partials) {
+    block_sum<2, 4>(v, lds);
+    if (threadIdx.x == 0) {
+        partials[2 * (int64_t)blockIdx.x] = v[0];
+        partials[2 * (int64_t)blockIdx.x + 1] = v[1];
+    }
+}
+
 }  // namespace mcg

@@ -22,6 +22,7 @@
 
 #include <cstring>
 
+#include "branching_device.hpp"
 #include "coalesce.hpp"
 #include "lsm_device.hpp"
 #include "mcg_internal.hpp"
@@ -237,7 +238,8 @@ __global__ __launch_bounds__(256) void k_batch_asym(BatchArgs a) {
 // paths' values from there -- the suffix-maximum matrix never exists in memory (until round 3 it was written to and
 // gathered from global memory: 3.8 ms of the batch's 9 ms at 20 000 rows).  The upper bound is a maximum over the dates
 // and the lower bound the FIRST date with a positive payoff, i.e. the one found last on the way back: the order of the
-// walk does not matter.  Same Philox blocks (counter = date, branch quad) as the single-contract kernel.
+// walk does not matter.  The resampling draws are the single-contract kernels': the contract stated in branching_device.hpp
+// (stream, counter = date * quads + quad, index, which draws exist), with the path id (row << 32) + path.
 __global__ __launch_bounds__(256) void k_batch_branching(BatchArgs a) {
     extern __shared__ double sm[];  // disc[n_cols]
     __shared__ double red[2 * 4];
@@ -255,7 +257,7 @@ __global__ __launch_bounds__(256) void k_batch_branching(BatchArgs a) {
     const bool live = p < a.n_paths;
     const double* col = a.S + row.off + (live ? p : 0);
     const uint64_t id = (row.id << 32) + (uint64_t)p;
-    const PhiloxLane lane_rng = philox_lane_setup(id, 2u, row.k1);
+    const PhiloxLane lane_rng = philox_lane_setup(id, STREAM_BRANCH, row.k1);
     const int quads = (a.num_branches + 3) >> 2;
     const double inv_b = a.num_branches > 0 ? 1.0 / (double)a.num_branches : 0.0;
     const int ex_last = row.n_steps - 1;
@@ -285,12 +287,12 @@ __global__ __launch_bounds__(256) void k_batch_branching(BatchArgs a) {
             double better = now;
             if (e < ex_last && a.num_branches > 0) {
                 double sum = 0.0;
-                for (int q = 0; q < quads; ++q) {
+                for (int q = 0; q < quads; ++q) {  // (branch_draw's run-time form written out: through it the code object moves)
                     const Philox4 w = philox4x32_10_lane(lane_rng, (uint32_t)(e * quads + q), row.k0, row.k1);
                     const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        if (4 * q + s < a.num_branches) sum += mine[__umulhi(ws[s], (uint32_t)a.n_paths)];
+                        if (4 * q + s < a.num_branches) sum += mine[branch_index(ws[s], (uint32_t)a.n_paths)];
                 }
                 const double cont = sum * inv_b;
                 if (cont > better) better = cont;
@@ -499,14 +501,9 @@ static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, 
     std::vector<double> four((size_t)n * 5);   // (host memory first: a bad_alloc below this line would leave a pool buffer out)
     void* d_map = nullptr;
     const size_t map_bytes = wg_map.size() * sizeof(uint32_t);
-    int rc_map = pool_alloc(ctx, map_bytes, &d_map);
+    PoolLease lease(ctx);   // the map goes back to the pool on every way out
+    int rc_map = lease.alloc(map_bytes, &d_map);
     if (rc_map) return rc_map;
-    struct PoolGuard {   // the map goes back to the pool on every way out
-        mcg_ctx* c;
-        void* p;
-        size_t b;
-        ~PoolGuard() { pool_release(c, p, b); }
-    } map_guard{ctx, d_map, map_bytes};
     if (hipMemcpyAsync(d_map, wg_map.data(), map_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
         return fail(MCG_ERR_HIP, "batch upload failed (workgroup map)");
     a.wg_map = (const uint32_t*)d_map;
@@ -695,22 +692,10 @@ int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_path
     int rc = MCG_OK;
     if (!plan.empty()) {
         void *S = nullptr, *small = nullptr;  // ONE pair of buffers for all chunks
-        rc = pool_alloc(ctx, max_S, &S);
+        PoolLease lease(ctx);   // both buffers go back to the pool on every way out (a bad_alloc in a chunk included)
+        rc = lease.alloc(max_S, &S);
+        if (!rc) rc = lease.alloc(max_small * sizeof(double), &small);
         if (rc) return rc;
-        rc = pool_alloc(ctx, max_small * sizeof(double), &small);
-        if (rc) {
-            pool_release(ctx, S, max_S);
-            return rc;
-        }
-        struct Release {   // both buffers go back to the pool on every way out (a bad_alloc in a chunk included)
-            mcg_ctx* c;
-            void *S, *small;
-            size_t bS, bsmall;
-            ~Release() {
-                pool_release(c, S, bS);
-                pool_release(c, small, bsmall);
-            }
-        } release{ctx, S, small, max_S, max_small * sizeof(double)};
         int64_t peak = (int64_t)(max_S + max_small * sizeof(double)), seen = g_stats.batch_peak_workspace_bytes.load(std::memory_order_relaxed);
         while (peak > seen && !g_stats.batch_peak_workspace_bytes.compare_exchange_weak(seen, peak, std::memory_order_relaxed)) {
         }

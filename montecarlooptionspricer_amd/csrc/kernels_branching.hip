@@ -13,12 +13,10 @@
 // t_idx+1 of F (L2/MALL-resident rows) with Philox-drawn path indices (stream 2, counter = (path, date, branch/4)).
 // The reference draws from an unseeded shared mt19937, so parity of the upper bound is statistical; the lower
 // bound is deterministic.  Sharded use resamples within the local shard (the matrix is never exchanged).
-#include "devmath.hpp"
+#include "branching_device.hpp"
 #include "paths_host.hpp"
 
 namespace mcg {
-
-enum : uint32_t { STREAM_BRANCH = 2u };
 
 // F[j][p] for j = n_cols-1 .. 0.  disc[j] = e^{-r j dt}; columns j >= n_dates (t_j > maturity) contribute 0.
 __global__ __launch_bounds__(256) void k_branch_suffix(const double* S, double* F, int64_t ld, int64_t n, int n_cols,
@@ -50,6 +48,46 @@ struct BranchArgs {
     int is_call;
 };
 
+// ---- the pieces every bounds kernel is made of ---------------------------------------------------------------------------------
+// Does the exercise date on column t_idx have a continuation (:104-121)?  Not the list's LAST entry (exerciseTimes.back(), :104 --
+// not its largest), and not an index on the last column: a trailing exercise index at or beyond the last column (the reference
+// tolerates one behind its `t > maturity` break, :97-99) leaves its `k` loop (:110) empty for t_idx = n_cols - 1, continuation 0.
+__host__ __device__ inline bool date_branches(int t_idx, int ex_last, int n_cols) { return t_idx < ex_last && t_idx + 1 < n_cols; }
+
+// the row of F that date t_idx gathers from (where it has no continuation: its own row, never read)
+__device__ __forceinline__ const double* branch_row_f(const BranchArgs& a, int t_idx, bool branch) {
+    return a.F + (int64_t)(branch ? t_idx + 1 : t_idx) * a.ld;
+}
+
+__device__ __forceinline__ PhiloxLane branch_rng(const BranchArgs& a, int64_t p) {
+    return philox_lane_setup(a.path_begin + (uint64_t)p, STREAM_BRANCH, a.k1);
+}
+
+// THE BOUNDS RULE of one path at one exercise date: `now` its discounted payoff there, `cont` its continuation where the date
+// branches.  :62-65 -- the first positive discounted payoff is the lower bound (lower > 0 <=> it has been seen: lower is only ever
+// set to a now > 0); :123-127 -- the upper bound is the running maximum of max(now, cont).
+__device__ __forceinline__ void branch_update(double& lower, double& upper, double now, double cont, bool branch) {
+    if (!(lower > 0.0) && now > 0.0) lower = now;
+    double better = now;
+    if (branch && cont > better) better = cont;
+    if (better > upper) upper = better;
+}
+
+// A path's bounds between the launches of a per-date route: `state` = {lower, upper} per path, 32 B per path and date, read and
+// written past the caches.
+typedef double br_v2d __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ br_v2d branch_state_load(const double2* state, int first_date, int64_t p) {
+    return first_date ? br_v2d{0.0, 0.0} : __builtin_nontemporal_load(reinterpret_cast<const br_v2d*>(state) + p);
+}
+__device__ __forceinline__ double branch_now(const BranchArgs& a, const double* rowS, double dsc, int64_t p) {  // rowS, dsc: of the date's column
+    return dsc * payoff_of(a.is_call != 0, __builtin_nontemporal_load(rowS + p), a.K);
+}
+__device__ __forceinline__ void branch_state_store(double2* state, int64_t p, bool live, br_v2d st, double now, double cont, bool branch) {
+    double lower = st.x, upper = st.y;
+    branch_update(lower, upper, now, cont, branch);
+    if (live) __builtin_nontemporal_store(br_v2d{lower, upper}, reinterpret_cast<br_v2d*>(state) + p);
+}
+
 // The dates are the OUTER loop: every thread carries the bounds of its BR_PPT paths in registers and all resident
 // threads work on one exercise date at about the same time, so the device's gathers of that moment fall into ONE row of
 // F instead of being spread over the whole matrix (round 2: paths outermost, each thread walking its own dates: 7.7 ms
@@ -74,21 +112,23 @@ constexpr int BR_WGS_PER_CU = 4;    // resident workgroups per CU the register b
 
 struct BranchLane {  // one thread's BR_PPT paths
     int64_t p[BR_PPT];
-    bool live[BR_PPT], have_lower[BR_PPT];
+    bool live[BR_PPT];
     double lower[BR_PPT], upper[BR_PPT];
     PhiloxLane rng[BR_PPT];  // block numbers are wave-uniform
 };
 
+// The paths of a lane: path q of thread t of workgroup w is p0 + (w 256 + t) + q (gridDim.x 256); a lane beyond the shard is
+// clamped to the last path (reads stay in range; the result is dropped).  The two per-date kernels have the same three lines
+// inside their own path loops.
 __device__ __forceinline__ void branch_lane_setup(BranchLane& t, const BranchArgs& a, int64_t p0) {
     const int64_t stride = (int64_t)gridDim.x * 256;
 #pragma unroll
     for (int q = 0; q < BR_PPT; ++q) {
         t.p[q] = p0 + (int64_t)blockIdx.x * 256 + threadIdx.x + q * stride;
         t.live[q] = t.p[q] < a.n;
-        if (!t.live[q]) t.p[q] = a.n - 1;  // (reads stay in range; the result is dropped)
-        t.have_lower[q] = false;
+        if (!t.live[q]) t.p[q] = a.n - 1;
         t.lower[q] = t.upper[q] = 0.0;
-        t.rng[q] = philox_lane_setup(a.path_begin + (uint64_t)t.p[q], STREAM_BRANCH, a.k1);
+        t.rng[q] = branch_rng(a, t.p[q]);
     }
 }
 
@@ -101,11 +141,14 @@ __device__ __forceinline__ void branch_lane_finish(const BranchLane& t, double* 
             v[1] += t.upper[q];
         }
     }
-    block_sum<2, 4>(v, red);
-    if (threadIdx.x == 0) {
-        partials[2 * (int64_t)blockIdx.x] = v[0];
-        partials[2 * (int64_t)blockIdx.x + 1] = v[1];
-    }
+    block_sum_store2(v, red, partials);
+}
+
+// an empty shard still takes part in the collective that follows: its workgroups' partials are zeros
+__device__ __forceinline__ bool branch_empty_shard(const BranchArgs& a, double* partials) {
+    if (a.n > 0) return false;
+    if (threadIdx.x == 0) partials[2 * (int64_t)blockIdx.x] = partials[2 * (int64_t)blockIdx.x + 1] = 0.0;
+    return true;
 }
 
 // QUADS = Philox blocks per path and date = ceil(num_branches / 4) <= 3 (the driver's 10 branches: 3); more branches than
@@ -114,46 +157,30 @@ template <int QUADS>
 __global__ __launch_bounds__(256, BR_WGS_PER_CU) void k_branch_bounds(BranchArgs a, int64_t p0, double* partials, int slice_shift, int n_slices) {
     __shared__ double red[2 * 4];
     const bool call = a.is_call != 0;
-    const uint32_t n32 = (uint32_t)a.n;
     const double inv_b = a.num_branches > 0 ? 1.0 / (double)a.num_branches : 0.0;
-    if (a.n <= 0) {  // an empty shard still takes part in the collective that follows
-        if (threadIdx.x == 0) partials[2 * (int64_t)blockIdx.x] = partials[2 * (int64_t)blockIdx.x + 1] = 0.0;
-        return;
-    }
+    if (branch_empty_shard(a, partials)) return;
     BranchLane t;
     branch_lane_setup(t, a, p0);
     for (int e = 0; e < a.n_ex; ++e) {
         const int t_idx = a.ex[e];
         const double* rowS = a.S + (int64_t)t_idx * a.ld;
         const double dsc = a.disc[t_idx];
-        // :104-121.  A trailing exercise index at or beyond the last column (the reference tolerates one behind its
-        // `t > maturity` break, :97-99) leaves its `k` loop (:110) empty for t_idx = n_cols-1: continuation 0.
-        const bool branch = t_idx < a.ex_last && t_idx + 1 < a.n_cols && a.num_branches > 0;
-        const double* rowF = a.F + (int64_t)(branch ? t_idx + 1 : t_idx) * a.ld;
-        double now[BR_PPT];
+        const bool branch = date_branches(t_idx, a.ex_last, a.n_cols) && a.num_branches > 0;
+        const double* rowF = branch_row_f(a, t_idx, branch);
+        double now[BR_PPT], sum[BR_PPT];
 #pragma unroll
         for (int q = 0; q < BR_PPT; ++q) {
             now[q] = dsc * payoff_of(call, rowS[t.p[q]], a.K);
-            if (!t.have_lower[q] && now[q] > 0.0) {  // :62-65, first positive discounted payoff
-                t.lower[q] = now[q];
-                t.have_lower[q] = true;
-            }
+            sum[q] = 0.0;
         }
-        double sum[BR_PPT];
-#pragma unroll
-        for (int q = 0; q < BR_PPT; ++q) sum[q] = 0.0;
         if (branch) {  // (wave-uniform)
-            uint32_t idx[BR_PPT][4 * QUADS];  // uniform on [0, n); a branch beyond num_branches gets an index in no slice
+            uint32_t idx[BR_PPT][4 * QUADS];  // uniform on [0, n); a draw beyond num_branches gets an index in no slice
 #pragma unroll
             for (int q = 0; q < BR_PPT; ++q) {
-#pragma unroll
-                for (int k = 0; k < QUADS; ++k) {
-                    const Philox4 w = philox4x32_10_lane(t.rng[q], (uint32_t)(e * QUADS + k), a.k0, a.k1);
-                    const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) idx[q][4 * k + s] = 4 * k + s < a.num_branches ? __umulhi(ws[s], n32) : 0xFFFFFFFFu;
-                }
+                branch_draw<QUADS>(t.rng[q], e, a.k0, a.k1,
+                                   [&](int b, uint32_t word) { idx[q][b] = b < a.num_branches ? branch_index(word, (uint32_t)a.n) : 0xFFFFFFFFu; });
             }
+            // pass sl gathers only the indices that fall into slice sl; the sum over a path's branches is formed in SLICE order
             for (int sl = 0; sl < n_slices; ++sl) {
                 const uint32_t first = (uint32_t)sl << slice_shift;  // (< n: the slices cover [0, n))
 #pragma unroll
@@ -168,12 +195,7 @@ __global__ __launch_bounds__(256, BR_WGS_PER_CU) void k_branch_bounds(BranchArgs
             }
         }
 #pragma unroll
-        for (int q = 0; q < BR_PPT; ++q) {
-            double better = now[q];
-            const double cont = sum[q] * inv_b;
-            if (branch && cont > better) better = cont;
-            if (better > t.upper[q]) t.upper[q] = better;
-        }
+        for (int q = 0; q < BR_PPT; ++q) branch_update(t.lower[q], t.upper[q], now[q], sum[q] * inv_b, branch);
     }
     branch_lane_finish(t, red, partials);
 }
@@ -185,38 +207,40 @@ __global__ __launch_bounds__(256, BR_WGS_PER_CU) void k_branch_bounds(BranchArgs
 template <int QUADS>
 __global__ __launch_bounds__(256, BR_WGS_PER_CU) void k_branch_date(BranchArgs a, int64_t p0, int e, double2* state, int first_date,
                                                                    int slice_shift, int n_slices) {
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    const bool call = a.is_call != 0;
+    // The lane's paths, the draws (branching_device.hpp's contract), k_branch_bounds' slice walk and the bounds rule (branch_update, on
+    // the pair in place) are WRITTEN OUT here: through branch_draw, and again with only branch_state_load / branch_state_store and a
+    // shared slice walk, this kernel measured 0.4-0.6 % slower at 1M x 50, beyond the parent's own spread.
+    // As it stands its three code objects are the parent commit's, instruction for instruction.
     const uint32_t n32 = (uint32_t)a.n;
     const double inv_b = 1.0 / (double)a.num_branches;
     const int t_idx = a.ex[e];
     const double* rowS = a.S + (int64_t)t_idx * a.ld;
     // :104-121.  No continuation at the list's last date nor at an index on the last column (k_branch_bounds): n_slices = 0
     const bool branch = n_slices > 0;
-    const double* rowF = a.F + (int64_t)(branch ? t_idx + 1 : t_idx) * a.ld;
+    const double* rowF = branch_row_f(a, t_idx, branch);
     const double dsc = a.disc[t_idx];
     const int64_t stride = (int64_t)gridDim.x * 256;
     int64_t p[BR_PPT];
     bool live[BR_PPT];
     double now[BR_PPT], sum[BR_PPT];
-    v2d st[BR_PPT];
+    br_v2d st[BR_PPT];
     uint32_t idx[BR_PPT][4 * QUADS];
 #pragma unroll
     for (int q = 0; q < BR_PPT; ++q) {
         p[q] = p0 + (int64_t)blockIdx.x * 256 + threadIdx.x + q * stride;
         live[q] = p[q] < a.n;
         if (!live[q]) p[q] = a.n - 1;
-        st[q] = first_date ? v2d{0.0, 0.0} : __builtin_nontemporal_load(reinterpret_cast<const v2d*>(state) + p[q]);
-        now[q] = dsc * payoff_of(call, __builtin_nontemporal_load(rowS + p[q]), a.K);
+        st[q] = first_date ? br_v2d{0.0, 0.0} : __builtin_nontemporal_load(reinterpret_cast<const br_v2d*>(state) + p[q]);
+        now[q] = branch_now(a, rowS, dsc, p[q]);
         sum[q] = 0.0;
         if (branch) {  // (wave-uniform)
-            const PhiloxLane rng = philox_lane_setup(a.path_begin + (uint64_t)p[q], STREAM_BRANCH, a.k1);
+            const PhiloxLane rng = branch_rng(a, p[q]);
 #pragma unroll
             for (int k = 0; k < QUADS; ++k) {
                 const Philox4 w = philox4x32_10_lane(rng, (uint32_t)(e * QUADS + k), a.k0, a.k1);
                 const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
 #pragma unroll
-                for (int s = 0; s < 4; ++s) idx[q][4 * k + s] = 4 * k + s < a.num_branches ? __umulhi(ws[s], n32) : 0xFFFFFFFFu;
+                for (int s = 0; s < 4; ++s) idx[q][4 * k + s] = 4 * k + s < a.num_branches ? branch_index(ws[s], n32) : 0xFFFFFFFFu;
             }
         }
     }
@@ -239,7 +263,7 @@ __global__ __launch_bounds__(256, BR_WGS_PER_CU) void k_branch_date(BranchArgs a
         const double cont = sum[q] * inv_b;
         if (branch && cont > better) better = cont;
         if (better > st[q].y) st[q].y = better;
-        if (live[q]) __builtin_nontemporal_store(st[q], reinterpret_cast<v2d*>(state) + p[q]);
+        if (live[q]) __builtin_nontemporal_store(st[q], reinterpret_cast<br_v2d*>(state) + p[q]);
     }
 }
 
@@ -265,25 +289,25 @@ inline size_t brb_lds_bytes(int num_branches, int ppt) { return (size_t)256 * ((
 template <int QUADS, int PPT>
 __global__ __launch_bounds__(256, 3) void k_branch_date_binned(BranchArgs a, int64_t p0, int e, double2* state, int first_date,
                                                                int slice_shift, int n_slices) {
-    typedef double v2d __attribute__((ext_vector_type(2)));
     static_assert(12 * PPT <= 63 && PPT <= 4, "bin positions are six-bit fields; the owner is two bits");
     extern __shared__ double brb_lds[];
     double (*sums)[256] = reinterpret_cast<double (*)[256]>(brb_lds);                // [owner][thread]
     uint32_t (*bins)[256] = reinterpret_cast<uint32_t (*)[256]>(brb_lds + 4 * 256);  // [pos][thread], pos < num_branches PPT
-    const bool call = a.is_call != 0;
+    // The lane's paths and branch_draw WRITTEN OUT, a path at a time: on a shared per-date frame and on branch_draw this kernel came out
+    // 0.7-0.8 % slower (1.3M x 50: 4.30 -> 4.34 ms); as it stands only its last block (the bounds rule and the store) differs from the parent commit's instructions.
     const uint32_t n32 = (uint32_t)a.n;
     const double inv_b = 1.0 / (double)a.num_branches;
     const int t_idx = a.ex[e];
     const double* rowS = a.S + (int64_t)t_idx * a.ld;
     const bool branch = n_slices > 0;  // (no continuation at the list's last date nor at an index on the last column)
-    const double* rowF = a.F + (int64_t)(branch ? t_idx + 1 : t_idx) * a.ld;
+    const double* rowF = branch_row_f(a, t_idx, branch);
     const double dsc = a.disc[t_idx];
     const int64_t stride = (int64_t)gridDim.x * 256;
     const unsigned tid = threadIdx.x;
     int64_t p[PPT];
     bool live[PPT];
     double now[PPT];
-    v2d st[PPT];
+    br_v2d st[PPT];
     // six-bit fields: slices 0..9 in lo, 10..15 in hi
     uint64_t f_lo = 0, f_hi = 0;
     auto field_shift = [](uint32_t sl) { return 6u * (sl >= 10u ? sl - 10u : sl); };
@@ -304,17 +328,17 @@ __global__ __launch_bounds__(256, 3) void k_branch_date_binned(BranchArgs a, int
         p[q] = p0 + (int64_t)blockIdx.x * 256 + threadIdx.x + q * stride;
         live[q] = p[q] < a.n;
         if (!live[q]) p[q] = a.n - 1;
-        st[q] = first_date ? v2d{0.0, 0.0} : __builtin_nontemporal_load(reinterpret_cast<const v2d*>(state) + p[q]);
-        now[q] = dsc * payoff_of(call, __builtin_nontemporal_load(rowS + p[q]), a.K);
-        if (branch) {  // (wave-uniform)
-            const PhiloxLane rng = philox_lane_setup(a.path_begin + (uint64_t)p[q], STREAM_BRANCH, a.k1);
+        st[q] = branch_state_load(state, first_date, p[q]);
+        now[q] = branch_now(a, rowS, dsc, p[q]);
+        if (branch) {  // (wave-uniform) the draws of branching_device.hpp's contract
+            const PhiloxLane rng = branch_rng(a, p[q]);
 #pragma unroll
             for (int k = 0; k < QUADS; ++k) {
                 const Philox4 w = philox4x32_10_lane(rng, (uint32_t)(e * QUADS + k), a.k0, a.k1);
                 const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    idx[q][4 * k + s] = __umulhi(ws[s], n32);
+                    idx[q][4 * k + s] = branch_index(ws[s], n32);
                     if (4 * k + s < a.num_branches) (void)bump(idx[q][4 * k + s] >> slice_shift);  // count
                 }
             }
@@ -369,12 +393,7 @@ __global__ __launch_bounds__(256, 3) void k_branch_date_binned(BranchArgs a, int
     }
 #pragma unroll
     for (int q = 0; q < PPT; ++q) {
-        if (!(st[q].x > 0.0) && now[q] > 0.0) st[q].x = now[q];  // :62-65, first positive discounted payoff
-        double better = now[q];
-        const double cont = sums[q][tid] * inv_b;
-        if (branch && cont > better) better = cont;
-        if (better > st[q].y) st[q].y = better;
-        if (live[q]) __builtin_nontemporal_store(st[q], reinterpret_cast<v2d*>(state) + p[q]);
+        branch_state_store(state, p[q], live[q], st[q], now[q], sums[q][tid] * inv_b, branch);
     }
 }
 
@@ -394,25 +413,18 @@ __global__ __launch_bounds__(256, 3) void k_branch_date_binned(BranchArgs a, int
 // 17.3 / 16.6 / 15.7 ms, and unbalanced whenever n is not a multiple of eight chunks (gpurun_out/r6n_branch_xcd.log).
 constexpr int BRX_PPT = 2;
 
-// bounds of path p after exercise date e: its eight cells added in XCD order (the same bits every run), then :62-65 and :123-127
+// bounds of path p after exercise date e: its eight cells added in XCD order (the same bits every run), then the bounds rule
 __device__ __forceinline__ void brx_finish_path(const BranchArgs& a, int e, const double* cells, int64_t ldc, double2* state, int first_date,
                                                 int branch, int64_t p) {
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    const bool call = a.is_call != 0;
     const int t_idx = a.ex[e];
-    v2d st = first_date ? v2d{0.0, 0.0} : __builtin_nontemporal_load(reinterpret_cast<const v2d*>(state) + p);
-    const double now = a.disc[t_idx] * payoff_of(call, __builtin_nontemporal_load(a.S + (int64_t)t_idx * a.ld + p), a.K);
-    double better = now;
+    const br_v2d st = branch_state_load(state, first_date, p);
+    const double now = branch_now(a, a.S + (int64_t)t_idx * a.ld, a.disc[t_idx], p);
+    double c = 0.0;
     if (branch) {
-        double c = 0.0;
 #pragma unroll
         for (int x = 0; x < 8; ++x) c += __builtin_nontemporal_load(cells + (int64_t)x * ldc + p);
-        const double cont = c * (1.0 / (double)a.num_branches);
-        if (cont > better) better = cont;
     }
-    if (!(st.x > 0.0) && now > 0.0) st.x = now;
-    if (better > st.y) st.y = better;
-    __builtin_nontemporal_store(st, reinterpret_cast<v2d*>(state) + p);
+    branch_state_store(state, p, true, st, now, c * (1.0 / (double)a.num_branches), branch != 0);
 }
 
 // A tile = 512 paths; workgroup w works on tile w >> 3 for XCD w & 7.  Which XCD a draw belongs to is read off the TOP bits of its
@@ -421,14 +433,15 @@ __device__ __forceinline__ void brx_finish_path(const BranchArgs& a, int e, cons
 // add-with-carry into the thread's mask; the words go to LDS four at a time and only the few that are kept are turned into indices.
 template <int QUADS>
 __global__ __launch_bounds__(256) void k_branch_date_xcd(BranchArgs a, int e, double* cells, int64_t ldc) {
-    __shared__ uint4 buf[QUADS * BRX_PPT][256];  // [Philox block of the thread][thread]: a thread only ever reads its own column
+    // [Philox block of the thread][thread][word]: a thread only ever reads its own column (hipcc merges the four stores of a block
+    // into one ds_write_b128, as many in the assembly as when a uint4 was stored: DESIGN.md section 8 f3)
+    __shared__ __attribute__((aligned(16))) uint32_t buf[QUADS * BRX_PPT][256][4];
     constexpr int DRAWS = 4 * QUADS * BRX_PPT;
     const unsigned tid = threadIdx.x;
     const uint32_t xcd = blockIdx.x & 7u;
     const int64_t tile = (int64_t)(blockIdx.x >> 3);
     const uint32_t n32 = (uint32_t)a.n;
-    const int t_idx = a.ex[e];
-    const double* rowF = a.F + (int64_t)(t_idx + 1) * a.ld;
+    const double* rowF = branch_row_f(a, a.ex[e], true);
     // draws that exist: branch b < num_branches of either path; draw i (in drawing order) sits at bit DRAWS - 1 - i of the mask
     uint32_t exists = 0;
 #pragma unroll
@@ -439,24 +452,19 @@ __global__ __launch_bounds__(256) void k_branch_date_xcd(BranchArgs a, int e, do
     for (int q = 0; q < BRX_PPT; ++q) {
         p[q] = tile * (256 * BRX_PPT) + tid + q * 256;
         const bool live = p[q] < a.n;
-        const PhiloxLane rng = philox_lane_setup(a.path_begin + (uint64_t)(live ? p[q] : a.n - 1), STREAM_BRANCH, a.k1);
-#pragma unroll
-        for (int k = 0; k < QUADS; ++k) {
-            const Philox4 w = philox4x32_10_lane(rng, (uint32_t)(e * QUADS + k), a.k0, a.k1);
-            buf[q * QUADS + k][tid] = make_uint4(w.w0, w.w1, w.w2, w.w3);
-            const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
-#pragma unroll
-            for (int s = 0; s < 4; ++s) m = m + m + ((((ws[s] >> 28) & 7u) == xcd && live) ? 1u : 0u);
-        }
+        const PhiloxLane rng = branch_rng(a, live ? p[q] : a.n - 1);
+        branch_draw<QUADS>(rng, e, a.k0, a.k1, [&](int b, uint32_t word) {
+            buf[q * QUADS + (b >> 2)][tid][b & 3] = word;
+            m = m + m + ((((word >> 28) & 7u) == xcd && live) ? 1u : 0u);
+        });
     }
     m &= exists;
     double sum[BRX_PPT];
 #pragma unroll
     for (int q = 0; q < BRX_PPT; ++q) sum[q] = 0.0;
-    const uint32_t* words = reinterpret_cast<const uint32_t*>(&buf[0][0]);
     auto word_of = [&](uint32_t bit) {  // the Philox word of the draw at mask bit `bit`
         const uint32_t i = (uint32_t)(DRAWS - 1) - bit;
-        return words[((i >> 2) * 256u + tid) * 4u + (i & 3u)];
+        return buf[i >> 2][tid][i & 3u];
     };
     while (__builtin_amdgcn_ballot_w64(m != 0u) != 0ull) {  // two of the thread's own gathers per trip
         const bool h0 = m != 0u;
@@ -466,8 +474,8 @@ __global__ __launch_bounds__(256) void k_branch_date_xcd(BranchArgs a, int e, do
         const uint32_t b1 = h1 ? (uint32_t)__builtin_ctz(m) : 0u;
         m &= m - (h1 ? 1u : 0u);
         const uint32_t w0 = word_of(b0), w1 = word_of(b1);
-        const double v0 = h0 ? rowF[__umulhi(w0, n32)] : 0.0;
-        const double v1 = h1 ? rowF[__umulhi(w1, n32)] : 0.0;
+        const double v0 = h0 ? rowF[branch_index(w0, n32)] : 0.0;
+        const double v1 = h1 ? rowF[branch_index(w1, n32)] : 0.0;
         // (bits >= 4 QUADS belong to the thread's FIRST path: it was drawn first)
         if (b0 >= 4u * QUADS) sum[0] += v0;
         else sum[BRX_PPT - 1] += v0;
@@ -494,11 +502,7 @@ __global__ __launch_bounds__(256) void k_branch_finish(const double2* state, int
         v[0] += st.x;
         v[1] += st.y;
     }
-    block_sum<2, 4>(v, red);
-    if (threadIdx.x == 0) {
-        partials[2 * (int64_t)blockIdx.x] = v[0];
-        partials[2 * (int64_t)blockIdx.x + 1] = v[1];
-    }
+    block_sum_store2(v, red, partials);
 }
 
 // any number of branches: the indices are used as they are drawn (no slices)
@@ -508,50 +512,106 @@ __global__ __launch_bounds__(256) void k_branch_bounds_any(BranchArgs a, int64_t
     const uint32_t n32 = (uint32_t)a.n;
     const int quads = (a.num_branches + 3) >> 2;
     const double inv_b = a.num_branches > 0 ? 1.0 / (double)a.num_branches : 0.0;
-    if (a.n <= 0) {
-        if (threadIdx.x == 0) partials[2 * (int64_t)blockIdx.x] = partials[2 * (int64_t)blockIdx.x + 1] = 0.0;
-        return;
-    }
+    if (branch_empty_shard(a, partials)) return;
     BranchLane t;
     branch_lane_setup(t, a, p0);
     for (int e = 0; e < a.n_ex; ++e) {
         const int t_idx = a.ex[e];
         const double* rowS = a.S + (int64_t)t_idx * a.ld;
         const double dsc = a.disc[t_idx];
-        const bool branch = t_idx < a.ex_last && t_idx + 1 < a.n_cols && a.num_branches > 0;
-        const double* rowF = a.F + (int64_t)(branch ? t_idx + 1 : t_idx) * a.ld;
+        const bool branch = date_branches(t_idx, a.ex_last, a.n_cols) && a.num_branches > 0;
+        const double* rowF = branch_row_f(a, t_idx, branch);
 #pragma unroll
         for (int q = 0; q < BR_PPT; ++q) {
             const double now = dsc * payoff_of(call, rowS[t.p[q]], a.K);
-            if (!t.have_lower[q] && now > 0.0) {
-                t.lower[q] = now;
-                t.have_lower[q] = true;
-            }
-            double better = now;
+            double sum = 0.0;
             if (branch) {
-                double sum = 0.0;
-                for (int k = 0; k < quads; ++k) {
-                    const Philox4 w = philox4x32_10_lane(t.rng[q], (uint32_t)(e * quads + k), a.k0, a.k1);
-                    const uint32_t ws[4] = {w.w0, w.w1, w.w2, w.w3};
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        if (4 * k + s < a.num_branches) sum += rowF[__umulhi(ws[s], n32)];  // uniform on [0, n)
-                    }
-                }
-                const double cont = sum * inv_b;
-                if (cont > better) better = cont;
+                branch_draw(t.rng[q], e, quads, a.k0, a.k1, [&](int b, uint32_t word) {
+                    if (b < a.num_branches) sum += rowF[branch_index(word, n32)];
+                });
             }
-            if (better > t.upper[q]) t.upper[q] = better;
+            branch_update(t.lower[q], t.upper[q], now, sum * inv_b, branch);
         }
     }
     branch_lane_finish(t, red, partials);
+}
+
+// ---- the host side ---------------------------------------------------------------------------------------------------------
+// Which kernels price a shard, and on what grid: computed once, from the shard's size and the branch count.
+enum : int { BR_ROUTE_ONE_LAUNCH = 1, BR_ROUTE_PER_DATE = 2, BR_ROUTE_BINNED = 3, BR_ROUTE_XCD = 4 };  // (mcg_debug_branch_route's numbers)
+struct BranchPlan {
+    int route;
+    int slice_shift, n_slices;       // the slices of a gathered row on that route (XCD: none, its chunks come off the Philox word)
+    int quads, ppt;                  // Philox blocks per path and date; paths per thread
+    int grid;                        // workgroups of a full launch
+    int64_t per_launch, n_launches;  // paths a full launch covers; launches that cover the shard
+    size_t lds_bytes;                // dynamic LDS per workgroup (the binned kernel's bins)
+};
+constexpr int64_t BRX_MIN_PATHS = (int64_t)7 << 18;  // 1.835M paths = rows of 14 MB: below, the binned kernel is at least as fast
+
+static BranchPlan plan_branching(const mcg_ctx* ctx, int64_t n, int num_branches, bool have_dates) {
+    BranchPlan pl{};
+    pl.quads = (num_branches + 3) / 4;
+    // slices of the gathered row: 2 MB each (mcg_debug_branch_route: another size to start from), at most `cap` of them -- then of
+    // n / cap, rounded up to a power of two
+    const int64_t last = (n > 0 ? n : 1) - 1;
+    auto slices = [&](int cap) {
+        pl.slice_shift = ctx->branch_shift ? ctx->branch_shift : BR_SLICE_SHIFT;
+        while ((last >> pl.slice_shift) + 1 > cap) ++pl.slice_shift;
+        pl.n_slices = (int)((last >> pl.slice_shift) + 1);
+    };
+    // What the per-date kernels need: indices kept in registers (up to twelve branches) and a date to launch for; the binned and
+    // XCD kernels keep the owner of an index in its top two bits: rows of up to 2^30 - 2 paths.
+    const bool dates_ok = pl.quads >= 1 && pl.quads <= 3 && have_dates;
+    const bool bins_ok = dates_ok && n < ((int64_t)1 << 30) - 1;
+    // Rows of more than four slices (more than a million paths): per-date launches of the BINNED kernel (k_branch_date_binned:
+    // every thread walks its indices sorted by slice), sixteen slices of >= 2 MB; from BRX_MIN_PATHS on the XCD-affine gathers.
+    // Rows of two to four slices: one launch per exercise date, bounds in `state`.  A/B on one board, 1M x 50: 5.55 ms
+    // (one launch, no slices) -> 5.25 (one launch, slices: 42 % L2 hits) -> 2.83 (per-date launches).  A pass costs
+    // ~40 cycles per wave-load however few lanes take part, so rows of many slices lose what the hits gain (4M x 50,
+    // 16 slices: 44.7 ms per date-launches against 29.6 in one launch with 8 slices and 35.3 without): where the binned kernel
+    // cannot run those keep the one-launch kernel.
+    slices(16);
+    const bool many = bins_ok && pl.n_slices > BR_DATE_MAX_SLICES;
+    slices(BR_MAX_SLICES);
+    pl.route = many ? (n >= BRX_MIN_PATHS ? BR_ROUTE_XCD : BR_ROUTE_BINNED)
+                    : dates_ok && pl.n_slices > 1 && pl.n_slices <= BR_DATE_MAX_SLICES ? BR_ROUTE_PER_DATE : BR_ROUTE_ONE_LAUNCH;
+    // a forced route, where it can run at all (the per-date kernels clamp dead lanes to path n - 1: never an empty shard)
+    const int forced = ctx->branch_route;
+    if (forced >= BR_ROUTE_ONE_LAUNCH && n >= 1 && dates_ok && (forced <= BR_ROUTE_PER_DATE || bins_ok)) pl.route = forced;
+
+    int wgs_per_cu = BR_WGS_PER_CU;  // launches of one resident wave of workgroups: all of them walk a row's slices together
+    pl.ppt = BR_PPT;
+    if (pl.route == BR_ROUTE_BINNED) {
+        slices(16);
+        // Paths per thread: a generation is three resident workgroups per CU of 256 x PPT paths, and a launch that is nearly
+        // empty still walks -- and pulls through every XCD's L2 -- the whole row.  A/B on one board (round 5): 4M x 50
+        // 21.4 ms at three paths per thread (6.8 generations) against 23.4 at four (5.1); 2M x 50 8.76 against 8.12
+        // (3.4 / 2.5 generations).  So: whichever leaves the fuller last generation.
+        const double gen4 = (double)n / (double)((int64_t)ctx->n_cus * 3 * 256 * 4), gen3 = (double)n / (double)((int64_t)ctx->n_cus * 3 * 256 * 3);
+        pl.ppt = std::ceil(gen3) - gen3 < std::ceil(gen4) - gen4 ? 3 : 4;
+        pl.lds_bytes = brb_lds_bytes(num_branches, pl.ppt);  // <= 56 KiB (twelve branches, four paths); 48 KiB at the driver's ten
+        wgs_per_cu = (int)std::min<size_t>(3, ((size_t)160 << 10) / pl.lds_bytes);
+    }
+    const int64_t per_wg = 256 * (int64_t)pl.ppt;
+    pl.grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + per_wg - 1) / per_wg, (int64_t)ctx->n_cus * wgs_per_cu));
+    if (pl.route == BR_ROUTE_XCD) {  // one launch over every tile of 512 paths, eight workgroups a tile
+        pl.slice_shift = pl.n_slices = 0;
+        pl.ppt = BRX_PPT;
+        pl.grid = (int)((n + 256 * BRX_PPT - 1) / (256 * BRX_PPT));
+    }
+    pl.per_launch = (int64_t)pl.grid * 256 * pl.ppt;
+    pl.n_launches = std::max<int64_t>(1, (n + pl.per_launch - 1) / pl.per_launch);
+    if (pl.route == BR_ROUTE_XCD) pl.grid *= 8;
+    return pl;
 }
 
 int run_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double maturity, double dt, int is_call,
                   int num_branches, const int* exercise_times, int n_ex_in, uint64_t seed, double* price, double* lower,
                   double* upper) {
     const int n_cols = P->n_steps + 1;
-    if (P->n_paths >= (int64_t)0xFFFFFFFFLL) return fail(MCG_ERR_INVALID, "BranchingProcesses: too many paths in one shard");
+    const int64_t n = P->n_paths;
+    if (n >= (int64_t)0xFFFFFFFFLL) return fail(MCG_ERR_INVALID, "BranchingProcesses: too many paths in one shard");
     std::vector<double> disc((size_t)n_cols);
     int n_dates = 0;
     for (int j = 0; j < n_cols; ++j) {
@@ -567,196 +627,108 @@ int run_branching(mcg_ctx* ctx, const mcg_paths* P, double r, double K, double m
         ex.push_back(t_idx);
     }
     const int ex_last = exercise_times[n_ex_in - 1];  // exerciseTimes.back(), :104
+    const int n_ex = (int)ex.size();
 
-    int grid = (int)std::min<int64_t>((P->n_paths + 255) / 256, (int64_t)ctx->n_cus * 8);
-    if (grid < 1) grid = 1;
-    // k_branch_bounds: launches of one resident wave of workgroups (all of them walk the dates -- and the slices of a
-    // date's row -- together), BR_PPT paths per thread
-    const int64_t per_wg = 256 * (int64_t)BR_PPT;
-    const int bgrid = (int)std::max<int64_t>(1, std::min<int64_t>((P->n_paths + per_wg - 1) / per_wg, (int64_t)ctx->n_cus * BR_WGS_PER_CU));
-    const int64_t per_launch = (int64_t)bgrid * per_wg;
-    const int64_t n_launches = std::max<int64_t>(1, (P->n_paths + per_launch - 1) / per_launch);
-    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * (size_t)std::max<int64_t>(grid, bgrid * n_launches));
+    const BranchPlan pl = plan_branching(ctx, n, num_branches, n_ex > 0);
+    ctx->branch_last_route = pl.route;
+    // the grid-stride kernels (k_branch_suffix, the XCD finishing pass, k_branch_finish, whose partials the per-date routes sum)
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->n_cus * 8));
+    const int64_t n_partials = pl.route == BR_ROUTE_ONE_LAUNCH ? (int64_t)pl.grid * pl.n_launches : grid;
+    int rc = ensure_cap(ctx, &ctx->partials, &ctx->partials_cap, (size_t)2 * (size_t)n_partials);
     if (rc) return rc;
-    void* Fbuf = nullptr;
-    rc = pool_alloc(ctx, P->bytes, &Fbuf);
-    if (rc) return rc;
-    HostPiece par[] = {{disc.data(), (size_t)n_cols * sizeof(double)}, {ex.data(), ex.size() * sizeof(int)}};
-    rc = upload_params(ctx, par);
-    // disc and ex die at return (upload_params)
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MCG_OK) rc = fail(MCG_ERR_HIP, "BranchingProcesses: table upload failed");
-    if (rc) {
-        pool_release(ctx, Fbuf, P->bytes);
-        return rc;
-    }
-    {
-        TimedLaunch t(ctx, MCG_K_BRANCHING);
-        hipLaunchKernelGGL(k_branch_suffix, dim3(grid), dim3(256), 0, ctx->stream, P->data, (double*)Fbuf, P->ld, P->n_paths,
-                           n_cols, n_dates, par[0].at, K, is_call);
-    }
-    BranchArgs a;
-    a.S = P->data;
-    a.F = (const double*)Fbuf;
-    a.ld = P->ld;
-    a.n = P->n_paths;
-    a.path_begin = P->path_begin;
-    a.k0 = (uint32_t)seed;
-    a.k1 = (uint32_t)(seed >> 32);
-    a.ex = reinterpret_cast<const int*>(par[1].at);
-    a.disc = par[0].at;
-    a.n_ex = (int)ex.size();
-    a.ex_last = ex_last;
-    a.n_cols = n_cols;
-    a.num_branches = num_branches;
-    a.K = K;
-    a.is_call = is_call;
-    // slices of the gathered row: 2 MB each, at most BR_MAX_SLICES (then of n / BR_MAX_SLICES, rounded up to a power of two)
-    int slice_shift = BR_SLICE_SHIFT;
-    while ((((P->n_paths > 0 ? P->n_paths : 1) - 1) >> slice_shift) + 1 > BR_MAX_SLICES) ++slice_shift;
-    const int n_slices = (int)((((P->n_paths > 0 ? P->n_paths : 1) - 1) >> slice_shift) + 1);
-    const int quads = (num_branches + 3) / 4;
-    int64_t n_partials = (int64_t)bgrid * n_launches;
-    void* state = nullptr;
-    size_t state_bytes = 0;
-    // Rows of more than four slices (more than a million paths), up to 2^30 - 2 paths: per-date launches of the BINNED
-    // kernel (k_branch_date_binned: every thread walks its indices sorted by slice), sixteen slices of >= 2 MB.
-    int bshift = study_switch("MCG_BRANCH_BIN_SHIFT", BR_SLICE_SHIFT);  // (A/B builds: 17 = 1 MB slices while sixteen of them cover the row)
-    while ((((P->n_paths > 0 ? P->n_paths : 1) - 1) >> bshift) + 1 > 16) ++bshift;
-    const int b_slices = (int)((((P->n_paths > 0 ? P->n_paths : 1) - 1) >> bshift) + 1);
-    const bool binned = b_slices > study_switch("MCG_BRANCH_BINNED_ABOVE", BR_DATE_MAX_SLICES) && quads >= 1 && quads <= 3 && !ex.empty() && P->n_paths < ((int64_t)1 << 30) - 1 &&
-                        study_switch("MCG_BRANCH_BINNED", 1) != 0;
-    constexpr int64_t BRX_MIN_PATHS = (int64_t)7 << 18;   // 1.835M paths = rows of 14 MB: below, the binned kernel is at least as fast
-    const int xcd_switch = study_switch("MCG_BRANCH_XCD", -1);   // (A/B builds: 0 never, 1 always)
-    if (binned && (xcd_switch < 0 ? P->n_paths >= BRX_MIN_PATHS : xcd_switch != 0)) {
-        // XCD-affine gathers (k_branch_date_xcd): a gather launch and a finishing pass per exercise date
-        const int64_t ldc = (P->n_paths + 511) / 512 * 512;
-        void* cells = nullptr;
-        const size_t cells_bytes = (size_t)8 * ldc * sizeof(double);
-        state_bytes = (size_t)P->n_paths * sizeof(double2);
-        rc = pool_alloc(ctx, state_bytes, &state);
-        if (!rc) rc = pool_alloc(ctx, cells_bytes, &cells);
-        if (rc) {
-            pool_release(ctx, Fbuf, P->bytes);
-            if (state) pool_release(ctx, state, state_bytes);
-            return rc;
-        }
-        const int64_t tiles = (P->n_paths + 256 * BRX_PPT - 1) / (256 * BRX_PPT);
+
+    PoolLease lease(ctx);  // F; on the per-date routes the paths' states; on the XCD route the cells
+    double s[3];           // {sum lower, sum upper, N}
+    // Everything that is queued, up to the sums.  THE ONE WAY OUT is the lease's: from the first launch until the sums have been
+    // synchronised it is `busy`, and whatever ends this function meanwhile -- an error code or an exception -- it waits for the stream
+    // before it hands back a buffer that a queued kernel may still be writing.
+    auto queue_and_sum = [&]() -> int {
+        void *Fbuf = nullptr, *state = nullptr, *cells = nullptr;
+        const int64_t ldc = (n + 511) / 512 * 512;
+        int rc = lease.alloc(P->bytes, &Fbuf);
+        if (!rc && pl.route != BR_ROUTE_ONE_LAUNCH) rc = lease.alloc((size_t)n * sizeof(double2), &state);
+        if (!rc && pl.route == BR_ROUTE_XCD) rc = lease.alloc((size_t)8 * ldc * sizeof(double), &cells);
+        if (rc) return rc;
+        HostPiece par[] = {{disc.data(), (size_t)n_cols * sizeof(double)}, {ex.data(), ex.size() * sizeof(int)}};
+        rc = upload_params(ctx, par);
+        // disc and ex die at return (upload_params)
+        if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == MCG_OK) rc = fail(MCG_ERR_HIP, "BranchingProcesses: table upload failed");
+        if (rc) return rc;
+        lease.busy = true;
         {
-            TimedLaunch t(ctx, MCG_K_BRANCHING, 2 * (int64_t)ex.size() + 1);
-            for (int e = 0; e < (int)ex.size(); ++e) {
-                const int t_idx = ex[(size_t)e];
-                const bool branch = t_idx < ex_last && t_idx + 1 < n_cols;
-                if (branch) {
-                    const dim3 g((unsigned)(tiles * 8)), b(256);
-                    if (quads == 1) hipLaunchKernelGGL(k_branch_date_xcd<1>, g, b, 0, ctx->stream, a, e, (double*)cells, ldc);
-                    else if (quads == 2) hipLaunchKernelGGL(k_branch_date_xcd<2>, g, b, 0, ctx->stream, a, e, (double*)cells, ldc);
-                    else hipLaunchKernelGGL(k_branch_date_xcd<3>, g, b, 0, ctx->stream, a, e, (double*)cells, ldc);
+            TimedLaunch t(ctx, MCG_K_BRANCHING);
+            hipLaunchKernelGGL(k_branch_suffix, dim3(grid), dim3(256), 0, ctx->stream, P->data, (double*)Fbuf, P->ld, n, n_cols, n_dates,
+                               par[0].at, K, is_call);
+        }
+        BranchArgs a;
+        a.S = P->data;
+        a.F = (const double*)Fbuf;
+        a.ld = P->ld;
+        a.n = n;
+        a.path_begin = P->path_begin;
+        a.k0 = (uint32_t)seed;
+        a.k1 = (uint32_t)(seed >> 32);
+        a.ex = reinterpret_cast<const int*>(par[1].at);
+        a.disc = par[0].at;
+        a.n_ex = n_ex;
+        a.ex_last = ex_last;
+        a.n_cols = n_cols;
+        a.num_branches = num_branches;
+        a.K = K;
+        a.is_call = is_call;
+
+        typedef void (*BoundsKernel)(BranchArgs, int64_t, double*, int, int);
+        typedef void (*DateKernel)(BranchArgs, int64_t, int, double2*, int, int, int);
+        typedef void (*XcdKernel)(BranchArgs, int, double*, int64_t);
+        static const BoundsKernel bounds_kernel[3] = {k_branch_bounds<1>, k_branch_bounds<2>, k_branch_bounds<3>};
+        static const DateKernel date_kernel[3] = {k_branch_date<1>, k_branch_date<2>, k_branch_date<3>};
+        static const DateKernel binned_kernel[3][2] = {{k_branch_date_binned<1, 3>, k_branch_date_binned<1, 4>},
+                                                       {k_branch_date_binned<2, 3>, k_branch_date_binned<2, 4>},
+                                                       {k_branch_date_binned<3, 3>, k_branch_date_binned<3, 4>}};
+        static const XcdKernel xcd_kernel[3] = {k_branch_date_xcd<1>, k_branch_date_xcd<2>, k_branch_date_xcd<3>};
+        // The per-date routes: for every exercise date the route's launches over the paths -- launch(e, p0, workgroups, branch), `per`
+        // kernels each; the last launch's grid covers the paths that are left (a workgroup without a live path would still draw,
+        // sort and gather for the clamped ones) --, then the sums of the states.  One event pair around the whole sequence.
+        auto per_date = [&](int per, auto&& launch) {
+            TimedLaunch t(ctx, MCG_K_BRANCHING, (int64_t)n_ex * per * pl.n_launches + 1);
+            const int64_t per_wg = 256 * (int64_t)pl.ppt;
+            for (int e = 0; e < n_ex; ++e) {
+                const bool branch = date_branches(ex[(size_t)e], ex_last, n_cols);
+                for (int64_t l = 0; l < pl.n_launches; ++l) {
+                    const int64_t left = n - l * pl.per_launch;
+                    launch(e, l * pl.per_launch, (unsigned)std::min<int64_t>(pl.grid, (left + per_wg - 1) / per_wg), branch);
                 }
+            }
+            hipLaunchKernelGGL(k_branch_finish, dim3(grid), dim3(256), 0, ctx->stream, (const double2*)state, n, ctx->partials);
+        };
+        if (pl.route == BR_ROUTE_XCD) {  // a gather launch where the date branches (all the tiles: pl.grid) and a finishing pass
+            per_date(2, [&](int e, int64_t, unsigned, bool branch) {
+                if (branch) hipLaunchKernelGGL(xcd_kernel[pl.quads - 1], dim3((unsigned)pl.grid), dim3(256), 0, ctx->stream, a, e, (double*)cells, ldc);
                 hipLaunchKernelGGL(k_branch_date_xcd_finish, dim3(grid), dim3(256), 0, ctx->stream, a, e, (const double*)cells, ldc, (double2*)state,
                                    e == 0, branch ? 1 : 0);
+            });
+        } else if (pl.route != BR_ROUTE_ONE_LAUNCH) {
+            const DateKernel k = pl.route == BR_ROUTE_BINNED ? binned_kernel[pl.quads - 1][pl.ppt - 3] : date_kernel[pl.quads - 1];
+            if (pl.lds_bytes > ((size_t)48 << 10)) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+            per_date(1, [&](int e, int64_t p0, unsigned g, bool branch) {
+                hipLaunchKernelGGL(k, dim3(g), dim3(256), pl.lds_bytes, ctx->stream, a, p0, e, (double2*)state, e == 0, pl.slice_shift,
+                                   branch ? pl.n_slices : 0);
+            });
+        } else {
+            for (int64_t l = 0; l < pl.n_launches; ++l) {
+                TimedLaunch t(ctx, MCG_K_BRANCHING);
+                double* part = ctx->partials + 2 * l * pl.grid;
+                const dim3 g(pl.grid), b(256);
+                if (pl.quads <= 3) hipLaunchKernelGGL(bounds_kernel[std::max(pl.quads, 1) - 1], g, b, 0, ctx->stream, a, l * pl.per_launch, part, pl.slice_shift, pl.n_slices);
+                else hipLaunchKernelGGL(k_branch_bounds_any, g, b, 0, ctx->stream, a, l * pl.per_launch, part);
             }
-            hipLaunchKernelGGL(k_branch_finish, dim3(grid), dim3(256), 0, ctx->stream, (const double2*)state, P->n_paths, ctx->partials);
         }
-        n_partials = grid;
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            pool_release(ctx, Fbuf, P->bytes);
-            pool_release(ctx, state, state_bytes);
-            pool_release(ctx, cells, cells_bytes);
-            return fail(MCG_ERR_HIP, "BranchingProcesses: kernel launch failed");
-        }
-        pool_release(ctx, cells, cells_bytes);
-    } else if (binned) {
-        // Paths per thread: a generation is three resident workgroups per CU of 256 x PPT paths, and a launch that is nearly
-        // empty still walks -- and pulls through every XCD's L2 -- the whole row.  A/B on one board (round 5): 4M x 50
-        // 21.4 ms at three paths per thread (6.8 generations) against 23.4 at four (5.1); 2M x 50 8.76 against 8.12
-        // (3.4 / 2.5 generations).  So: whichever leaves the fuller last generation.
-        const double gen4 = (double)P->n_paths / (double)((int64_t)ctx->n_cus * 3 * 256 * 4), gen3 = (double)P->n_paths / (double)((int64_t)ctx->n_cus * 3 * 256 * 3);
-        const int ppt = std::ceil(gen3) - gen3 < std::ceil(gen4) - gen4 ? 3 : 4;
-        const int64_t per_wg_b = 256 * (int64_t)ppt;
-        const size_t lds_b = brb_lds_bytes(num_branches, ppt);  // <= 56 KiB (twelve branches, four paths); 48 KiB at the driver's ten
-        const int wgs_per_cu = (int)std::min<size_t>(3, ((size_t)160 << 10) / lds_b);
-        const int ggrid = (int)std::max<int64_t>(1, std::min<int64_t>((P->n_paths + per_wg_b - 1) / per_wg_b, (int64_t)ctx->n_cus * wgs_per_cu));
-        typedef void (*BinnedKernel)(BranchArgs, int64_t, int, double2*, int, int, int);
-        static const BinnedKernel kern[3][2] = {{k_branch_date_binned<1, 3>, k_branch_date_binned<1, 4>},
-                                                {k_branch_date_binned<2, 3>, k_branch_date_binned<2, 4>},
-                                                {k_branch_date_binned<3, 3>, k_branch_date_binned<3, 4>}};
-        const BinnedKernel k = kern[quads - 1][ppt - 3];
-        if (lds_b > ((size_t)48 << 10)) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b);
-        const int64_t per_launch_b = (int64_t)ggrid * per_wg_b;
-        const int64_t n_launches_b = std::max<int64_t>(1, (P->n_paths + per_launch_b - 1) / per_launch_b);
-        state_bytes = (size_t)P->n_paths * sizeof(double2);
-        rc = pool_alloc(ctx, state_bytes, &state);
-        if (rc) {
-            pool_release(ctx, Fbuf, P->bytes);
-            return rc;
-        }
-        {
-            TimedLaunch t(ctx, MCG_K_BRANCHING, (int64_t)ex.size() * n_launches_b + 1);
-            for (int e = 0; e < (int)ex.size(); ++e) {
-                const int t_idx = ex[(size_t)e];
-                const bool branch = t_idx < ex_last && t_idx + 1 < n_cols;
-                const int ns = branch ? b_slices : 0;
-                for (int64_t l = 0; l < n_launches_b; ++l) {
-                    // (the last generation's grid covers the paths that are left: a workgroup without a live path would still
-                    //  draw, sort and gather for the clamped ones)
-                    const int64_t left = P->n_paths - l * per_launch_b;
-                    const int g = (int)std::min<int64_t>(ggrid, (left + per_wg_b - 1) / per_wg_b);
-                    hipLaunchKernelGGL(k, dim3(g), dim3(256), lds_b, ctx->stream, a, l * per_launch_b, e, (double2*)state, e == 0, bshift, ns);
-                }
-            }
-            hipLaunchKernelGGL(k_branch_finish, dim3(grid), dim3(256), 0, ctx->stream, (const double2*)state, P->n_paths, ctx->partials);
-        }
-        n_partials = grid;
-    } else if (n_slices > 1 && n_slices <= BR_DATE_MAX_SLICES && quads >= 1 && quads <= 3 && !ex.empty()) {
-        // Rows of two to four slices: one launch per exercise date, bounds in `state`.  A/B on one board, 1M x 50: 5.55 ms
-        // (one launch, no slices) -> 5.25 (one launch, slices: 42 % L2 hits) -> 2.83 (per-date launches).  A pass costs
-        // ~40 cycles per wave-load however few lanes take part, so rows of many slices lose what the hits gain (4M x 50,
-        // 16 slices: 44.7 ms per date-launches against 29.6 in one launch with 8 slices and 35.3 without): those keep the
-        // one-launch kernel.
-        state_bytes = (size_t)P->n_paths * sizeof(double2);
-        rc = pool_alloc(ctx, state_bytes, &state);
-        if (rc) {
-            pool_release(ctx, Fbuf, P->bytes);
-            return rc;
-        }
-        {
-            TimedLaunch t(ctx, MCG_K_BRANCHING, (int64_t)ex.size() * n_launches + 1);
-            for (int e = 0; e < (int)ex.size(); ++e) {
-                const int t_idx = ex[(size_t)e];
-                const bool branch = t_idx < ex_last && t_idx + 1 < n_cols;
-                for (int64_t l = 0; l < n_launches; ++l) {
-                    const int64_t left = P->n_paths - l * per_launch;
-                    const dim3 g((unsigned)std::min<int64_t>(bgrid, (left + per_wg - 1) / per_wg)), b(256);
-                    const int ns = branch ? n_slices : 0;
-                    if (quads == 1) hipLaunchKernelGGL(k_branch_date<1>, g, b, 0, ctx->stream, a, l * per_launch, e, (double2*)state, e == 0, slice_shift, ns);
-                    else if (quads == 2) hipLaunchKernelGGL(k_branch_date<2>, g, b, 0, ctx->stream, a, l * per_launch, e, (double2*)state, e == 0, slice_shift, ns);
-                    else hipLaunchKernelGGL(k_branch_date<3>, g, b, 0, ctx->stream, a, l * per_launch, e, (double2*)state, e == 0, slice_shift, ns);
-                }
-            }
-            hipLaunchKernelGGL(k_branch_finish, dim3(grid), dim3(256), 0, ctx->stream, (const double2*)state, P->n_paths, ctx->partials);
-        }
-        n_partials = grid;
-    } else {
-        for (int64_t l = 0; l < n_launches; ++l) {
-            TimedLaunch t(ctx, MCG_K_BRANCHING);
-            double* part = ctx->partials + 2 * l * bgrid;
-            const dim3 g(bgrid), b(256);
-            if (quads <= 1) hipLaunchKernelGGL(k_branch_bounds<1>, g, b, 0, ctx->stream, a, l * per_launch, part, slice_shift, n_slices);
-            else if (quads == 2) hipLaunchKernelGGL(k_branch_bounds<2>, g, b, 0, ctx->stream, a, l * per_launch, part, slice_shift, n_slices);
-            else if (quads == 3) hipLaunchKernelGGL(k_branch_bounds<3>, g, b, 0, ctx->stream, a, l * per_launch, part, slice_shift, n_slices);
-            else hipLaunchKernelGGL(k_branch_bounds_any, g, b, 0, ctx->stream, a, l * per_launch, part);
-        }
-    }
-    if (hipGetLastError() != hipSuccess) {
-        (void)hipStreamSynchronize(ctx->stream);
-        pool_release(ctx, Fbuf, P->bytes);
-        if (state) pool_release(ctx, state, state_bytes);
-        return fail(MCG_ERR_HIP, "BranchingProcesses: kernel launch failed");
-    }
-    double s[3];
-    rc = finish_sums(ctx, n_partials, P->n_paths, s);  // {sum lower, sum upper, N}; synchronises the stream
-    pool_release(ctx, Fbuf, P->bytes);
-    if (state) pool_release(ctx, state, state_bytes);
+        if (hipGetLastError() != hipSuccess) return fail(MCG_ERR_HIP, "BranchingProcesses: kernel launch failed");
+        rc = finish_sums(ctx, n_partials, n, s);  // synchronises the stream
+        if (!rc) lease.busy = false;
+        return rc;
+    };
+    rc = queue_and_sum();
     if (rc) return rc;
     if (!(s[2] >= 1.0)) return fail(MCG_ERR_EMPTY_PATHS, "BranchingProcesses: Empty pricePaths.");
     const double lo = s[0] / s[2], up = s[1] / s[2];

@@ -1292,6 +1292,18 @@ int mcg_debug_gbm_route(mcg_ctx* ctx, int route, int* last_route) {
     return MCG_OK;
 }
 
+int mcg_debug_branch_route(mcg_ctx* ctx, int route, int slice_shift, int* last_route) {
+    if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
+    if (route < -1 || route > 4) return fail(MCG_ERR_INVALID, "route must be 0 (auto), 1 (one launch), 2 (per date), 3 (binned), 4 (XCD) or -1 (unchanged)");
+    if (route >= 0 && (slice_shift < 0 || slice_shift > 30)) return fail(MCG_ERR_INVALID, "slice_shift must be in [0,30] (got %d)", slice_shift);
+    if (route >= 0) {
+        ctx->branch_route = route;
+        ctx->branch_shift = slice_shift;
+    }
+    if (last_route) *last_route = ctx->branch_last_route;
+    return MCG_OK;
+}
+
 int mcg_debug_batch_budget(mcg_ctx* ctx, size_t bytes) {
     if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
     ctx->batch_budget = bytes;

@@ -119,6 +119,9 @@ struct mcg_ctx {
     double* sincos2_tab = nullptr;  // device copy of host_sincos2_tables(): coarse, then fine (128 KiB; fm::sincos_two_level)
     int gbm_route = 0;           // mcg_debug_gbm_route: 0 = launch_gbm chooses, 1 = k_gbm_paths, 2 = k_gbm_paths_wide
     int gbm_last_route = 0;      //   what the last GBM launch took (1 or 2; 0: none yet)
+    int branch_route = 0;        // mcg_debug_branch_route: 0 = run_branching's plan chooses, 1..4 = that route where it can run
+    int branch_shift = 0;        //   the slice shift the plan starts from (0: the default, 18)
+    int branch_last_route = 0;   //   what the last mcg_price_branching took (1..4; 0: none yet)
     int64_t lsm_dual_executed = 0;  // mcg_debug_lsm_dual_executed: path-steps the waves of the last mcg_lsm_dual_upper ran through
     size_t lsm_dual_ws_doubles = 0;  // mcg_debug_lsm_dual_workspace: the workspace bound of one batch of mcg_lsm_dual_upper (0: default)
 
@@ -175,6 +178,27 @@ constexpr int SC_LSM_STATE = 144;  // [144..147) per-date LSM state: date, phase
 
 int pool_alloc(mcg_ctx* ctx, size_t bytes, void** out);
 void pool_release(mcg_ctx* ctx, void* ptr, size_t bytes);
+// Pool buffers of one scope: whatever alloc() handed out goes back to the pool on every way out of it.  Nothing queued may still
+// use a buffer then: the holder sets `busy` while launches that use them may be pending, and the lease waits for the stream first
+// (or the holder synchronises itself on its error paths, as run_batch_chunk does).
+struct PoolLease {
+    mcg_ctx* ctx;
+    std::vector<PoolBuf> held;
+    bool busy = false;
+    explicit PoolLease(mcg_ctx* c) : ctx(c) {}
+    PoolLease(const PoolLease&) = delete;
+    PoolLease& operator=(const PoolLease&) = delete;
+    int alloc(size_t bytes, void** out) {
+        held.reserve(held.size() + 1);  // (a bad_alloc here leaves no buffer out)
+        const int rc = pool_alloc(ctx, bytes, out);
+        if (!rc) held.push_back(PoolBuf{*out, bytes});
+        return rc;
+    }
+    ~PoolLease() {
+        if (busy) (void)hipStreamSynchronize(ctx->stream);
+        for (const PoolBuf& b : held) pool_release(ctx, b.ptr, b.bytes);
+    }
+};
 int ensure_cap(mcg_ctx* ctx, double** buf, size_t* cap, size_t need_doubles);
 // timing scope: records events around a launch when ctx->timing is on
 struct TimedLaunch {

@@ -796,6 +796,14 @@ class PathEngine:
         check(self._L.mcg_debug_gbm_route(self._ctx, int(route), C.byref(last)))
         return last.value
 
+    def debug_branch_route(self, route: int = -1, slice_shift: int = 0) -> int:
+        """Test hook (mcg_debug_branch_route): 0 = price_branching chooses its kernels by size, 1 = one launch, 2 = a launch
+        per date, 3 = binned, 4 = XCD-affine, -1 = unchanged; slice_shift = log2 of the paths in a slice of the gathered row
+        (0: 18); returns what the last price_branching took (1..4; 0: none yet)."""
+        last = C.c_int()
+        check(self._L.mcg_debug_branch_route(self._ctx, int(route), int(slice_shift), C.byref(last)))
+        return last.value
+
     # -- measurement ----------------------------------------------------------------------------
     def timing_enable(self, on: bool = True) -> None:
         check(self._L.mcg_timing_enable(self._ctx, int(on)))

@@ -23,8 +23,10 @@ struct mcg_ctx;
 namespace mcg {
 namespace co {
 
-constexpr int MAX_PATHS = 256;   // columns of a row's matrix block (kernels_batch.hip: BATCH_LD)
-constexpr int MAX_STEPS = 1020;  // steps the row kernels serve (BATCH_MAX_STEPS)
+// The two limits of a row, stated here once: kernels_batch.hip defines BATCH_LD and BATCH_MAX_STEPS from them and asserts what its
+// kernels need of them (one path per thread of 256, transforms up to 1024 points).
+constexpr int MAX_PATHS = 256;   // columns of a row's matrix block = the paths a row can have
+constexpr int MAX_STEPS = 1020;  // steps the row kernels serve
 constexpr size_t SLOT_DOUBLES = (size_t)MAX_PATHS * (size_t)(MAX_STEPS + 1);  // one thread's resident matrix block
 
 enum Kind { GEN = 0, ASYM = 1, BRANCH = 2, LSM = 3, MART = 4, N_KINDS = 5 };

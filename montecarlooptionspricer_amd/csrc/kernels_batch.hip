@@ -1,13 +1,20 @@
 // Batched driver rows: the per-row work of the reference's production caller
 // (/root/reference/src/core/PredictionGen.cpp:700-791 -- 250 rBergomi paths, then AsymptoticAnalysis,
 // BranchingProcesses(10 branches, exercise dates 0..steps-1), LSM(polyOrder 2), MartingaleOptimization(2))
-// for MANY option rows in six launches (per chunk of rows, run_batch_rows) instead of ~15 launches and ~8 host
-// synchronisations per row:
-//   k_batch_weights    one workgroup per row: lambda -> |phi_k|^2 -> spectral amplitudes a_k and compensator
-//                      (the host/volterra.cpp math, done with a direct DFT against an LDS table of roots of unity)
-//   k_batch_paths      a few workgroups per row: the FFT generator of rbergomi_device.hpp
-//   k_batch_asym / _branching / _lsm / _martingale    one workgroup per row (n_paths <= 256: one path per
-//                      thread), all reductions inside the workgroup, regression solves on thread 0
+// for MANY option rows at once instead of ~15 launches and ~8 host synchronisations per row.  Three layers:
+//   the six row kernels
+//     k_batch_weights    one workgroup per row: lambda -> |phi_k|^2 -> spectral amplitudes a_k and compensator
+//                        (the host/volterra.cpp math, done with a direct DFT against an LDS table of roots of unity)
+//     k_batch_paths      a few workgroups per row: the FFT generator of rbergomi_device.hpp
+//     k_batch_asym / _branching / _lsm / _martingale    one workgroup per row (n_paths <= 256: one path per
+//                        thread), all reductions inside the workgroup, regression solves on thread 0
+//   one launch function behind each kernel (launch_row_weights ... launch_row_martingale): grid, block, the dynamic LDS
+//     that kernel's layout needs, the instance for an LDS class or a polynomial order -- stated once, for both hosts
+//   two hosts
+//     run_batch_rows / run_batch_chunk   mcg_batch_price_rows{,6}: all six launches per chunk of rows
+//     co::run_round                      the class API's coalesced calls (coalesce.hpp): one launch per group of queued calls
+// Both hosts make a row's device image with batch_row_image and the generator's workgroup map with batch_row_shares /
+// batch_wg_entry.
 // Row c uses Philox path ids (c << 32) + p, so its four prices equal those of the single-contract entry
 // points called with path_begin = c << 32 (up to the ~1e-13 difference between the device DFT and the host FFT
 // in the amplitudes).  Matrix layout: every row owns ONE contiguous block of (n_steps + 1) x 256 doubles, step-major
@@ -18,9 +25,9 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <vector>
-
 #include <cstring>
+#include <tuple>
+#include <vector>
 
 #include "branching_device.hpp"
 #include "coalesce.hpp"
@@ -30,9 +37,20 @@
 
 namespace mcg {
 
+// The two limits of a row.  coalesce.hpp owns the numbers (its slots and the drop-in classes' arena are sized from them); the row
+// kernels index by these names.
 // steps of a row the row kernels serve (their transforms go up to Mz = 1024, their per-row LDS tables with them); longer
 // rows take the single-contract entry points (run_batch_rows)
-constexpr int BATCH_MAX_STEPS = 1020;
+constexpr int BATCH_MAX_STEPS = co::MAX_STEPS;
+constexpr int64_t BATCH_LD = co::MAX_PATHS;  // columns of a row's block = paths a row can have: one path per thread of a 256-thread workgroup
+
+__host__ __device__ __forceinline__ constexpr int batch_next_pow2(int n) {  // a row's transform size M: the next power of two at or above n_steps
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+static_assert(BATCH_LD == 256 && batch_next_pow2(BATCH_MAX_STEPS) == 1024,
+              "the row kernels launch 256 threads, one per path, and k_batch_paths<3> transforms 1024 points at the most");
 
 struct BatchRow {  // device image of one option row
     double S0, logS0, xi, H, eta, strike, maturity, sigma, dividend;
@@ -42,7 +60,31 @@ struct BatchRow {  // device image of one option row
     uint32_t k0, k1;  // its Philox key: the call's seed (mcg_batch_price_rows) or the row's own (coalesced class-API calls, coalesce.hpp)
     int n_steps, M, is_call, valid;
 };
-constexpr int64_t BATCH_LD = 256;  // columns of a row's block (n_paths <= 256)
+
+// The device image of a row from its contract fields (Row: mcg_row or co::Request, which name them alike), its Philox id and key.
+// off / woff are the host's to place.  logS0 is the caller's: log(S0) where k_batch_paths will generate the row, and the
+// coalesced pricer requests, whose matrix exists already, pass 0 and pay for no log.
+template <class Row>
+static BatchRow batch_row_image(const Row& s, uint64_t id, uint64_t seed, double logS0) {
+    BatchRow d{};
+    d.S0 = s.S0;
+    d.logS0 = logS0;
+    d.xi = s.xi;
+    d.H = s.H;
+    d.eta = s.eta;
+    d.strike = s.strike;
+    d.maturity = s.maturity;
+    d.sigma = s.sigma;
+    d.dividend = s.dividend;
+    d.id = id;
+    d.k0 = (uint32_t)seed;
+    d.k1 = (uint32_t)(seed >> 32);
+    d.n_steps = s.n_steps;
+    d.M = batch_next_pow2(s.n_steps);
+    d.is_call = s.is_call;
+    d.valid = 1;
+    return d;
+}
 
 struct BatchArgs {
     const BatchRow* rows;
@@ -54,24 +96,21 @@ struct BatchArgs {
     double* S;      // the rows' matrix blocks (BatchRow::off)
     const double2* log_tab;
     double* out;    // [n_rows][4]: asymptotic, branching, lsm, martingale (chunk-local row order)
-    const uint32_t* wg_map;  // k_batch_paths: workgroup -> (chunk-local row << 6) | share of the row's pairs
+    const uint32_t* wg_map;  // k_batch_paths: workgroup -> batch_wg_entry(launch-local row, share of the row's pairs)
     double* bad;    // [n_rows]: != 0 when the row's path block holds a non-finite price (the driver zeroes such a row, PredictionGen.cpp:752-777)
     int num_branches, max_iterations;
 };
 
-__device__ __forceinline__ int next_pow2_dev(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 // ---- weights ---------------------------------------------------------------------------------
 // LDS: ct/st[Mphi] roots of unity, lam[steps+1], P[M] (then amp in place)
+static size_t batch_weights_lds_bytes(const BatchArgs& a) {  // (Mphi = next_pow2(steps + 1) <= 2 M)
+    return (4 * (size_t)a.m_max + (size_t)a.max_steps + 1 + (size_t)a.m_max) * sizeof(double);
+}
 __global__ __launch_bounds__(256) void k_batch_weights(BatchArgs a) {
     extern __shared__ double sm[];
     const BatchRow row = a.rows[blockIdx.x];
     if (!row.valid) return;
-    const int steps = row.n_steps, M = row.M, Mphi = next_pow2_dev(steps + 1);
+    const int steps = row.n_steps, M = row.M, Mphi = batch_next_pow2(steps + 1);
     double* ct = sm;
     double* st = ct + Mphi;
     double* lam = st + Mphi;
@@ -113,16 +152,38 @@ __global__ __launch_bounds__(256) void k_batch_weights(BatchArgs a) {
 // CLS = the LDS class of the launch's rows (lds_class: Mz <= 128 / 256 / 512 / 1024): a launch holds rows of ONE class, and its
 // kernel only the transforms that class can need -- the register count of the Mz = 1024 variant is not what the many short
 // rows of the driver (Mz <= 128) should pay for.
+// LDS class of a row: the row kernels' dynamic LDS is sized by the longest row of a LAUNCH, so the rare long rows (Mz >= 256:
+// more than half a year of trading days) are launched apart from the many short ones, whose occupancy they would cost.
+static int lds_class(int M) { return M <= 128 ? 0 : M == 256 ? 1 : M == 512 ? 2 : 3; }
+constexpr int N_LDS_CLASSES = 4;
+
+// The workgroup map: one workgroup per share of rb_pairs_per_block(M) pairs of a row -- exactly those that exist -- as one word,
+// the launch-local row above BATCH_SHARE_BITS bits of share.
+constexpr int BATCH_SHARE_BITS = 6;
+constexpr size_t BATCH_MAP_MAX_ROWS = (size_t)1 << (32 - BATCH_SHARE_BITS);  // rows of one launch the word has room for: 2^26
+constexpr size_t BATCH_CHUNK_MAX_ROWS = (size_t)1 << 24;  // rows run_batch_rows gives a chunk: a cap of its own, a quarter of that
+static_assert(BATCH_CHUNK_MAX_ROWS <= BATCH_MAP_MAX_ROWS, "a chunk's rows do not fit the map's row bits");
+__host__ __device__ constexpr int batch_row_shares(int n_paths, int M) { return ((n_paths + 1) / 2 + rb_pairs_per_block(M) - 1) / rb_pairs_per_block(M); }
+__host__ __device__ constexpr uint32_t batch_wg_entry(int64_t row, int share) { return ((uint32_t)row << BATCH_SHARE_BITS) | (uint32_t)share; }
+// (the most shares a row can have: every path, at the transform with the fewest pairs per workgroup)
+static_assert(batch_row_shares((int)BATCH_LD, batch_next_pow2(BATCH_MAX_STEPS)) <= 1 << BATCH_SHARE_BITS, "a row's shares do not fit the map's share bits");
+
+// LDS: rb_smem_bytes of the transform, the largest over the transform sizes the launch can hold (the staging part does not grow with Mz)
+static size_t batch_paths_lds_bytes(const BatchArgs& a) {
+    size_t bytes = 0;
+    for (int m = 1; m <= a.m_max; m <<= 1) bytes = std::max(bytes, rb_smem_bytes(m, std::min(m, a.max_steps)));
+    return bytes;
+}
 template <int CLS>
 __global__ __launch_bounds__(256, MCG_BATCH_PATHS_WAVES) void k_batch_paths(BatchArgs a) {
     extern __shared__ double smem[];
     __shared__ fm::Tables tabs;
-    // One workgroup per (row, share) that exists (run_batch_chunk's map).  Until round 5 the grid was rows x the widest row's
+    // One workgroup per (row, share) that exists (BatchArgs::wg_map).  Until round 5 the grid was rows x the widest row's
     // shares and the others left at once -- but a workgroup that leaves at once has still been given its 71 KB of LDS and 185
     // registers: 45 % of the 80 000 workgroups of a 20 000-row call queued for the two slots of a CU only to return.
     const uint32_t m = a.wg_map[blockIdx.x];
-    const int64_t r_idx = m >> 6;
-    const int sub = (int)(m & 63u);
+    const int64_t r_idx = m >> BATCH_SHARE_BITS;
+    const int sub = (int)(m & ((1u << BATCH_SHARE_BITS) - 1u));
     const BatchRow row = a.rows[r_idx];
     if (!row.valid) return;
     RbArgs g;
@@ -170,6 +231,7 @@ __global__ __launch_bounds__(256, MCG_BATCH_PATHS_WAVES) void k_batch_paths(Batc
 #define MCG_ASYM_DEPTH 4   // loads of a thread's scan in flight (A/B builds: 8)
 #endif
 // ---- AsymptoticAnalysis (AsymptoticAnalysisPricer.cpp:38-113), one workgroup per row ------------
+static size_t batch_asym_lds_bytes(const BatchArgs& a) { return 2 * ((size_t)a.max_steps + 1) * sizeof(double); }  // (disc begins at sm + max_steps + 1)
 __global__ __launch_bounds__(256) void k_batch_asym(BatchArgs a) {
     extern __shared__ double sm[];  // bnd[n_cols], disc[n_cols]
     __shared__ double red[2 * 4];
@@ -240,6 +302,7 @@ __global__ __launch_bounds__(256) void k_batch_asym(BatchArgs a) {
 // and the lower bound the FIRST date with a positive payoff, i.e. the one found last on the way back: the order of the
 // walk does not matter.  The resampling draws are the single-contract kernels': the contract stated in branching_device.hpp
 // (stream, counter = date * quads + quad, index, which draws exist), with the path id (row << 32) + path.
+static size_t batch_branching_lds_bytes(const BatchArgs& a) { return ((size_t)a.max_steps + 1) * sizeof(double); }
 __global__ __launch_bounds__(256) void k_batch_branching(BatchArgs a) {
     extern __shared__ double sm[];  // disc[n_cols]
     __shared__ double red[2 * 4];
@@ -324,6 +387,7 @@ __global__ __launch_bounds__(64) void k_batch_lsm(BatchArgs a) {
 }
 
 // ---- MartingaleOptimization (MartingaleOptimizationPricer.cpp:21-189) ----------------------------
+static size_t batch_martingale_lds_bytes(const BatchArgs& a) { return ((size_t)a.max_steps + 1) * sizeof(double); }
 template <int NB>
 __global__ __launch_bounds__(256) void k_batch_martingale(BatchArgs a) {
     constexpr int NM = 3 * NB - 1;
@@ -437,29 +501,57 @@ __global__ __launch_bounds__(256) void k_batch_martingale(BatchArgs a) {
     }
 }
 
-// LSM on `lsm_stream`, MartingaleOptimization on `mo_stream` (run_batch_chunk: the same stream, or the auxiliary one)
-template <int NB>
-static void launch_row_regressions(const BatchArgs& a, size_t smem_cols, hipStream_t lsm_stream, hipStream_t mo_stream) {
-    hipLaunchKernelGGL(k_batch_lsm<NB>, dim3((unsigned)a.n_rows), dim3(64), 0, lsm_stream, a);
-    hipLaunchKernelGGL(k_batch_martingale<NB>, dim3((unsigned)a.n_rows), dim3(256), smem_cols, mo_stream, a);
+// ---- the launch of each row kernel, for both hosts -------------------------------------------------------------------
+// One workgroup per row of `a` (k_batch_paths: per entry of a.wg_map; k_batch_lsm: one wavefront), the dynamic LDS the
+// kernel's layout asks for at a.max_steps / a.m_max (the *_lds_bytes beside each kernel), on the caller's stream.
+typedef void (*RowKernel)(BatchArgs);
+
+static void launch_row_weights(hipStream_t s, const BatchArgs& a) {
+    hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)a.n_rows), dim3(256), batch_weights_lds_bytes(a), s, a);
 }
 
-namespace {
+// cls: the LDS class of the launch's rows (one class to a launch); n_map: the entries of a.wg_map
+static void launch_row_paths(hipStream_t s, const BatchArgs& a, int cls, size_t n_map) {
+    static const RowKernel paths_kernel[N_LDS_CLASSES] = {k_batch_paths<0>, k_batch_paths<1>, k_batch_paths<2>, k_batch_paths<3>};
+    // (A/B builds: fewer workgroups per CU -- how much does the generator live off its occupancy?)
+    const size_t lds = batch_paths_lds_bytes(a) + ((size_t)study_switch("MCG_BATCH_PATHS_EXTRA_LDS_KB", 0) << 10);
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)paths_kernel[cls], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(paths_kernel[cls], dim3((unsigned)n_map), dim3(256), lds, s, a);
+}
+
+static void launch_row_asym(hipStream_t s, const BatchArgs& a) {
+    hipLaunchKernelGGL(k_batch_asym, dim3((unsigned)a.n_rows), dim3(256), batch_asym_lds_bytes(a), s, a);
+}
+
+static void launch_row_branching(hipStream_t s, const BatchArgs& a) {
+    hipLaunchKernelGGL(k_batch_branching, dim3((unsigned)a.n_rows), dim3(256), batch_branching_lds_bytes(a), s, a);
+}
+
+// The two regressions' instances by polynomial order (NB = order + 1 basis functions; both hosts send orders above 4 elsewhere).
+struct OrderKernels {
+    RowKernel lsm, martingale;
+};
+static const OrderKernels& order_kernels(int poly_order) {
+    static const OrderKernels k[5] = {{k_batch_lsm<1>, k_batch_martingale<1>}, {k_batch_lsm<2>, k_batch_martingale<2>}, {k_batch_lsm<3>, k_batch_martingale<3>},
+                                      {k_batch_lsm<4>, k_batch_martingale<4>}, {k_batch_lsm<5>, k_batch_martingale<5>}};
+    return k[std::min(poly_order, 4)];
+}
+
+static void launch_row_lsm(hipStream_t s, const BatchArgs& a, int poly_order) {  // (its workspace is static LDS)
+    hipLaunchKernelGGL(order_kernels(poly_order).lsm, dim3((unsigned)a.n_rows), dim3(64), 0, s, a);
+}
+
+static void launch_row_martingale(hipStream_t s, const BatchArgs& a, int poly_order) {
+    hipLaunchKernelGGL(order_kernels(poly_order).martingale, dim3((unsigned)a.n_rows), dim3(256), batch_martingale_lds_bytes(a), s, a);
+}
 
 // Device workspace one row needs in a chunk: its matrix block, its amplitudes + compensator, its image and its four prices.
-size_t row_workspace_bytes(int n_steps, int M) {
+static size_t row_workspace_bytes(int n_steps, int M) {
     // (+ the generator's workgroup map: at most 32 shares of 4 bytes per row at 256 paths)
     return ((size_t)BATCH_LD * (size_t)(n_steps + 1) + (size_t)M + (size_t)n_steps + 5) * sizeof(double) + sizeof(BatchRow) + 32 * sizeof(uint32_t);
 }
 
-// LDS class of a row: the row kernels' dynamic LDS is sized by the longest row of a LAUNCH, so the rare long rows (Mz >= 256:
-// more than half a year of trading days) are launched apart from the many short ones, whose occupancy they would cost.
-int lds_class(int M) { return M <= 128 ? 0 : M == 256 ? 1 : M == 512 ? 2 : 3; }
-constexpr int N_LDS_CLASSES = 4;
-
-}  // namespace
-
-// The six launches for ONE chunk of rows (h: their device images, already with offsets); prices into out[4 * h[k].id ...].
+// All six launches for ONE chunk of rows (h: their device images, already with offsets); prices into out[4 * h[k].id ...].
 static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, double* d_S, double* d_small, int poly_order, double* out,
                            unsigned char* priced) {
     const int64_t n = (int64_t)h.size();
@@ -484,19 +576,11 @@ static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, 
     hipError_t e = hipMemcpyAsync((void*)a.rows, h.data(), sizeof(BatchRow) * (size_t)n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(a.out, 0, 5 * sizeof(double) * (size_t)n, ctx->stream);  // (prices and the rows' flags)
     if (e != hipSuccess) return fail(MCG_ERR_HIP, "batch upload failed: %s", hipGetErrorString(e));
-    const int mphi_max = 2 * m_max >= 2 ? 2 * m_max : 2;
-    const size_t smem_w = ((size_t)2 * mphi_max + (size_t)max_steps + 1 + (size_t)m_max) * sizeof(double);
-    size_t smem_p = 0;  // largest over the transform sizes present (the staging part does not grow with Mz)
-    for (int m = 1; m <= m_max; m <<= 1) smem_p = std::max(smem_p, rb_smem_bytes(m, std::min(m, max_steps)));
-    smem_p += (size_t)study_switch("MCG_BATCH_PATHS_EXTRA_LDS_KB", 0) << 10;  // (A/B builds: fewer workgroups per CU -- how much does the generator live off its occupancy?)
-    const size_t smem_c = ((size_t)max_steps + 1) * sizeof(double);
-    // k_batch_paths: one workgroup per share of rb_pairs_per_block(Mz) pairs of a row -- exactly those that exist
-    const int n_pairs = (a.n_paths + 1) / 2;
-    std::vector<uint32_t> wg_map;
+    std::vector<uint32_t> wg_map;  // k_batch_paths' workgroups
     wg_map.reserve((size_t)n * 2);
     for (int64_t k = 0; k < n; ++k) {
-        const int shares = (n_pairs + rb_pairs_per_block(h[(size_t)k].M) - 1) / rb_pairs_per_block(h[(size_t)k].M);  // <= 63 (n_paths <= 256)
-        for (int sub = 0; sub < shares; ++sub) wg_map.push_back((uint32_t)(k << 6) | (uint32_t)sub);
+        const int shares = batch_row_shares(a.n_paths, h[(size_t)k].M);
+        for (int sub = 0; sub < shares; ++sub) wg_map.push_back(batch_wg_entry(k, sub));
     }
     std::vector<double> four((size_t)n * 5);   // (host memory first: a bad_alloc below this line would leave a pool buffer out)
     void* d_map = nullptr;
@@ -509,12 +593,8 @@ static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, 
     a.wg_map = (const uint32_t*)d_map;
     {
         TimedLaunch t(ctx, MCG_K_BATCH);
-        hipLaunchKernelGGL(k_batch_weights, dim3((unsigned)n), dim3(256), smem_w, ctx->stream, a);
-        typedef void (*PathsKernel)(BatchArgs);
-        static const PathsKernel paths_kernel[N_LDS_CLASSES] = {k_batch_paths<0>, k_batch_paths<1>, k_batch_paths<2>, k_batch_paths<3>};
-        const PathsKernel pk = paths_kernel[lds_class(m_max)];  // (a chunk holds rows of one class, run_batch_rows)
-        if (smem_p > 48 * 1024) (void)hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_p);
-        hipLaunchKernelGGL(pk, dim3((unsigned)wg_map.size()), dim3(256), smem_p, ctx->stream, a);
+        launch_row_weights(ctx->stream, a);
+        launch_row_paths(ctx->stream, a, lds_class(m_max), wg_map.size());  // (a chunk holds rows of one class, run_batch_rows)
         // The four pricers only read the row blocks and write columns of their own, so two of them run on a second stream beside the
         // other two, forked and joined by events: LSM + MartingaleOptimization (one wavefront per row walking its dates; chains of
         // dependent loads: 0.79 / 0.42 VALU busy at 20 000 rows) beside AsymptoticAnalysis + BranchingProcesses (0.53 / 0.85) -- one
@@ -538,15 +618,10 @@ static int run_batch_chunk(mcg_ctx* ctx, std::vector<BatchRow>& h, BatchArgs a, 
                 aux = ctx->batch_aux;
         }
         const hipStream_t s_asym = aux_mode == 2 ? ctx->stream : aux, s_lsm = aux_mode == 2 ? aux : ctx->stream;
-        hipLaunchKernelGGL(k_batch_asym, dim3((unsigned)n), dim3(256), 2 * smem_c, s_asym, a);
-        hipLaunchKernelGGL(k_batch_branching, dim3((unsigned)n), dim3(256), smem_c, ctx->stream, a);
-        switch (poly_order + 1) {
-            case 1: launch_row_regressions<1>(a, smem_c, s_lsm, aux); break;
-            case 2: launch_row_regressions<2>(a, smem_c, s_lsm, aux); break;
-            case 3: launch_row_regressions<3>(a, smem_c, s_lsm, aux); break;
-            case 4: launch_row_regressions<4>(a, smem_c, s_lsm, aux); break;
-            default: launch_row_regressions<5>(a, smem_c, s_lsm, aux); break;
-        }
+        launch_row_asym(s_asym, a);
+        launch_row_branching(ctx->stream, a);
+        launch_row_lsm(s_lsm, a, poly_order);
+        launch_row_martingale(aux, a, poly_order);
         if (aux != ctx->stream) {   // join: nothing behind this point on the main stream starts before the auxiliary stream's kernels are done
             if (hipEventRecord(ctx->batch_join, aux) != hipSuccess || hipStreamWaitEvent(ctx->stream, ctx->batch_join, 0) != hipSuccess) {
                 (void)hipGetLastError();
@@ -618,7 +693,7 @@ bool batch_row_valid(const mcg_row& s) {
 // A row longer than the row kernels' LDS tables reach (more than four years of trading days), or any row of a call
 // with more than 256 paths per row or an order above 4, is priced after the batch through the single-contract
 // entry points, on the same Philox path ids: never refused, never answered with zeros.
-bool batch_row_singly(const mcg_row& s, int n_paths, int poly_order) { return s.n_steps > BATCH_MAX_STEPS || n_paths > 256 || poly_order > 4; }
+bool batch_row_singly(const mcg_row& s, int n_paths, int poly_order) { return s.n_steps > BATCH_MAX_STEPS || n_paths > BATCH_LD || poly_order > 4; }
 
 int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_paths, double r, double dt, int num_branches,
                    int poly_order, int max_iterations, uint64_t seed, double* out, unsigned char* priced) {
@@ -637,9 +712,7 @@ int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_path
             long_rows.push_back(i);
             continue;
         }
-        int M = 1;
-        while (M < s.n_steps) M <<= 1;
-        cls[lds_class(M)].push_back(i);
+        cls[lds_class(batch_next_pow2(s.n_steps))].push_back(i);
     }
 #ifdef MCG_BATCH_TRACE
     const auto bt1 = BT_NOW();
@@ -668,10 +741,9 @@ int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_path
             size_t used = 0, w = 0;
             while (ch.end < cls[c].size()) {
                 const mcg_row& s = rows[cls[c][ch.end]];
-                int M = 1;
-                while (M < s.n_steps) M <<= 1;
+                const int M = batch_next_pow2(s.n_steps);
                 const size_t need = row_workspace_bytes(s.n_steps, M);
-                if (ch.end > ch.begin && (used + need > budget || ch.end - ch.begin >= ((size_t)1 << 24))) break;  // (k_batch_paths' workgroup map holds the chunk-local row in 26 bits)
+                if (ch.end > ch.begin && (used + need > budget || ch.end - ch.begin >= BATCH_CHUNK_MAX_ROWS)) break;
                 used += need;
                 ch.bytes_S += (size_t)BATCH_LD * (size_t)(s.n_steps + 1) * sizeof(double);
                 w += (size_t)M + (size_t)s.n_steps;
@@ -719,26 +791,7 @@ int run_batch_rows(mcg_ctx* ctx, const mcg_row* rows, int64_t n_rows, int n_path
             h.reserve(ch.end - ch.begin);
             for (size_t k = ch.begin; k < ch.end; ++k) {
                 const int64_t i = cls[ch.c][k];
-                const mcg_row& s = rows[i];
-                BatchRow d{};
-                d.S0 = s.S0;
-                d.logS0 = std::log(s.S0);
-                d.xi = s.xi;
-                d.H = s.H;
-                d.eta = s.eta;
-                d.strike = s.strike;
-                d.maturity = s.maturity;
-                d.sigma = s.sigma;
-                d.dividend = s.dividend;
-                d.id = (uint64_t)i;
-                d.k0 = a.k0;
-                d.k1 = a.k1;
-                d.n_steps = s.n_steps;
-                d.is_call = s.is_call;
-                d.valid = 1;
-                d.M = 1;
-                while (d.M < d.n_steps) d.M <<= 1;
-                h.push_back(d);
+                h.push_back(batch_row_image(rows[i], (uint64_t)i, seed, std::log(rows[i].S0)));  // the call's key, the row's index as its Philox id
             }
 #ifdef MCG_BATCH_TRACE
             const auto bc1 = BT_NOW();
@@ -844,18 +897,16 @@ namespace {
 struct Key {  // what the requests of one launch must share
     int kind, n_paths, cls, a, b;
     double r, dt;
-    bool operator==(const Key& o) const {
-        return kind == o.kind && n_paths == o.n_paths && cls == o.cls && a == o.a && b == o.b && r == o.r && dt == o.dt;
+    // r and dt are compared by bit pattern: a total order whatever a caller hands in (a NaN would make the round's sort undefined for
+    // every thread in it); +0.0 and -0.0 are then two groups, which moves a request to another launch and leaves its price alone
+    static uint64_t bits(double x) {
+        uint64_t u;
+        std::memcpy(&u, &x, sizeof u);
+        return u;
     }
-    bool operator<(const Key& o) const {
-        if (kind != o.kind) return kind < o.kind;
-        if (n_paths != o.n_paths) return n_paths < o.n_paths;
-        if (cls != o.cls) return cls < o.cls;
-        if (a != o.a) return a < o.a;
-        if (b != o.b) return b < o.b;
-        if (r != o.r) return r < o.r;
-        return dt < o.dt;
-    }
+    std::tuple<int, int, int, int, int, uint64_t, uint64_t> tied() const { return {kind, n_paths, cls, a, b, bits(r), bits(dt)}; }
+    bool operator==(const Key& o) const { return tied() == o.tied(); }
+    bool operator<(const Key& o) const { return tied() < o.tied(); }
 };
 
 Key key_of(const Request& q) {
@@ -895,15 +946,6 @@ int grow(RoundBuffers& rb, size_t bytes, size_t n_req) {
     return MCG_OK;
 }
 
-template <int NB>
-void launch_lsm_rows(mcg_ctx* ctx, const BatchArgs& a) {
-    hipLaunchKernelGGL(k_batch_lsm<NB>, dim3((unsigned)a.n_rows), dim3(64), 0, ctx->stream, a);
-}
-template <int NB>
-void launch_martingale_rows(mcg_ctx* ctx, const BatchArgs& a, size_t smem_c) {
-    hipLaunchKernelGGL(k_batch_martingale<NB>, dim3((unsigned)a.n_rows), dim3(256), smem_c, ctx->stream, a);
-}
-
 int run_round(mcg_ctx* ctx, RoundBuffers& rb, double* arena_base, Request** reqs, int n) {
     const auto t_begin = std::chrono::steady_clock::now();
     MCG_HIP(hipSetDevice(ctx->device));
@@ -921,8 +963,7 @@ int run_round(mcg_ctx* ctx, RoundBuffers& rb, double* arena_base, Request** reqs
         const Request& q = *reqs[i];
         if (q.kind == GEN) {
             w_doubles += (size_t)q.M + (size_t)q.n_steps;
-            const int ppb = rb_pairs_per_block(q.M);
-            n_map += (size_t)(((q.n_paths + 1) / 2 + ppb - 1) / ppb);
+            n_map += (size_t)batch_row_shares(q.n_paths, q.M);
             ++n_gen;
         } else if (q.upload) {
             ++n_up;
@@ -961,25 +1002,10 @@ int run_round(mcg_ctx* ctx, RoundBuffers& rb, double* arena_base, Request** reqs
         if (groups.empty() || !(groups.back().key == k)) groups.push_back(Group{k, pos, pos, mpos, 0, 1, 1});
         Group& g = groups.back();
         g.end = pos + 1;
-        BatchRow d{};
-        d.S0 = q.S0;
-        d.logS0 = q.kind == GEN ? std::log(q.S0) : 0.0;
-        d.xi = q.xi;
-        d.H = q.H;
-        d.eta = q.eta;
-        d.strike = q.strike;
-        d.maturity = q.maturity;
-        d.sigma = q.sigma;
-        d.dividend = q.dividend;
+        // the row's own key; Philox path ids 0 .. n_paths - 1: what mcg_paths_rbergomi / mcg_price_branching use for a matrix that begins
+        // at path 0; only a matrix still to be generated needs log(S0)
+        BatchRow d = batch_row_image(q, 0, q.seed, q.kind == GEN ? std::log(q.S0) : 0.0);
         d.off = q.slot_off;
-        d.id = 0;  // Philox path ids 0 .. n_paths - 1: what mcg_paths_rbergomi / mcg_price_branching use for a matrix that begins at path 0
-        d.k0 = (uint32_t)q.seed;
-        d.k1 = (uint32_t)(q.seed >> 32);
-        d.n_steps = q.n_steps;
-        d.is_call = q.is_call;
-        d.valid = 1;
-        d.M = 1;
-        while (d.M < d.n_steps) d.M <<= 1;
         g.max_steps = std::max(g.max_steps, d.n_steps);
         g.m_max = std::max(g.m_max, d.M);
         const int n_cols = q.n_steps + 1;
@@ -988,9 +1014,8 @@ int run_round(mcg_ctx* ctx, RoundBuffers& rb, double* arena_base, Request** reqs
             std::memcpy(h_w + woff, q.amp, sizeof(double) * (size_t)q.M);
             std::memcpy(h_w + woff + q.M, q.comp, sizeof(double) * (size_t)q.n_steps);
             woff += (size_t)q.M + (size_t)q.n_steps;
-            const int ppb = rb_pairs_per_block(q.M);
-            const int shares = ((q.n_paths + 1) / 2 + ppb - 1) / ppb;
-            for (int sub = 0; sub < shares; ++sub) h_map[mpos++] = ((uint32_t)(pos - g.begin) << 6) | (uint32_t)sub;
+            const int shares = batch_row_shares(q.n_paths, q.M);
+            for (int sub = 0; sub < shares; ++sub) h_map[mpos++] = batch_wg_entry(pos - g.begin, sub);
             g.map_n += (size_t)shares;
             h_x[xg++] = Xfer{q.slot_off, q.host_dev, q.n_paths, n_cols};
             gen_tiles = std::max(gen_tiles, (n_cols + CO_TILE - 1) / CO_TILE);
@@ -1022,38 +1047,12 @@ int run_round(mcg_ctx* ctx, RoundBuffers& rb, double* arena_base, Request** reqs
         a.wg_map = d_map + g.map_begin;
         a.num_branches = g.key.a;
         a.max_iterations = g.key.b == 1 ? 1 : 5;
-        const size_t smem_c = ((size_t)g.max_steps + 1) * sizeof(double);
         switch (g.key.kind) {
-            case GEN: {
-                size_t smem_p = 0;
-                for (int m = 1; m <= g.m_max; m <<= 1) smem_p = std::max(smem_p, rb_smem_bytes(m, std::min(m, g.max_steps)));
-                typedef void (*PathsKernel)(BatchArgs);
-                static const PathsKernel paths_kernel[N_LDS_CLASSES] = {k_batch_paths<0>, k_batch_paths<1>, k_batch_paths<2>, k_batch_paths<3>};
-                const PathsKernel pk = paths_kernel[g.key.cls];
-                if (smem_p > 48 * 1024) (void)hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_p);
-                hipLaunchKernelGGL(pk, dim3((unsigned)g.map_n), dim3(256), smem_p, ctx->stream, a);
-                break;
-            }
-            case ASYM: hipLaunchKernelGGL(k_batch_asym, dim3((unsigned)a.n_rows), dim3(256), 2 * smem_c, ctx->stream, a); break;
-            case BRANCH: hipLaunchKernelGGL(k_batch_branching, dim3((unsigned)a.n_rows), dim3(256), smem_c, ctx->stream, a); break;
-            case LSM:
-                switch (g.key.a + 1) {
-                    case 1: launch_lsm_rows<1>(ctx, a); break;
-                    case 2: launch_lsm_rows<2>(ctx, a); break;
-                    case 3: launch_lsm_rows<3>(ctx, a); break;
-                    case 4: launch_lsm_rows<4>(ctx, a); break;
-                    default: launch_lsm_rows<5>(ctx, a); break;
-                }
-                break;
-            default:
-                switch (g.key.a + 1) {
-                    case 1: launch_martingale_rows<1>(ctx, a, smem_c); break;
-                    case 2: launch_martingale_rows<2>(ctx, a, smem_c); break;
-                    case 3: launch_martingale_rows<3>(ctx, a, smem_c); break;
-                    case 4: launch_martingale_rows<4>(ctx, a, smem_c); break;
-                    default: launch_martingale_rows<5>(ctx, a, smem_c); break;
-                }
-                break;
+            case GEN: launch_row_paths(ctx->stream, a, g.key.cls, g.map_n); break;
+            case ASYM: launch_row_asym(ctx->stream, a); break;
+            case BRANCH: launch_row_branching(ctx->stream, a); break;
+            case LSM: launch_row_lsm(ctx->stream, a, g.key.a); break;
+            default: launch_row_martingale(ctx->stream, a, g.key.a); break;
         }
     }
     if (n_gen) hipLaunchKernelGGL(k_co_gather, dim3((unsigned)(n_gen * (size_t)gen_tiles)), dim3(256), 0, ctx->stream, d_x, (const double*)arena_base, gen_tiles);

@@ -52,9 +52,9 @@ struct RbArgs {
 #ifndef RB_LT_DEFAULT
 #define RB_LT_DEFAULT 2
 #endif
-__host__ __device__ inline int rb_log_tiles(int M) { return M > (64 * 4 << RB_LT_DEFAULT) ? 3 : RB_LT_DEFAULT; }
+__host__ __device__ constexpr int rb_log_tiles(int M) { return M > (64 * 4 << RB_LT_DEFAULT) ? 3 : RB_LT_DEFAULT; }
 // pairs handled by one 256-thread workgroup of the variant chosen for Mz
-__host__ __device__ inline int rb_pairs_per_block(int M) { return M < 32 ? 256 : 4 * (64 / (M >> (2 + rb_log_tiles(M)))); }
+__host__ __device__ constexpr int rb_pairs_per_block(int M) { return M < 32 ? 256 : 4 * (64 / (M >> (2 + rb_log_tiles(M)))); }
 
 // Output staging (FFT variants): one 4G-step tile of the workgroup's pairs, [4G rows][pairs + 1 pad] double2,
 // double-buffered while LDS allows (LT = 2), so that the step-major rows leave as (pairs * 16)-byte runs

@@ -11,6 +11,8 @@ case is well conditioned are in tests/test_batch_rows_reference.py (CPU).
 (d) the row kernels on uploaded matrices through the class API (coalesced_fallbacks == 0), against the oracle; and, as a
     second check, the same calls with coalescing off (the single-contract kernels) against the row kernels.
 (e) the error paths of the dump hook.
+(f) the two hosts of the row kernels (mcg_batch_price_rows and the class API's coalesced calls) on the same dumped blocks,
+    one row per LDS class: byte-equal prices.
 
 A price error is |got - want| / K (MartingaleOptimization's price is ~1e-16 where nothing is ever in the money: an error
 relative to the price means nothing there).  Each bound is ten times the largest error observed on an MI355X against the
@@ -51,9 +53,9 @@ import pytest
 import montecarlooptionspricer_amd as mc
 from montecarlooptionspricer_amd.engine import make_rows
 from oracle.binding import Oracle
-from test_batch_rows_reference import (BOUNDS, D_SEED, DT, PATH_CALLS, R, SEED64, class_api_cases, column_of, four_columns,
-                                       oracle_four, oracle_price, path_rows, pricer_calls, spectrum_errors, degenerate_cases,
-                                       weight_rows)
+from test_batch_rows_reference import (BOUNDS, D_SEED, DT, H_ETA, PATH_CALLS, R, SEED64, class_api_cases, column_of, four_columns,
+                                       lds_class, next_pow2, oracle_four, oracle_price, path_rows, pricer_calls, row,
+                                       spectrum_errors, degenerate_cases, weight_rows)
 
 pytestmark = pytest.mark.gpu
 
@@ -208,6 +210,51 @@ def test_row_kernels_through_the_class_api(orc, kind):
         mc.set_compat_seed(None)
     errs.settle()
     errs2.settle()
+
+
+@pytest.mark.parametrize("n_paths", [2, 250])
+def test_both_hosts_drive_the_kernels_alike(eng, n_paths):
+    """The row kernels have two hosts: run_batch_chunk (mcg_batch_price_rows) and co::run_round (the class API's coalesced
+    calls), which share one launch function per kernel.  One call of four rows, one per LDS class (31, 200, 500 and 1020 steps);
+    each row's dumped block goes path-major to the class API with the row's own arguments.  AsymptoticAnalysis, LSM (order 2)
+    and MartingaleOptimization (order 2, 5 iterations) draw nothing: both hosts launch the same kernel on the same doubles, so
+    the prices must be byte-equal to columns 0, 2 and 3 of the batch call.  BranchingProcesses draws with the Philox id
+    (row << 32) + path in the batch and with path ids 0 .. n_paths - 1 through the class API: row 0 is the one row whose ids
+    agree, and set_compat_seed gives the class API the batch call's key, so column 1 of row 0 is compared as well.
+    On the commit before the launch functions existed every one of these 26 prices was byte-equal too."""
+    steps_list = (31, 200, 500, 1020)
+    rows = [row(s, *H_ETA[i], strike=(95.0, 100.0, 104.0, 99.0)[i], maturity=(1.0, 0.69, 1.5, 1.0)[i] * s * DT, is_call=i % 2,
+                s0=96.0 + 2.0 * i, xi=0.04 + 0.02 * i) for i, s in enumerate(steps_list)]
+    assert [lds_class(next_pow2(d["n_steps"])) for d in rows] == [0, 1, 2, 3]
+    arr = make_rows(rows)
+    kw = dict(n_paths=n_paths, num_branches=10, poly_order=2, max_iterations=5, seed=SEED64, **BATCH)
+    plain = eng.batch_price_rows(arr, **kw)
+    assert np.isfinite(plain).all()
+    differ, calls = [], 0
+    mc.set_compat_seed(SEED64)
+    try:
+        mc.stats(reset=True)
+        for i, d in enumerate(rows):
+            out, amp, comp, block = eng.debug_batch_row_dump(arr, i, **kw)
+            assert bits(out) == bits(plain), i
+            matrix = np.ascontiguousarray(block.T)
+            assert matrix.shape == (n_paths, d["n_steps"] + 1)
+            a = (matrix, R, d["strike"], d["maturity"], DT, bool(d["is_call"]))
+            got = {0: mc.AsymptoticAnalysis().PredictOptionPrice(*a, d["sigma"], d["dividend"]),
+                   2: mc.LSM().PredictOptionPrice(*a, 2),
+                   3: mc.MartingaleOptimization().PredictOptionPrice(*a, 2, 5)}
+            if i == 0:
+                got[1] = mc.BranchingProcesses().PredictOptionPrice(*a, 10, list(range(d["n_steps"])))
+            calls += len(got)
+            for col, g in sorted(got.items()):
+                print(f"\nn_paths {n_paths} row {i} ({d['n_steps']} steps) column {col}: class API {g!r}, batch {float(plain[i][col])!r}", end="")
+                if bits(g) != bits(plain[i][col]):
+                    differ.append((i, col, g, float(plain[i][col])))
+        s = mc.stats()
+    finally:
+        mc.set_compat_seed(None)
+    assert s["coalesced_fallbacks"] == 0 and s["coalesced_calls"] >= calls, s
+    assert calls == 13 and not differ, differ
 
 
 def test_dump_hook_error_paths(eng):

@@ -895,6 +895,65 @@ int mcg_gbm_twin_stats(mcg_ctx* ctx, const mcg_gbm_twin* twin, int n_steps, int 
 int mcg_gbm_expectation(const mcg_control* c, double S0, double r, double q, double sigma, double dt,
         int n_steps, int first_row, double* mean);
 
+/* ---- multilevel Monte Carlo for local volatility ------------------------------------------------ */
+/* Multilevel Monte Carlo (Giles 2008) trades steps against paths: E P_L = E P_0 + sum_{l=1..L} E (P_l - P_{l-1}), each difference
+ * taken on a fine and a coarse path built from the SAME Brownian path, so that its variance falls with the step and nearly all
+ * paths run on the coarsest grids.  mcg_mlmc_localvol_level is one level in one launch: both paths in registers, reduced to
+ * the five statistics of mcg_path_stats, the book of mcg_price_exotics on them.  No matrix is stored.
+ *
+ * The fine path is mcg_paths_localvol's at (dt_f = T / n_fine, n_fine), step for step: the table mcg_localvol_table(dt_f,
+ * n_fine), the same step, z_n = draw n of Philox stream 0 of (seed, path_begin + p).
+ * The coarse path (has_coarse; n_fine even): n_coarse = n_fine / 2, dt_c = 2 * dt_f, m_c = (r - q) * dt_c, X_0 = 0, S_0 = S0;
+ * its table is mcg_localvol_table(dt_c, n_coarse), slice k at t = k * dt_c; its draw k is (z_{2k} + z_{2k+1}) * sqrt(0.5) -- that
+ * one addition and one multiplication -- and the step is mcg_paths_localvol's.
+ * Monitoring: the fine rows k * stride_fine and the coarse rows k * stride_coarse, k = first_obs (0 or 1) .. n / stride.
+ * stride_fine = 2 * stride_coarse monitors the same dates on both grids; stride_fine = stride_coarse = 1 each grid's own rows
+ * (the continuous limit).  Per grid, over its monitored rows, in mcg_path_stats' layout and meaning: S_T; A = mean S summed in
+ * row order; G = S0 exp(mean X) as the GBM twin computes it; min and max as fmin / fmax of the S values themselves.
+ *   stats10[q * n_paths + p], q = 0..4 the fine grid's, q = 5..9 the coarse one's; without a coarse path five rows.
+ * The book: P_f and P_c are a contract's payoff (mcg_price_exotics) on the fine and the coarse statistics, Y = P_f - P_c;
+ * without a coarse path P_c = 0 and Y = P_f.  Taken in a fixed order with no floating-point atomics:
+ *   sums[6c + k] = {sum Y, sum Y^2, sum P_f, sum P_f^2, sum P_c, sum P_c^2},   sums[6 n_contracts] = n_paths
+ * A contract's sums do not depend on the rest of the book or on where it stands.  A path depends on (seed, path_begin + p)
+ * only: the stats10 of shards are the one-call matrix's columns bit for bit, repeated calls are bit-identical, path_begin may be
+ * odd or beyond 2^32.  Sums of shards ADD UP to the one-call sums (to rounding); no all-reduce takes place inside the call, also
+ * on a ctx with a collective.  Three launches: the level kernel booked under MCG_K_LOCALVOL, the book kernel and its reduction
+ * under MCG_K_EXOTIC.
+ * MCG_ERR_INVALID with a message and nothing left allocated: everything mcg_paths_localvol (at dt_f, n_fine) and
+ * mcg_price_exotics reject; a NULL lv, book or sums; a non-finite T or T <= 0; n_fine < 1; a coarse path with an odd n_fine; a
+ * stride < 1 or one that does not divide its grid (stride_coarse is not read without a coarse path); first_obs outside {0, 1}.
+ * n_paths < 1 is MCG_ERR_EMPTY_PATHS.
+ *
+ * mcg_mlmc_combine (host only, binary64, no fused multiply-add), levels l = 0 .. n_levels - 1 in this order:
+ *   m_l = sum_y[l] / n[l];   V_l = max((sum_y2[l] - n[l] * m_l * m_l) / (n[l] - 1), 0), and 0 at n[l] = 1
+ *   price = e^{-rT} sum_l m_l;   std_err = e^{-rT} sqrt(sum_l V_l / n[l])
+ * mcg_mlmc_plan (host only, likewise), from per-level n, mean = m_l, var = V_l, cost C_l (path-steps a path: n_fine + n_coarse)
+ * and a target eps:
+ *   n_opt[l] = ceil((2 / (eps * eps)) * sqrt(V_l / C_l) * sum_k sqrt(V_k * C_k))                              (Giles' rule)
+ *   alpha = minus the least-squares slope of log2 |m_l| on l over the levels l >= 1 with m_l != 0, clamped to [0.5, 2];
+ *           1 where fewer than two such levels exist
+ *   bias = max(|m_L|, |m_{L-1}| / 2^alpha) / (2^alpha - 1), L = n_levels - 1; the second term only for L >= 2 (level 0 is no
+ *          difference); infinite for n_levels = 1
+ *   converged = bias < eps / sqrt(2)
+ * Rules (MCG_ERR_INVALID): a NULL array; n_levels outside [1, MCG_MLMC_MAX_LEVELS]; an n[l] < 1; a non-finite r, T, mean or eps;
+ * eps <= 0; a negative or non-finite var; a cost that is not positive and finite.
+ * Out of scope: Heston, Bates, rBergomi and multi-asset levels; Sobol' levels; antithetic or conditional (bridge) couplings for
+ * barriers; Greeks; an all-reduce inside the call; the batched rows, the coalescing layer and the drop-in classes. */
+#define MCG_MLMC_MAX_LEVELS 32
+typedef struct mcg_mlmc_level { uint64_t seed; int n_fine; int has_coarse; int stride_fine, stride_coarse; int first_obs;
+                                uint64_t path_begin; int64_t n_paths; } mcg_mlmc_level;
+
+int mcg_mlmc_localvol_level(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max,
+                            int n_x, const double* sigma, double T, const mcg_mlmc_level* lv, const mcg_exotic* book,
+                            int n_contracts /* 1..1024 */, double* sums /* 6 n_contracts + 1: then n_paths */,
+                            double* host_stats10 /* NULL, or [10 or 5][n_paths] */);
+/* host only; std_err may be NULL */
+int mcg_mlmc_combine(const double* sum_y, const double* sum_y2, const double* n, int n_levels, double r, double T,
+                     double* price, double* std_err);
+/* host only; alpha, bias, converged may be NULL */
+int mcg_mlmc_plan(const double* n, const double* mean, const double* var, const double* cost, int n_levels, double eps,
+                  double* n_opt /* [n_levels] */, double* alpha, double* bias, int* converged);
+
 /* ---- notes on an observation schedule: autocallables and cliquets ------------------------------ */
 /* mcg_price_scheduled prices a book of structured notes whose payoff is a small state machine walked over a few dates of the
  * matrix ("called yet?", "coupons missed so far", "knocked in?", "last reset level"): no function of the five statistics above.

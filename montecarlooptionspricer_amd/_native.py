@@ -122,6 +122,15 @@ class GbmTwin(C.Structure):
                 ("dt", C.c_double), ("path_begin", C.c_uint64)]
 
 
+MLMC_MAX_LEVELS = 32  # MCG_MLMC_MAX_LEVELS
+
+
+class MlmcLevel(C.Structure):
+    """mcg_mlmc_level (include/mcgpu.h): the shape, the monitoring and the paths of one multilevel level."""
+    _fields_ = [("seed", C.c_uint64), ("n_fine", C.c_int), ("has_coarse", C.c_int), ("stride_fine", C.c_int), ("stride_coarse", C.c_int),
+                ("first_obs", C.c_int), ("path_begin", C.c_uint64), ("n_paths", C.c_int64)]
+
+
 class Obs(C.Structure):
     """mcg_obs (include/mcgpu.h): one date of an observation schedule."""
     _fields_ = [("row", C.c_int), ("flags", C.c_int)]
@@ -288,6 +297,10 @@ def load_library():
                                     C.POINTER(C.c_int32)])
     newer("mcg_gbm_twin_stats",[vp, C.POINTER(GbmTwin), C.c_int, C.c_int, C.c_int64, dp])
     newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
+    newer("mcg_mlmc_localvol_level", [vp, C.c_double, C.c_double, C.c_double, dp, C.c_int, C.c_double, C.c_double, C.c_int, dp, C.c_double,
+                                      C.POINTER(MlmcLevel), C.POINTER(Exotic), C.c_int, dp, dp])
+    newer("mcg_mlmc_combine", [dp, dp, dp, C.c_int, C.c_double, C.c_double, dp, dp])
+    newer("mcg_mlmc_plan", [dp, dp, dp, dp, C.c_int, C.c_double, dp, dp, dp, C.POINTER(C.c_int)])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_compat_asymptotic_price.argtypes = [dp, C.c_int64, C.c_int] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]
     L.mcg_price_martingale.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_int, C.c_int, dp, dp, dp]

@@ -411,5 +411,7 @@ int localvol_check_surface(const double* times, int n_t, int n_x, const double* 
 int localvol_check_model(double S0, double r, double q, double x_min, double x_max, bool payoff, double K);
 void localvol_fill_table(const double* times, int n_t, int n_x, const double* sigma, double dt, int n_steps, double* table);
 LocalVolScalars localvol_scalars(double r, double q, double x_min, double x_max, int n_x, double dt);
+// host/mlmc.cpp: what mcg_mlmc_localvol_level rejects of T and of a level's shape (kernels_mlmc.hip)
+int mlmc_check_level(const mcg_mlmc_level* lv, double T);
 
 }  // namespace mcg

@@ -604,6 +604,95 @@ class PathEngine:
                                            pp.ctypes.data_as(dp), ps.ctypes.data_as(dp), sums.ctypes.data_as(dp) if return_sums else None))
         return CvResult(price, se, beta, pp, ps, sums if return_sums else None)
 
+    def mlmc_level(self, seed: int, S0: float, r: float, surface: "LocalVolSurface", T: float, book, n_fine: int, n_paths: int,
+                   has_coarse: bool = True, stride_fine: int = 1, stride_coarse: int = 1, first_obs: int = 1, path_begin: int = 0,
+                   q: float = 0.0, return_stats: bool = False):
+        """One level of multilevel Monte Carlo under local volatility in one launch (mcg_mlmc_localvol_level): a fine path of
+        n_fine steps over [0, T] and, with has_coarse, a coarse one of n_fine / 2 steps from the same Brownian path, both reduced
+        to the five statistics of path_stats in registers; no matrix is stored.  Returns sums[6 n + 1] = {sum Y, sum Y^2,
+        sum P_f, sum P_f^2, sum P_c, sum P_c^2} per contract of `book` (Y = P_f - P_c), then the path count; with return_stats
+        (sums, stats10): [10][n_paths], the fine statistics then the coarse ones ([5][n_paths] without a coarse path)."""
+        arr = make_book(book)
+        n = len(arr)
+        dp = C.POINTER(C.c_double)
+        lv = N.MlmcLevel(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_fine), int(bool(has_coarse)), int(stride_fine), int(stride_coarse),
+                         int(first_obs), int(path_begin) & 0xFFFFFFFFFFFFFFFF, int(n_paths))
+        sums = np.empty(6 * n + 1)
+        stats = np.empty((10 if has_coarse else 5, max(int(n_paths), 0))) if return_stats else None
+        check(self._L.mcg_mlmc_localvol_level(self._ctx, S0, r, q, surface.times.ctypes.data_as(dp), surface.n_t, surface.x_min,
+                                              surface.x_max, surface.n_x, surface.sigma.ctypes.data_as(dp), T, C.byref(lv), arr, n,
+                                              sums.ctypes.data_as(dp), stats.ctypes.data_as(dp) if return_stats else None))
+        return (sums, stats) if return_stats else sums
+
+    def mlmc_local_vol(self, seed: int, S0: float, r: float, surface: "LocalVolSurface", T: float, book, eps: float, n0: int = 4,
+                       n_obs: Optional[int] = None, first_obs: int = 1, q: float = 0.0, n_pilot: int = 10_000, l_min: int = 2,
+                       l_max: int = 10) -> "MlmcResult":
+        """The multilevel estimator of a price_exotics book under local volatility, to a root-mean-square error of about eps
+        (undiscounted bias below eps / sqrt(2) by the estimate of mlmc_plan, variance eps^2 / 2 by Giles' rule).  Level l has
+        n0 2^l fine steps (level 0 no coarse path) and draws with the Philox key seed + l (mod 2^64); every level starts with
+        n_pilot paths, and further batches of a level continue at path_begin = paths already drawn, so the result is a function
+        of the arguments alone.  The path counts are those of the worst contract of the book.  Levels l_min + 1, ... are added
+        until every contract's bias test passes or l_max is reached (converged False then; no error).  n_obs None monitors each
+        grid's own rows; an integer monitors that many equidistant dates on every grid and must divide n0 / 2."""
+        n = len(book)
+        if not (eps > 0.0) or not math.isfinite(eps):
+            raise McgError("mlmc: eps must be finite and > 0", 1)
+        if n0 < 1 or n_pilot < 2 or l_min < 0 or l_max < l_min or l_max >= N.MLMC_MAX_LEVELS:
+            raise McgError(f"mlmc: needs n0 >= 1, n_pilot >= 2 and 0 <= l_min <= l_max < {N.MLMC_MAX_LEVELS}", 1)
+        if l_max > 0 and n0 % 2:
+            raise McgError(f"mlmc: n0 must be even (got {n0})", 1)
+        if n_obs is not None and (n_obs < 1 or n0 % 2 or (n0 // 2) % n_obs):
+            raise McgError(f"mlmc: n_obs must divide n0 / 2 (got n_obs = {n_obs}, n0 = {n0})", 1)
+        sums, paths = [], []           # per level: [n][6] sums, paths drawn
+
+        def draw(l, count):
+            n_fine = n0 << l
+            n_coarse = n_fine // 2
+            sf, sc = (1, 1) if n_obs is None else (n_fine // n_obs, max(n_coarse // n_obs, 1))
+            s = self.mlmc_level((seed + l) & 0xFFFFFFFFFFFFFFFF, S0, r, surface, T, book, n_fine, count, has_coarse=l > 0,
+                                stride_fine=sf, stride_coarse=sc, first_obs=first_obs, path_begin=paths[l], q=q)
+            sums[l] += s[:-1].reshape(n, 6)
+            paths[l] += count
+
+        def add_level():
+            sums.append(np.zeros((n, 6)))
+            paths.append(0)
+            draw(len(paths) - 1, n_pilot)
+
+        def table():
+            cnt = np.array(paths, dtype=np.float64)
+            mean = np.array([[sums[l][c, 0] / paths[l] for l in range(len(paths))] for c in range(n)])
+            var = np.array([[max((sums[l][c, 1] - paths[l] * mean[c, l] * mean[c, l]) / (paths[l] - 1.0), 0.0)
+                             for l in range(len(paths))] for c in range(n)])
+            cost = np.array([float((n0 << l) + ((n0 << l) // 2 if l else 0)) for l in range(len(paths))])
+            return cnt, mean, var, cost
+
+        for _ in range(l_min + 1):
+            add_level()
+        while True:
+            for _round in range(8):  # top the levels up to Giles' counts; the variances move as paths are added
+                cnt, mean, var, cost = table()
+                want = np.max([mlmc_plan(cnt, mean[c], var[c], cost, eps)[0] for c in range(n)], axis=0)
+                more = [int(want[l]) - paths[l] for l in range(len(paths))]
+                if max(more) <= 0:
+                    break
+                for l, m in enumerate(more):
+                    if m > 0:
+                        draw(l, m)
+            cnt, mean, var, cost = table()
+            plans = [mlmc_plan(cnt, mean[c], var[c], cost, eps) for c in range(n)]
+            bias = np.array([p[2] for p in plans])
+            converged = all(p[3] for p in plans)
+            if converged or len(paths) - 1 >= l_max:
+                break
+            add_level()
+        price, se = np.empty(n), np.empty(n)
+        for c in range(n):
+            price[c], se[c] = mlmc_combine([sums[l][c, 0] for l in range(len(paths))], [sums[l][c, 1] for l in range(len(paths))], cnt, r, T)
+        levels = [dict(n_fine=n0 << l, paths=paths[l], mean_y=mean[:, l].copy(), var_y=var[:, l].copy(),
+                       mean_pf=sums[l][:, 2] / paths[l], cost=cost[l]) for l in range(len(paths))]
+        return MlmcResult(price, se, levels, math.exp(-r * T) * bias, bool(converged), float(np.dot(cnt, cost)))
+
     def price_scheduled(self, paths: PathMatrix, r: float, dt: float, schedule, book, return_sums: bool = False,
                         return_hist: bool = False):
         """Autocallables and cliquets on an observation schedule (mcg_price_scheduled).  schedule: what schedule(...) takes;
@@ -996,6 +1085,47 @@ def rqmc_combine(estimates) -> Tuple[float, float]:
     mean, se = C.c_double(), C.c_double()
     check(L.mcg_rqmc_combine(e.ctypes.data_as(C.POINTER(C.c_double)), e.size, C.byref(mean), C.byref(se)))
     return mean.value, se.value
+
+
+def mlmc_combine(sum_y, sum_y2, n, r: float, T: float) -> Tuple[float, float]:
+    """(price, std_err) of a multilevel estimator from its per-level sums of Y and Y^2 and path counts (mcg_mlmc_combine; host
+    only): price = e^{-rT} sum_l mean Y_l, std_err = e^{-rT} sqrt(sum_l V_l / N_l) with V_l the unbiased sample variance."""
+    L = N.load_library()
+    a, b, c = _vec(sum_y), _vec(sum_y2), _vec(n)
+    if not (len(a) == len(b) == len(c)):
+        raise McgError("mlmc_combine: sum_y, sum_y2 and n hold one value per level", 1)
+    dp = C.POINTER(C.c_double)
+    price, se = C.c_double(), C.c_double()
+    check(L.mcg_mlmc_combine(a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), len(a), r, T, C.byref(price), C.byref(se)))
+    return price.value, se.value
+
+
+def mlmc_plan(n, mean, var, cost, eps: float):
+    """(n_opt[n_levels], alpha, bias, converged) of mcg_mlmc_plan (host only): Giles' path counts for the target eps from the
+    levels' variances and costs, the fitted weak rate, the estimate of the remaining (undiscounted) bias and whether it lies
+    below eps / sqrt(2)."""
+    L = N.load_library()
+    a, b, c, d = _vec(n), _vec(mean), _vec(var), _vec(cost)
+    if not (len(a) == len(b) == len(c) == len(d)):
+        raise McgError("mlmc_plan: n, mean, var and cost hold one value per level", 1)
+    dp = C.POINTER(C.c_double)
+    n_opt = np.empty(max(len(a), 1))
+    alpha, bias, conv = C.c_double(), C.c_double(), C.c_int()
+    check(L.mcg_mlmc_plan(a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), d.ctypes.data_as(dp), len(a), eps,
+                          n_opt.ctypes.data_as(dp), C.byref(alpha), C.byref(bias), C.byref(conv)))
+    return n_opt[:len(a)], alpha.value, bias.value, bool(conv.value)
+
+
+class MlmcResult(tuple):
+    """What mlmc_local_vol returns: (price[n], std_err[n]) as a pair, and as attributes the per-level table `levels` (dicts of
+    n_fine, paths, mean_y[n], var_y[n], mean_pf[n], cost in path-steps a path), bias_estimate[n] (discounted), converged and
+    cost, the total in path-steps."""
+
+    def __new__(cls, price, std_err, levels, bias_estimate, converged, cost):
+        self = super().__new__(cls, (price, std_err))
+        self.price, self.std_err, self.levels = price, std_err, levels
+        self.bias_estimate, self.converged, self.cost = bias_estimate, converged, cost
+        return self
 
 
 def make_rows(rows):

@@ -937,8 +937,9 @@ int mcg_gbm_expectation(const mcg_control* c, double S0, double r, double q, dou
  *   converged = bias < eps / sqrt(2)
  * Rules (MCG_ERR_INVALID): a NULL array; n_levels outside [1, MCG_MLMC_MAX_LEVELS]; an n[l] < 1; a non-finite r, T, mean or eps;
  * eps <= 0; a negative or non-finite var; a cost that is not positive and finite.
- * Out of scope: Heston, Bates, rBergomi and multi-asset levels; Sobol' levels; antithetic or conditional (bridge) couplings for
- * barriers; Greeks; an all-reduce inside the call; the batched rows, the coalescing layer and the drop-in classes. */
+ * Out of scope: Heston, Bates, rBergomi and multi-asset levels; Sobol' levels; antithetic couplings (the bridge coupling for
+ * barriers is mcg_mlmc_localvol_level_ex below); Greeks; an all-reduce inside the call; the batched rows, the coalescing layer
+ * and the drop-in classes. */
 #define MCG_MLMC_MAX_LEVELS 32
 typedef struct mcg_mlmc_level { uint64_t seed; int n_fine; int has_coarse; int stride_fine, stride_coarse; int first_obs;
                                 uint64_t path_begin; int64_t n_paths; } mcg_mlmc_level;
@@ -953,6 +954,53 @@ int mcg_mlmc_combine(const double* sum_y, const double* sum_y2, const double* n,
 /* host only; alpha, bias, converged may be NULL */
 int mcg_mlmc_plan(const double* n, const double* mean, const double* var, const double* cost, int n_levels, double eps,
                   double* n_opt /* [n_levels] */, double* alpha, double* bias, int* converged);
+
+/* ---- multilevel barriers: Milstein levels with a Brownian-bridge coupling ------------------------- */
+/* mcg_mlmc_localvol_level_ex is mcg_mlmc_localvol_level with two switches.  scheme = MCG_MLMC_LOG_EULER and bridge = 0 is that
+ * call: the same kernels, sums and stats10 bit for bit.  A discretely monitored barrier's level variance falls at rate 1/2
+ * only, and a scheme of strong order 1/2 keeps that rate under any coupling (Giles 2008, the Milstein paper); the two switches
+ * together lift it above 1, and level 0 with bridge = 1 is the plain continuously monitored barrier estimator under sigma(t, S)
+ * with no price or variance matrix stored.
+ *
+ * scheme = MCG_MLMC_MILSTEIN.  The lookup is mcg_paths_localvol's: u, j, f, {a_j, d_j}, s = fma(f, d_j, a_j).  Then
+ *   uu = fma(X, inv_dx, u0);   g = (uu > 0 && uu < n_x - 1) ? d_j * inv_dx : 0        (the surface is flat outside the grid)
+ *   e  = fma(s, z, fma(-0.5 * s, s, m));   e' = fma((0.5 * s) * g, fma(z, z, -1.0), e);   X += e';   S = scaled_exp(S, e')
+ * on the fine grid, and on the coarse one with its own table, drift and summed draw.  Where g = 0 (a flat surface) the path is
+ * the log-Euler path bit for bit.
+ *
+ * bridge = 1.  A level is (B, up) of a barrier contract of the book, compared bitwise, in the order of first appearance
+ * (mcg_mlmc_bridge_levels lists them); contracts with the same level share it; at most MCG_MLMC_BRIDGE_L_MAX a call.  A down
+ * barrier at exactly 0 is never touched: P = 1 by rule, no level (the EURO idiom: a down-and-out contract with B = 0 is the
+ * vanilla payoff).  Any other barrier <= 0 is rejected.  h = log(B / S0) is formed on the host in binary64; d = X - h.
+ * Survival along a grid: monitoring is continuous over [0, T] on EVERY step of the grid, whatever the strides and first_obs
+ * are (they govern the five statistics only).  A row is safe when d > 0 (down) or d < 0 (up); row 0 has X = 0.  P = 0 if a row
+ * is unsafe; otherwise P is the product, in ascending order, over the sub-intervals (a, b) of
+ *   1 - exp(max(d_a * d_b, 0) * (-2 / w)),            a sub-interval with w = 0 contributes 1
+ * Fine step n (and every step of a level without a coarse path): one sub-interval (X_n, X_n+1), w = s_n * s_n.
+ * Coarse step k, s_c its step volatility: the midpoint xm = fma(0.5 * s_c, (z_2k - z_2k+1) * sqrt(0.5), 0.5 * (X_k + X_k+1))
+ * is a row of its own (on the wrong side: P = 0), and the two sub-intervals (X_k, xm) and (xm, X_k+1) have w = 0.5 * (s_c * s_c)
+ * each.  z_2k - z_2k+1 is independent of the coarse increment z_2k + z_2k+1, so xm is a draw of the Brownian bridge between the
+ * coarse step's ends under its frozen volatility, and the conditional expectation of the two factors given the ends is the
+ * one-step factor 1 - exp(-2 d_k d_k+1 / (s_c * s_c)): E P_c(level l) = E P_f(level l - 1), the telescoping sum stays exact.
+ * Samples, f the vanilla payoff on the grid's own S_T: out contracts f P + rebate (1 - P), in contracts f (1 - P) + rebate P,
+ * as mcg_price_barriers_bridge forms them; a contract of another kind as mcg_mlmc_localvol_level; with bridge = 0 barrier
+ * contracts too.
+ *   surv[(g * n_levels + l) * n_paths + p]: P of level l on the fine grid (g = 0) and, with a coarse path, the coarse one (g = 1)
+ * Kept: a path depends on (seed, path_begin + p) only -- shards, repeats, an odd path_begin or one beyond 2^32 are bit-identical;
+ * a contract's sums do not depend on the rest of the book, a level's P not on the other levels.  An exponential is skipped
+ * where its argument is <= -38 on every lane of a wavefront: 1 - exp(x) is 1.0 there, no bit changes.  No float atomics.
+ * MCG_ERR_INVALID with a message: everything mcg_mlmc_localvol_level rejects; a scheme or a bridge flag outside {0, 1}; with
+ * bridge = 1 an up barrier <= 0, a down barrier < 0, more than MCG_MLMC_BRIDGE_L_MAX distinct levels.
+ * Out of scope: bridge-sampled minima and maxima for lookbacks; Asian couplings; double barriers; more levels a call. */
+#define MCG_MLMC_BRIDGE_L_MAX 4
+enum mcg_mlmc_scheme { MCG_MLMC_LOG_EULER = 0, MCG_MLMC_MILSTEIN = 1 };
+int mcg_mlmc_localvol_level_ex(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max,
+                               int n_x, const double* sigma, double T, const mcg_mlmc_level* lv, int scheme, int bridge,
+                               const mcg_exotic* book, int n_contracts /* 1..1024 */, double* sums /* 6 n_contracts + 1 */,
+                               double* host_stats10 /* NULL, or [10 or 5][n_paths] */,
+                               double* host_surv /* NULL, or [(1 or 2) * n_levels][n_paths]: fine levels, then coarse */);
+/* host only: the distinct levels of a book in the order the kernel holds them; barriers and is_up hold MCG_MLMC_BRIDGE_L_MAX */
+int mcg_mlmc_bridge_levels(const mcg_exotic* book, int n_contracts, double* barriers, int* is_up, int* n_levels);
 
 /* ---- notes on an observation schedule: autocallables and cliquets ------------------------------ */
 /* mcg_price_scheduled prices a book of structured notes whose payoff is a small state machine walked over a few dates of the

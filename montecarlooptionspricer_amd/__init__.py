@@ -17,7 +17,7 @@ from .engine import CvResult, control, exotics_cv_from_sums, gbm_expectation  # 
 from ._native import POL_CONTINUE, POL_EXERCISE_RULE, POL_TERMINAL  # noqa: F401
 from .engine import DualResult, LsmPolicy  # noqa: F401
 from .engine import LocalVolSurface, PathEngine, PathMatrix, cholesky_corr, estimate_params, exotic, local_vol_table, make_rows, rbergomi_spectrum, row_build, row_features, stats  # noqa: F401
-from .engine import MlmcResult, mlmc_combine, mlmc_plan  # noqa: F401
+from .engine import MlmcResult, mlmc_bridge_levels, mlmc_combine, mlmc_plan  # noqa: F401
 from .engine import Sobol, rqmc_combine, sobol_bridge, sobol_table  # noqa: F401
 from ._native import OBS_CALL, OBS_COUPON, OBS_KI, OBS_RESET, S_AUTOCALL, S_CLIQUET  # noqa: F401
 from .engine import autocall, cliquet, make_sched_book, schedule  # noqa: F401
@@ -32,4 +32,4 @@ __all__ = ["McgError", "PathEngine", "PathMatrix", "RoughVolatility", "LSM", "As
            "control", "gbm_expectation", "exotics_cv_from_sums", "CvResult", "LsmPolicy", "DualResult", "POL_CONTINUE", "POL_EXERCISE_RULE", "POL_TERMINAL", "CV_PAYOFF", "CV_VANILLA", "CV_ST", "CV_A", "CV_G",
            "Sobol", "sobol_table", "sobol_bridge", "rqmc_combine", "TANGENT_STATS", "BRIDGE_L_MAX", "BRIDGE_ROWS",
            "schedule", "autocall", "cliquet", "make_sched_book", "OBS_COUPON", "OBS_CALL", "OBS_KI", "OBS_RESET", "S_AUTOCALL", "S_CLIQUET",
-           "MlmcResult", "mlmc_plan", "mlmc_combine"]
+           "MlmcResult", "mlmc_plan", "mlmc_combine", "mlmc_bridge_levels"]

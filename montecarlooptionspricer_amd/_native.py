@@ -123,6 +123,8 @@ class GbmTwin(C.Structure):
 
 
 MLMC_MAX_LEVELS = 32  # MCG_MLMC_MAX_LEVELS
+MLMC_BRIDGE_L_MAX = 4  # MCG_MLMC_BRIDGE_L_MAX
+MLMC_SCHEMES = {"euler": 0, "milstein": 1}  # mcg_mlmc_scheme
 
 
 class MlmcLevel(C.Structure):
@@ -299,6 +301,9 @@ def load_library():
     newer("mcg_gbm_expectation", [C.POINTER(Control)] + [C.c_double] * 5 + [C.c_int, C.c_int, dp])
     newer("mcg_mlmc_localvol_level", [vp, C.c_double, C.c_double, C.c_double, dp, C.c_int, C.c_double, C.c_double, C.c_int, dp, C.c_double,
                                       C.POINTER(MlmcLevel), C.POINTER(Exotic), C.c_int, dp, dp])
+    newer("mcg_mlmc_localvol_level_ex", [vp, C.c_double, C.c_double, C.c_double, dp, C.c_int, C.c_double, C.c_double, C.c_int, dp, C.c_double,
+                                         C.POINTER(MlmcLevel), C.c_int, C.c_int, C.POINTER(Exotic), C.c_int, dp, dp, dp])
+    newer("mcg_mlmc_bridge_levels", [C.POINTER(Exotic), C.c_int, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)])
     newer("mcg_mlmc_combine", [dp, dp, dp, C.c_int, C.c_double, C.c_double, dp, dp])
     newer("mcg_mlmc_plan", [dp, dp, dp, dp, C.c_int, C.c_double, dp, dp, dp, C.POINTER(C.c_int)])
     L.mcg_price_asymptotic.argtypes = [vp, vp] + [C.c_double] * 4 + [C.c_int, C.c_double, C.c_double, dp]

@@ -3,6 +3,7 @@
 //   xs_load, xs_split, path_scan   the streaming scan that reduces a path to its statistics (k_path_stats, k_path_tangent_stats)
 //   lane_paths                     the entry of a kernel with one lane per W adjacent paths (those two and k_bridge_survival)
 //   exotic_payoff                  the payoff of one mcg_exotic contract on a path's five statistics
+//   bridge_payoff                  the sample of a barrier contract from S_T and a Brownian-bridge survival probability
 //   book_partials                  the frame of a book kernel: per-block partial sums of NF accumulators over the paths
 //   k_book_reduce                  the fixed-order reduction of a book kernel's partials into per-contract sums
 // Device-only code for gfx950.
@@ -235,6 +236,14 @@ __device__ __forceinline__ double exotic_payoff(const mcg_exotic& c, double st, 
             return hit == in ? payoff_of(call, st, c.K) : c.rebate;
         }
     }
+}
+
+// The sample of a barrier contract from a Brownian-bridge survival probability p (k_bridge_book, k_mlmc_book): the vanilla
+// payoff f on S_T weighted by p, the rebate by its complement; an in contract the other way round
+__device__ __forceinline__ double bridge_payoff(const mcg_exotic& c, double st, double p) {
+    const double f = payoff_of(c.is_call != 0, st, c.K), q = 1.0 - p;
+    const bool in = c.kind == MCG_X_BARRIER_UP_IN || c.kind == MCG_X_BARRIER_DOWN_IN;
+    return in ? f * q + c.rebate * p : f * p + c.rebate * q;
 }
 
 // The frame of a book kernel (256 lanes): NF accumulators from zero, per_path(i, e) for the paths i = this lane's place in

@@ -158,13 +158,6 @@ __global__ __launch_bounds__(256) void k_bridge_survival(const BridgeArgs a) {
     lane_paths<W>(a.n_paths, [&](int64_t p0, int64_t, auto w) { bridge_scan<VAR, NL, w.value>(a, p0); });
 }
 
-// Y of include/mcgpu.h: the vanilla payoff f on S_T weighted by the survival probability, the rebate by its complement
-__device__ __forceinline__ double bridge_payoff(const mcg_exotic& c, double st, double p) {
-    const double f = payoff_of(c.is_call != 0, st, c.K), q = 1.0 - p;
-    const bool in = c.kind == MCG_X_BARRIER_UP_IN || c.kind == MCG_X_BARRIER_DOWN_IN;
-    return in ? f * q + c.rebate * p : f * p + c.rebate * q;
-}
-
 // k_exotic_book's layout over the contracts [c_lo, c_hi) of one level group, in the order of BridgePlan::order: blockIdx.y
 // counts the chunks of XB_CH contracts from c_lo's chunk on, blockIdx.x strides over the paths (book_partials).  A chunk
 // that two groups share is visited by both launches; each writes the fields of its own contracts only (and the one that

@@ -1,6 +1,6 @@
-// Multilevel Monte Carlo for local volatility (include/mcgpu.h: mcg_mlmc_localvol_level).
+// Multilevel Monte Carlo for local volatility (include/mcgpu.h: mcg_mlmc_localvol_level, mcg_mlmc_localvol_level_ex).
 //
-// k_mlmc_localvol_level<COARSE, ONE_SLICE>   one level of the estimator in one launch, on the generators' skeleton of
+// k_mlmc_localvol_level<COARSE, ONE_SLICE, MILSTEIN, NL>   one level of the estimator in one launch, on the generators' skeleton of
 //                    paths_device.hpp (two adjacent paths per lane, fm::Tables in LDS, walk_blocks over the FINE steps): the fine
 //                    path is mcg_paths_localvol's at (T / n_fine, n_fine), step for step (localvol_step, draw n of stream 0); the
 //                    coarse path runs on n_fine / 2 steps of twice the length from the same Brownian path -- its draw k is
@@ -14,19 +14,30 @@
 //                    says why the LDS wait in front of that barrier is written out).
 //                    Issue-bound on the VALU like the generators' loops: per 8 fine path-steps (one Philox block of a lane) two
 //                    Philox blocks, two Box-Muller pairs, 8 + 4 surface steps with their exponentials.
+//                    MILSTEIN adds the correction of localvol_step_vol to both grids' steps (three FMAs and a select a step).
+//                    NL in {0, 1, 2, 4}: the Brownian-bridge survival probability of NL barrier levels along both grids, in
+//                    registers (per path, grid and level the distance d to the level at the last row and the running product;
+//                    per path and grid the extremes of X for the safe test): X and the step volatility are at hand, so a step
+//                    costs one fp64 division a path and grid, and per level a subtraction, three multiplies and -- unless every
+//                    lane of the wave is at or below ML_SKIP -- an exponential; a coarse step two of each, through its midpoint.
+//                    <.., false, 0> is the kernel of mcg_mlmc_localvol_level, instruction for instruction.
 // k_mlmc_book        the book on the statistics: per contract {sum Y, sum Y^2, sum P_f, sum P_f^2, sum P_c, sum P_c^2}, Y = P_f -
 //                    P_c, four contracts (24 accumulators) a workgroup on blockIdx.y, on book_partials, then
 //                    k_book_reduce<ML_CH, ML_NS> in a fixed order (both exotic_device.hpp's).  No float atomics.
+// k_mlmc_book_bridge  the same with a slot per contract: a barrier contract takes bridge_payoff on its level's P_f and P_c.
 // The host arithmetic on the sums (mcg_mlmc_combine, mcg_mlmc_plan) and what a level's shape must satisfy are host/mlmc.cpp.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "devmath.hpp"
 #include "exotic_device.hpp"
 #include "fastmath.hpp"
 #include "localvol_device.hpp"
+#include "../host/mlmc.hpp"
 #include "paths_host.hpp"
 #include "paths_device.hpp"
 
@@ -43,6 +54,10 @@ constexpr int ML_CH = 4;                             // contracts one workgroup 
 constexpr int ML_NS = 6;                             // sums per contract
 constexpr int ML_NF = ML_CH * ML_NS;
 constexpr double ML_SQRT_HALF = 0x1.6a09e667f3bcdp-1;  // sqrt(0.5) in binary64
+constexpr int ML_L_MAX = MCG_MLMC_BRIDGE_L_MAX;      // bridge levels a launch keeps in registers
+// x <= ML_SKIP: exp(x) < 2^-54, so 1 - exp(x) rounds to 1.0 and the factor changes no bit of the product (k_bridge_survival's rule)
+constexpr double ML_SKIP = -38.0;
+constexpr double ML_FLOOR = -64.0;
 
 struct MlmcArgs {
     LocalVolArgs f;         // the fine grid as k_localvol_paths takes it: n_steps = n_fine, m = (r - q) dt_f, surf = its table
@@ -53,6 +68,16 @@ struct MlmcArgs {
     int first_obs;          // 0: row 0 (S0) is monitored too
     double nd_f, nd_c;      // monitored rows per grid
 };
+// ... and the bridge levels of the instances with NL > 0 (the others take MlmcArgs as it was: their kernel arguments, too, are
+// those of mcg_mlmc_localvol_level's kernel): slot l < n_live is written, the slots behind repeat the last live one
+struct MlmcBridgeArgs : MlmcArgs {
+    double h[ML_L_MAX];     // ln(B / S0), formed on the host in binary64
+    unsigned up_mask;       // bit l: slot l is an up level
+    int n_live;
+    double* surv;           // [(1 or 2) n_live][n_paths]: the fine grid's levels, then the coarse one's
+};
+template <int NL>
+using MlmcArgsOf = std::conditional_t<NL == 0, MlmcArgs, MlmcBridgeArgs>;
 
 // One grid's path pair: the state of the step and the running statistics; `left`: rows until the next monitored one (wave-uniform)
 struct MlmcGrid {
@@ -60,9 +85,52 @@ struct MlmcGrid {
     int left;
 };
 
-template <bool COARSE, bool ONE_SLICE>
-__global__ __launch_bounds__(256) void k_mlmc_localvol_level(MlmcArgs g) {
+// One grid's survival state for NL levels: d at the last row and the running product per path and level, and the extremes of
+// X over the rows so far (row 0: X = 0; a coarse midpoint is a row).  Untouched, and so no register, where NL = 0.
+template <int NL>
+struct MlmcSurvival {
+    double dprev[ML_PPL][NL ? NL : 1], prod[ML_PPL][NL ? NL : 1], lo[ML_PPL], hi[ML_PPL];
+};
+
+// The sub-interval that ends in the row x of both paths, c = -2 / w: bridge_row's arithmetic (kernels_barrier_bridge.hip) on X
+// itself, no logarithm.  The exponent is held at ML_FLOOR from below, where the factor is 1.0 as everywhere below ML_SKIP: w = 0
+// gives c = -inf and an exponent of -inf or NaN, both end there (fmax returns its other operand for a NaN) -- factor 1, as
+// the contract says, with no flag kept.  The exponentials are exp_full2's: the polynomial of the step's scaled_exp, whose
+// constants the loop already holds in scalar registers.
+template <int NL>
+__device__ __forceinline__ void mlmc_bridge_row(const MlmcBridgeArgs& g, const double (&x)[ML_PPL], const double (&c)[ML_PPL],
+                                                MlmcSurvival<NL>& V) {
+#pragma unroll
+    for (int p = 0; p < ML_PPL; ++p) {
+        V.lo[p] = __builtin_fmin(V.lo[p], x[p]);
+        V.hi[p] = __builtin_fmax(V.hi[p], x[p]);
+    }
+#pragma unroll
+    for (int q = 0; q < NL; ++q) {
+        double t[ML_PPL];
+        bool live = false;
+#pragma unroll
+        for (int p = 0; p < ML_PPL; ++p) {
+            const double d = x[p] - g.h[q];
+            const double m = __builtin_fmax(V.dprev[p][q] * d, 0.0);
+            t[p] = __builtin_fmax(m * c[p], ML_FLOOR);
+            V.dprev[p][q] = d;
+            live = live || t[p] > ML_SKIP;
+        }
+        if (__builtin_amdgcn_ballot_w64(live) != 0ull) {  // (wave-uniform)
+            static_assert(ML_PPL == 2, "one exp_full2 a level");
+            double e[ML_PPL];
+            fm::exp_full2(t[0], t[1], e[0], e[1]);
+#pragma unroll
+            for (int p = 0; p < ML_PPL; ++p) V.prod[p][q] *= 1.0 - e[p];
+        }
+    }
+}
+
+template <bool COARSE, bool ONE_SLICE, bool MILSTEIN, int NL>
+__global__ __launch_bounds__(256) void k_mlmc_localvol_level(MlmcArgsOf<NL> g) {
     constexpr int PPL = ML_PPL;
+    constexpr bool PLAIN = !MILSTEIN && NL == 0;  // mcg_mlmc_localvol_level's kernel
     constexpr int STAGE = ML_FINE_STAGE + (COARSE ? ML_COARSE_STAGE : 0);
     __shared__ fm::Tables tabs;
     __shared__ double2 slices[ONE_SLICE ? (COARSE ? 2 : 1) * ML_SLICE_MAX : 2 * STAGE];
@@ -109,6 +177,18 @@ __global__ __launch_bounds__(256) void k_mlmc_localvol_level(MlmcArgs g) {
     }
     F.left = g.stride_f;
     C.left = g.stride_c;
+    MlmcSurvival<NL> VF, VC;
+    if constexpr (NL > 0) {
+#pragma unroll
+        for (int p = 0; p < PPL; ++p) {
+            VF.lo[p] = VF.hi[p] = VC.lo[p] = VC.hi[p] = 0.0;
+#pragma unroll
+            for (int q = 0; q < NL; ++q) {
+                VF.dprev[p][q] = VC.dprev[p][q] = 0.0 - g.h[q];
+                VF.prod[p][q] = VC.prod[p][q] = 1.0;
+            }
+        }
+    }
     // behind a step of grid G: its new row is monitored where its index is a multiple of the stride
     auto watch = [&](MlmcGrid& G, const int stride) {
         if (--G.left == 0) {  // (wave-uniform)
@@ -175,15 +255,40 @@ __global__ __launch_bounds__(256) void k_mlmc_localvol_level(MlmcArgs g) {
         [&](auto elem) {
             constexpr int k = decltype(elem)::value;
             const double2* sl = ONE_SLICE ? cur : cur + k * nx1;
+            if constexpr (PLAIN) {
 #pragma unroll
-            for (int p = 0; p < PPL; ++p) localvol_step(a, sl, (k & 1 ? zb : za)[p], F.S[p], F.X[p]);
+                for (int p = 0; p < PPL; ++p) localvol_step(a, sl, (k & 1 ? zb : za)[p], F.S[p], F.X[p]);
+            } else {  // the sub-interval (X_n, X_n+1) with w = s s
+                double cw[PPL];
+#pragma unroll
+                for (int p = 0; p < PPL; ++p) {
+                    const double s = localvol_step_vol<MILSTEIN>(a, sl, (k & 1 ? zb : za)[p], F.S[p], F.X[p]);
+                    cw[p] = -2.0 / (s * s);
+                }
+                if constexpr (NL > 0) mlmc_bridge_row<NL>(g, F.X, cw, VF);
+            }
             watch(F, g.stride_f);
             if constexpr (COARSE && (k & 1) != 0) {  // fine steps 2j and 2j + 1 are done: coarse step j on the sum of their draws
                 const double2* sc = ONE_SLICE ? slices + ML_SLICE_MAX : cur + ML_FINE_STAGE + (k >> 1) * nx1;
+                if constexpr (PLAIN) {
 #pragma unroll
-                for (int p = 0; p < PPL; ++p) {
-                    const double zc = (za[p] + zb[p]) * ML_SQRT_HALF;
-                    localvol_step(c, sc, zc, C.S[p], C.X[p]);
+                    for (int p = 0; p < PPL; ++p) {
+                        const double zc = (za[p] + zb[p]) * ML_SQRT_HALF;
+                        localvol_step(c, sc, zc, C.S[p], C.X[p]);
+                    }
+                } else {  // through the midpoint, drawn from the difference of the two draws: (X_k, xm) and (xm, X_k+1), w = s s / 2 each
+                    double cw[PPL], xm[PPL];
+#pragma unroll
+                    for (int p = 0; p < PPL; ++p) {
+                        const double zc = (za[p] + zb[p]) * ML_SQRT_HALF, x0 = C.X[p];
+                        const double s = localvol_step_vol<MILSTEIN>(c, sc, zc, C.S[p], C.X[p]);
+                        xm[p] = __builtin_fma(0.5 * s, (za[p] - zb[p]) * ML_SQRT_HALF, 0.5 * (x0 + C.X[p]));
+                        cw[p] = -2.0 / (0.5 * (s * s));
+                    }
+                    if constexpr (NL > 0) {
+                        mlmc_bridge_row<NL>(g, xm, cw, VC);
+                        mlmc_bridge_row<NL>(g, C.X, cw, VC);
+                    }
                 }
                 watch(C, g.stride_c);
             }
@@ -209,6 +314,21 @@ __global__ __launch_bounds__(256) void k_mlmc_localvol_level(MlmcArgs g) {
     };
     finish(F, g.nd_f, g.stats);
     if (COARSE) finish(C, g.nd_c, g.stats + ML_Q * n);
+    if constexpr (NL > 0) {  // P = 0 where a row was unsafe: the extremes of X against h, the complement of d > 0 (d < 0) on every row
+        auto survive = [&](const MlmcSurvival<NL>& V, double* out) {
+#pragma unroll
+            for (int p = 0; p < PPL; ++p) {
+                const int64_t col = i + p;
+#pragma unroll
+                for (int q = 0; q < NL; ++q) {
+                    const bool safe = ((g.up_mask >> q) & 1u) ? V.hi[p] < g.h[q] : V.lo[p] > g.h[q];
+                    if (col < n && q < g.n_live) out[(int64_t)q * n + col] = safe ? V.prod[p][q] : 0.0;
+                }
+            }
+        };
+        survive(VF, g.surv);
+        if (COARSE) survive(VC, g.surv + (int64_t)g.n_live * n);
+    }
 }
 
 // blockIdx.y: a chunk of ML_CH contracts; blockIdx.x strides over the paths.  stats: [10][n] with a coarse path, else [5][n].
@@ -247,13 +367,66 @@ __global__ __launch_bounds__(256) void k_mlmc_book(const double* stats, int64_t 
     });
 }
 
+// k_mlmc_book with bridge levels.  slot[c] >= 0: a barrier contract on level slot[c], surv[(grid * n_live + slot) * n + i] its
+// P (bridge_payoff); MLMC_SLOT_UNTOUCHED: a barrier never touched, P = 1; MLMC_SLOT_NONE: another kind, as k_mlmc_book.
+__global__ __launch_bounds__(256) void k_mlmc_book_bridge(const double* stats, const double* surv, int n_live, int64_t n, int has_coarse,
+                                                          const mcg_exotic* book, const int* slot, int n_contracts, double* partials) {
+    __shared__ double red[ML_NF * 4];
+    const int c0 = blockIdx.y * ML_CH;
+    const int live = min(ML_CH, n_contracts - c0);
+    book_partials<ML_NF>(n, red, partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * ML_NF, [&](int64_t i, double (&e)[ML_NF]) {
+        const double st = stats[i], A = stats[n + i], G = stats[2 * n + i], mn = stats[3 * n + i], mx = stats[4 * n + i];
+        double cst = 0.0, cA = 0.0, cG = 0.0, cmn = 0.0, cmx = 0.0;
+        if (has_coarse) {
+            const double* cs = stats + ML_Q * n;
+            cst = cs[i];
+            cA = cs[n + i];
+            cG = cs[2 * n + i];
+            cmn = cs[3 * n + i];
+            cmx = cs[4 * n + i];
+        }
+#pragma unroll
+        for (int q = 0; q < ML_CH; ++q) {
+            if (q < live) {
+                const mcg_exotic& x = book[c0 + q];
+                const int sl = slot[c0 + q];
+                double pf, pc = 0.0;
+                if (sl == MLMC_SLOT_NONE) {
+                    pf = exotic_payoff(x, st, A, G, mn, mx);
+                    if (has_coarse) pc = exotic_payoff(x, cst, cA, cG, cmn, cmx);
+                } else {
+                    pf = bridge_payoff(x, st, sl < 0 ? 1.0 : surv[(int64_t)sl * n + i]);
+                    if (has_coarse) pc = bridge_payoff(x, cst, sl < 0 ? 1.0 : surv[(int64_t)(n_live + sl) * n + i]);
+                }
+                const double y = pf - pc;
+                double* s = e + ML_NS * q;
+                s[0] += y;
+                s[1] = fma(y, y, s[1]);
+                s[2] += pf;
+                s[3] = fma(pf, pf, s[3]);
+                s[4] += pc;
+                s[5] = fma(pc, pc, s[5]);
+            }
+        }
+    });
+}
+
 // One level: the tables and the book go up, the level kernel fills the statistics, the book kernel and its reduction the sums.
-// Workspace (one pool buffer): [10 n or 5 n statistics][n_chunks * n_blocks * ML_NF partials][6 n_contracts + 1 sums].
-// Parameters (ctx->weights): [fine table][coarse table][book].  On an error the stream is synchronised before the workspace
+// Workspace (one pool buffer): [10 n or 5 n statistics][(2 or 1) n_live n survival probabilities][n_chunks * n_blocks * ML_NF
+// partials][6 n_contracts + 1 sums].  Parameters (ctx->weights): [fine table][coarse table][book][slots].  plan null: no
+// bridge (k_mlmc_book); otherwise its levels are the kernel's slots, padded to 1, 2 or 4 with the last one.  On an error the stream is synchronised before the workspace
 // goes back to the pool.
+// The bridge levels of a call (host/mlmc.hpp: mlmc_bridge_plan)
+struct MlmcBridgePlan {
+    double barrier[ML_L_MAX];
+    int up[ML_L_MAX];
+    int n_levels;
+    std::vector<int> slot;  // [n_contracts]
+};
+
 static int run_mlmc_level(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max, int n_x,
-                          const double* sigma, double T, const mcg_mlmc_level* lv, const mcg_exotic* book, int nc, double* sums,
-                          double* host_stats10) {
+                          const double* sigma, double T, const mcg_mlmc_level* lv, bool milstein, const MlmcBridgePlan* plan,
+                          const mcg_exotic* book, int nc, double* sums, double* host_stats10, double* host_surv) {
     const int64_t n = lv->n_paths;
     const bool coarse = lv->has_coarse != 0;
     const int n_fine = lv->n_fine, n_coarse = n_fine / 2;
@@ -270,19 +443,22 @@ static int run_mlmc_level(mcg_ctx* ctx, double S0, double r, double q, const dou
     const int n_q = coarse ? 2 * ML_Q : ML_Q;
     const int n_sums = ML_NS * nc + 1, n_chunks = (nc + ML_CH - 1) / ML_CH;
     const int n_blocks = book_blocks(ctx, n);
+    const int n_live = plan ? plan->n_levels : 0;
     const size_t n_stats = (size_t)n_q * n, n_part = (size_t)n_chunks * n_blocks * ML_NF;
-    const size_t ws_bytes = (n_stats + n_part + n_sums) * sizeof(double);
+    const size_t n_surv = (size_t)(coarse ? 2 : 1) * n_live * n;
+    const size_t ws_bytes = (n_stats + n_surv + n_part + n_sums) * sizeof(double);
     void* ws = nullptr;
     int rc = pool_alloc(ctx, ws_bytes, &ws);
     if (rc) return rc;
-    double *d_stats = (double*)ws, *d_part = d_stats + n_stats, *d_sums = d_part + n_part;
+    double *d_stats = (double*)ws, *d_surv = d_stats + n_stats, *d_part = d_surv + n_surv, *d_sums = d_part + n_part;
     auto body = [&]() -> int {
         HostPiece up[] = {{tab_f.data(), tab_f.size() * sizeof(double)},
                           {tab_c.data(), tab_c.size() * sizeof(double)},
-                          {book, (size_t)nc * sizeof(mcg_exotic)}};
+                          {book, (size_t)nc * sizeof(mcg_exotic)},
+                          {plan ? plan->slot.data() : nullptr, plan ? (size_t)nc * sizeof(int) : 0}};
         int r2 = upload_params(ctx, up);
         if (r2) return r2;
-        MlmcArgs g;
+        MlmcBridgeArgs g;
         std::memset(&g, 0, sizeof(g));
         g.f.n_paths = n;
         g.f.n_steps = n_fine;
@@ -305,23 +481,39 @@ static int run_mlmc_level(mcg_ctx* ctx, double S0, double r, double q, const dou
         g.first_obs = lv->first_obs;
         g.nd_f = (double)(n_fine / lv->stride_fine + 1 - lv->first_obs);
         g.nd_c = coarse ? (double)(n_coarse / lv->stride_coarse + 1 - lv->first_obs) : 1.0;
+        for (int l = 0; l < ML_L_MAX && n_live; ++l) {
+            const int src = std::min(l, n_live - 1);
+            g.h[l] = std::log(plan->barrier[src] / S0);
+            if (plan->up[src]) g.up_mask |= 1u << l;
+        }
+        g.n_live = n_live;
+        g.surv = d_surv;
+        const int nl = n_live <= 2 ? n_live : ML_L_MAX;  // 0, 1, 2 or 4 slots
         r2 = PathLaunch{ctx, n_gen}.run(MCG_K_LOCALVOL, [&] {
             dispatch_flags(
-                [&](auto coarse_, auto one_slice) {
-                    hipLaunchKernelGGL((k_mlmc_localvol_level<coarse_.value, one_slice.value>), dim3((unsigned)n_gen), dim3(256), 0, ctx->stream, g);
+                [&](auto coarse_, auto one_slice, auto milstein_, auto hi, auto lo) {
+                    constexpr int NL = hi.value ? (lo.value ? ML_L_MAX : 2) : (lo.value ? 1 : 0);
+                    hipLaunchKernelGGL((k_mlmc_localvol_level<coarse_.value, one_slice.value, milstein_.value, NL>), dim3((unsigned)n_gen),
+                                       dim3(256), 0, ctx->stream, static_cast<const MlmcArgsOf<NL>&>(g));
                 },
-                coarse, n_t == 1);
+                coarse, n_t == 1, milstein, nl >= 2, nl == 1 || nl == ML_L_MAX);
         });
         if (r2) return r2;
         {
             TimedLaunch t(ctx, MCG_K_EXOTIC, 2);
-            hipLaunchKernelGGL(k_mlmc_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, coarse ? 1 : 0,
-                               reinterpret_cast<const mcg_exotic*>(up[2].at), nc, d_part);
+            if (plan)
+                hipLaunchKernelGGL(k_mlmc_book_bridge, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, d_surv, n_live, n,
+                                   coarse ? 1 : 0, reinterpret_cast<const mcg_exotic*>(up[2].at), reinterpret_cast<const int*>(up[3].at), nc,
+                                   d_part);
+            else
+                hipLaunchKernelGGL(k_mlmc_book, dim3(n_blocks, n_chunks), dim3(256), 0, ctx->stream, d_stats, n, coarse ? 1 : 0,
+                                   reinterpret_cast<const mcg_exotic*>(up[2].at), nc, d_part);
             hipLaunchKernelGGL((k_book_reduce<ML_CH, ML_NS>), dim3(n_chunks), dim3(256), 0, ctx->stream, d_part, n_blocks, nc, (double)n, d_sums);
         }
         MCG_HIP(hipGetLastError());
         MCG_HIP(hipMemcpyAsync(sums, d_sums, n_sums * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (host_stats10) MCG_HIP(hipMemcpyAsync(host_stats10, d_stats, n_stats * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (host_surv && n_surv) MCG_HIP(hipMemcpyAsync(host_surv, d_surv, n_surv * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         MCG_HIP(hipStreamSynchronize(ctx->stream));
         return MCG_OK;
     };
@@ -335,9 +527,9 @@ static int run_mlmc_level(mcg_ctx* ctx, double S0, double r, double q, const dou
 
 using namespace mcg;
 
-int mcg_mlmc_localvol_level(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max,
-                            int n_x, const double* sigma, double T, const mcg_mlmc_level* lv, const mcg_exotic* book, int n_contracts,
-                            double* sums, double* host_stats10) {
+int mcg_mlmc_localvol_level_ex(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max,
+                               int n_x, const double* sigma, double T, const mcg_mlmc_level* lv, int scheme, int bridge,
+                               const mcg_exotic* book, int n_contracts, double* sums, double* host_stats10, double* host_surv) {
     // (the model and the level are checked before the ctx: what is wrong with them is reported on a machine without a GPU too)
     if (!lv || !book || !sums) return fail(MCG_ERR_INVALID, "mlmc: lv/book/sums is NULL");
     int rc = mlmc_check_level(lv, T);
@@ -351,8 +543,24 @@ int mcg_mlmc_localvol_level(mcg_ctx* ctx, double S0, double r, double q, const d
         rc = exotic_contract_check(book[c], "contract", c);
         if (rc) return rc;
     }
+    rc = mlmc_check_scheme(scheme, bridge);
+    if (rc) return rc;
+    MlmcBridgePlan plan;
+    if (bridge) {
+        plan.slot.resize((size_t)n_contracts);
+        rc = mlmc_bridge_plan(book, n_contracts, plan.barrier, plan.up, plan.slot.data(), &plan.n_levels);
+        if (rc) return rc;
+    }
     if (lv->n_paths < 1) return fail(MCG_ERR_EMPTY_PATHS, "mlmc: no paths on this level");
     if (!ctx) return fail(MCG_ERR_INVALID, "ctx is NULL");
     MCG_HIP(hipSetDevice(ctx->device));
-    return run_mlmc_level(ctx, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, T, lv, book, n_contracts, sums, host_stats10);
+    return run_mlmc_level(ctx, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, T, lv, scheme == MCG_MLMC_MILSTEIN, bridge ? &plan : nullptr,
+                          book, n_contracts, sums, host_stats10, host_surv);
+}
+
+int mcg_mlmc_localvol_level(mcg_ctx* ctx, double S0, double r, double q, const double* times, int n_t, double x_min, double x_max,
+                            int n_x, const double* sigma, double T, const mcg_mlmc_level* lv, const mcg_exotic* book, int n_contracts,
+                            double* sums, double* host_stats10) {
+    return mcg_mlmc_localvol_level_ex(ctx, S0, r, q, times, n_t, x_min, x_max, n_x, sigma, T, lv, MCG_MLMC_LOG_EULER, 0, book, n_contracts,
+                                      sums, host_stats10, nullptr);
 }

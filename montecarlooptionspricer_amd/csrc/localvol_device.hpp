@@ -37,4 +37,24 @@ __device__ __forceinline__ void localvol_step(const LocalVolArgs& a, const doubl
     S = fm::scaled_exp(S, e);
 }
 
+// The step of mcg_mlmc_localvol_level_ex: localvol_step's lookup and, with MILSTEIN, the correction (s / 2) (ds / dX) (z z - 1)
+// from the slope of the bilinear table, zero where the lookup clamps.  Returns the step volatility s.
+template <bool MILSTEIN>
+__device__ __forceinline__ double localvol_step_vol(const LocalVolArgs& a, const double2* sl, double z, double& S, double& X) {
+    const double uu = __builtin_fma(X, a.inv_dx, a.u0);
+    const double u = __builtin_fmin(__builtin_fmax(uu, 0.0), a.u_max);
+    const int j = min((int)u, a.nx1 - 1);
+    const double f = u - (double)j;
+    const double2 ad = sl[j];
+    const double s = __builtin_fma(f, ad.y, ad.x);
+    double e = __builtin_fma(s, z, __builtin_fma(-0.5 * s, s, a.m));
+    if constexpr (MILSTEIN) {
+        const double g = (uu > 0.0 && uu < a.u_max) ? ad.y * a.inv_dx : 0.0;
+        e = __builtin_fma((0.5 * s) * g, __builtin_fma(z, z, -1.0), e);
+    }
+    X = X + e;
+    S = fm::scaled_exp(S, e);
+    return s;
+}
+
 }  // namespace mcg

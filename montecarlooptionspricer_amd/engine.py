@@ -606,34 +606,49 @@ class PathEngine:
 
     def mlmc_level(self, seed: int, S0: float, r: float, surface: "LocalVolSurface", T: float, book, n_fine: int, n_paths: int,
                    has_coarse: bool = True, stride_fine: int = 1, stride_coarse: int = 1, first_obs: int = 1, path_begin: int = 0,
-                   q: float = 0.0, return_stats: bool = False):
+                   q: float = 0.0, return_stats: bool = False, scheme: str = "euler", bridge: bool = False,
+                   return_survival: bool = False):
         """One level of multilevel Monte Carlo under local volatility in one launch (mcg_mlmc_localvol_level): a fine path of
         n_fine steps over [0, T] and, with has_coarse, a coarse one of n_fine / 2 steps from the same Brownian path, both reduced
         to the five statistics of path_stats in registers; no matrix is stored.  Returns sums[6 n + 1] = {sum Y, sum Y^2,
         sum P_f, sum P_f^2, sum P_c, sum P_c^2} per contract of `book` (Y = P_f - P_c), then the path count; with return_stats
-        (sums, stats10): [10][n_paths], the fine statistics then the coarse ones ([5][n_paths] without a coarse path)."""
+        (sums, stats10): [10][n_paths], the fine statistics then the coarse ones ([5][n_paths] without a coarse path).
+        scheme "milstein" adds the Milstein correction to both grids' steps; bridge samples the barrier contracts from the
+        Brownian-bridge survival probability of their level along each grid (continuous monitoring; at most four distinct
+        levels, mlmc_bridge_levels(book) lists them) -- mcg_mlmc_localvol_level_ex.  return_survival appends surv[(1 or 2)
+        n_levels][n_paths] to the result: P per level on the fine grid, then on the coarse one (no rows without bridge)."""
         arr = make_book(book)
         n = len(arr)
         dp = C.POINTER(C.c_double)
+        if scheme not in N.MLMC_SCHEMES:
+            raise McgError(f"mlmc: scheme must be one of {sorted(N.MLMC_SCHEMES)} (got {scheme!r})", 1)
         lv = N.MlmcLevel(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_fine), int(bool(has_coarse)), int(stride_fine), int(stride_coarse),
                          int(first_obs), int(path_begin) & 0xFFFFFFFFFFFFFFFF, int(n_paths))
         sums = np.empty(6 * n + 1)
         stats = np.empty((10 if has_coarse else 5, max(int(n_paths), 0))) if return_stats else None
-        check(self._L.mcg_mlmc_localvol_level(self._ctx, S0, r, q, surface.times.ctypes.data_as(dp), surface.n_t, surface.x_min,
-                                              surface.x_max, surface.n_x, surface.sigma.ctypes.data_as(dp), T, C.byref(lv), arr, n,
-                                              sums.ctypes.data_as(dp), stats.ctypes.data_as(dp) if return_stats else None))
-        return (sums, stats) if return_stats else sums
+        surv = None
+        if return_survival:
+            n_levels = len(mlmc_bridge_levels(book)) if bridge else 0
+            surv = np.empty(((2 if has_coarse else 1) * n_levels, max(int(n_paths), 0)))
+        check(self._L.mcg_mlmc_localvol_level_ex(self._ctx, S0, r, q, surface.times.ctypes.data_as(dp), surface.n_t, surface.x_min,
+                                                 surface.x_max, surface.n_x, surface.sigma.ctypes.data_as(dp), T, C.byref(lv),
+                                                 N.MLMC_SCHEMES[scheme], int(bool(bridge)), arr, n, sums.ctypes.data_as(dp),
+                                                 stats.ctypes.data_as(dp) if return_stats else None,
+                                                 surv.ctypes.data_as(dp) if return_survival and surv.size else None))
+        out = (sums,) + ((stats,) if return_stats else ()) + ((surv,) if return_survival else ())
+        return out if len(out) > 1 else sums
 
     def mlmc_local_vol(self, seed: int, S0: float, r: float, surface: "LocalVolSurface", T: float, book, eps: float, n0: int = 4,
                        n_obs: Optional[int] = None, first_obs: int = 1, q: float = 0.0, n_pilot: int = 10_000, l_min: int = 2,
-                       l_max: int = 10) -> "MlmcResult":
+                       l_max: int = 10, scheme: str = "euler", bridge: bool = False) -> "MlmcResult":
         """The multilevel estimator of a price_exotics book under local volatility, to a root-mean-square error of about eps
         (undiscounted bias below eps / sqrt(2) by the estimate of mlmc_plan, variance eps^2 / 2 by Giles' rule).  Level l has
         n0 2^l fine steps (level 0 no coarse path) and draws with the Philox key seed + l (mod 2^64); every level starts with
         n_pilot paths, and further batches of a level continue at path_begin = paths already drawn, so the result is a function
         of the arguments alone.  The path counts are those of the worst contract of the book.  Levels l_min + 1, ... are added
         until every contract's bias test passes or l_max is reached (converged False then; no error).  n_obs None monitors each
-        grid's own rows; an integer monitors that many equidistant dates on every grid and must divide n0 / 2."""
+        grid's own rows; an integer monitors that many equidistant dates on every grid and must divide n0 / 2.  scheme and
+        bridge are mlmc_level's: with bridge the barrier contracts are continuously monitored ones, whatever n_obs is."""
         n = len(book)
         if not (eps > 0.0) or not math.isfinite(eps):
             raise McgError("mlmc: eps must be finite and > 0", 1)
@@ -650,7 +665,7 @@ class PathEngine:
             n_coarse = n_fine // 2
             sf, sc = (1, 1) if n_obs is None else (n_fine // n_obs, max(n_coarse // n_obs, 1))
             s = self.mlmc_level((seed + l) & 0xFFFFFFFFFFFFFFFF, S0, r, surface, T, book, n_fine, count, has_coarse=l > 0,
-                                stride_fine=sf, stride_coarse=sc, first_obs=first_obs, path_begin=paths[l], q=q)
+                                stride_fine=sf, stride_coarse=sc, first_obs=first_obs, path_begin=paths[l], q=q, scheme=scheme, bridge=bridge)
             sums[l] += s[:-1].reshape(n, 6)
             paths[l] += count
 
@@ -1098,6 +1113,16 @@ def mlmc_combine(sum_y, sum_y2, n, r: float, T: float) -> Tuple[float, float]:
     price, se = C.c_double(), C.c_double()
     check(L.mcg_mlmc_combine(a.ctypes.data_as(dp), b.ctypes.data_as(dp), c.ctypes.data_as(dp), len(a), r, T, C.byref(price), C.byref(se)))
     return price.value, se.value
+
+
+def mlmc_bridge_levels(book):
+    """The distinct bridge levels [(barrier, is_up), ...] of a price_exotics book in the order mlmc_level(bridge=True) holds them
+    (mcg_mlmc_bridge_levels; host only): the barrier contracts' (barrier, up), compared bitwise, by first appearance; a down
+    barrier at zero is never touched and takes no level.  Raises McgError for more than four levels or a barrier <= 0 otherwise."""
+    arr = make_book(book)
+    b, up, n = np.empty(N.MLMC_BRIDGE_L_MAX), (C.c_int * N.MLMC_BRIDGE_L_MAX)(), C.c_int(0)
+    check(N.load_library().mcg_mlmc_bridge_levels(arr, len(arr), b.ctypes.data_as(C.POINTER(C.c_double)), up, C.byref(n)))
+    return [(float(b[l]), bool(up[l])) for l in range(n.value)]
 
 
 def mlmc_plan(n, mean, var, cost, eps: float):

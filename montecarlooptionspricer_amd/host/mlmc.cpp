@@ -1,9 +1,11 @@
-// The host side of multilevel Monte Carlo (include/mcgpu.h: mcg_mlmc_combine, mcg_mlmc_plan) and what mcg_mlmc_localvol_level
-// rejects of a level's shape.  A host translation unit: no FMA contraction here, so the formulas below, written in any
+// The host side of multilevel Monte Carlo (include/mcgpu.h: mcg_mlmc_combine, mcg_mlmc_plan, mcg_mlmc_bridge_levels) and what
+// mcg_mlmc_localvol_level and mcg_mlmc_localvol_level_ex reject of a level's shape, the scheme and the book's bridge levels
+// (host/mlmc.hpp).  A host translation unit: no FMA contraction here, so the formulas below, written in any
 // language's binary64 in the same order, give the same bits.
 #include <cmath>
+#include <cstring>
 
-#include "../../include/mcgpu.h"
+#include "mlmc.hpp"
 
 namespace mcg {
 int fail(int status, const char* fmt, ...);
@@ -22,6 +24,49 @@ int mlmc_check_level(const mcg_mlmc_level* lv, double T) {
     return MCG_OK;
 }
 
+int mlmc_check_scheme(int scheme, int bridge) {
+    if (scheme != MCG_MLMC_LOG_EULER && scheme != MCG_MLMC_MILSTEIN)
+        return fail(MCG_ERR_INVALID, "mlmc: scheme must be 0 (log-Euler) or 1 (Milstein) (got %d)", scheme);
+    if (bridge != 0 && bridge != 1) return fail(MCG_ERR_INVALID, "mlmc: bridge must be 0 or 1 (got %d)", bridge);
+    return MCG_OK;
+}
+
+// The bridge levels of a book: (barrier, up) of its barrier contracts, compared bitwise, in the order of first appearance.
+// slot (may be null) [n_contracts]: the level of a barrier contract, MLMC_SLOT_UNTOUCHED for a down barrier at zero,
+// MLMC_SLOT_NONE for a contract of another kind.
+int mlmc_bridge_plan(const mcg_exotic* book, int n_contracts, double* barriers, int* is_up, int* slot, int* n_levels) {
+    int n = 0;
+    for (int c = 0; c < n_contracts; ++c) {
+        const mcg_exotic& x = book[c];
+        if (x.kind < MCG_X_ASIAN_ARITH_FIXED || x.kind > MCG_X_BARRIER_DOWN_IN)
+            return fail(MCG_ERR_INVALID, "contract %d: kind must be in [0, 9] (got %d)", c, x.kind);
+        int s = MLMC_SLOT_NONE;
+        if (x.kind >= MCG_X_BARRIER_UP_OUT) {
+            const int up = x.kind == MCG_X_BARRIER_UP_OUT || x.kind == MCG_X_BARRIER_UP_IN;
+            if (!std::isfinite(x.barrier)) return fail(MCG_ERR_INVALID, "contract %d: barrier must be finite", c);
+            if (!up && x.barrier == 0.0) {
+                s = MLMC_SLOT_UNTOUCHED;
+            } else if (!(x.barrier > 0.0)) {
+                return fail(MCG_ERR_INVALID, "contract %d: a bridge level needs a barrier > 0, or a down barrier at 0 (got %s %g)", c,
+                            up ? "up" : "down", x.barrier);
+            } else {
+                for (s = 0; s < n; ++s)
+                    if (std::memcmp(&barriers[s], &x.barrier, sizeof(double)) == 0 && is_up[s] == up) break;
+                if (s == n) {
+                    if (n == MCG_MLMC_BRIDGE_L_MAX)
+                        return fail(MCG_ERR_INVALID, "contract %d: more than %d distinct bridge levels in one call", c, MCG_MLMC_BRIDGE_L_MAX);
+                    barriers[n] = x.barrier;
+                    is_up[n] = up;
+                    ++n;
+                }
+            }
+        }
+        if (slot) slot[c] = s;
+    }
+    *n_levels = n;
+    return MCG_OK;
+}
+
 // what both host entry points reject of a table of levels
 static int mlmc_check_levels(const char* who, int n_levels, const double* n) {
     if (n_levels < 1 || n_levels > MCG_MLMC_MAX_LEVELS)
@@ -34,6 +79,12 @@ static int mlmc_check_levels(const char* who, int n_levels, const double* n) {
 }  // namespace mcg
 
 using namespace mcg;
+
+extern "C" int mcg_mlmc_bridge_levels(const mcg_exotic* book, int n_contracts, double* barriers, int* is_up, int* n_levels) {
+    if (!book || !barriers || !is_up || !n_levels) return fail(MCG_ERR_INVALID, "mlmc bridge levels: book/barriers/is_up/n_levels is NULL");
+    if (n_contracts < 1 || n_contracts > 1024) return fail(MCG_ERR_INVALID, "n_contracts must be in [1, 1024] (got %d)", n_contracts);
+    return mlmc_bridge_plan(book, n_contracts, barriers, is_up, nullptr, n_levels);
+}
 
 extern "C" int mcg_mlmc_combine(const double* sum_y, const double* sum_y2, const double* n, int n_levels, double r, double T,
                                 double* price, double* std_err) {
